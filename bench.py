@@ -20,6 +20,11 @@ when data parallel). Rank 0 prints ONE JSON line:
   * `roofline`: the headline's dominant kernel timed live with HIP events; `cpu_baseline`: the
     oracle's restatement of the same step on the host cores.
 `python bench.py --model <name>` benches one workload only (profiling helper; not the driver line).
+`--dump-outputs DIR`: rank 0 writes what the last timed step of the line's `value` record computed — loss, parameters
+after the update and the gradient of the flat buffer — as DIR/<name>.npy (float32), so that two builds can be compared
+output for output; the inputs and initial weights are seeded, identical from run to run for the same arguments. The
+fused attention backward sums dQ in arrival order (ops.set_deterministic), so last bits differ run to run; Adam turns
+those of the entries whose true gradient is 0 (the key half of every attention `_kv.bias`) into +-lr steps.
 """
 
 import argparse
@@ -39,6 +44,7 @@ import torch.distributed as dist  # noqa: E402
 BF16_PEAK_TFLOPS = 2500.0  # dense bf16 MFMA peak (MI355X_MICROARCH.md)
 FP32_PEAK_TFLOPS = 157.3  # MI355X_MICROARCH.md: dense fp32 matrix == vector peak (no TF32 on gfx950)
 LN2 = 0.6931471805599453
+DUMP_MAX_BYTES = 60_000_000  # --dump-outputs: all arrays together (under 64 MB with the .npy headers)
 
 
 def _attn_flops_per_pair(dk, dv):
@@ -221,7 +227,7 @@ class _Watchdog:
 
 
 def run_workload(env, name, batch, steps, warmup, use_graph=True, require_graph=False, min_seconds=0.0,
-                 same_batch=False, single=False, keep_params=False, x_override=None):
+                 same_batch=False, single=False, keep_params=False, x_override=None, dump=False):
     """Builds the model, captures the step and times EXACTLY `steps` steps between barriers
     (max over ranks). Returns the record of this workload at this per-GPU batch.
 
@@ -229,7 +235,7 @@ def run_workload(env, name, batch, steps, warmup, use_graph=True, require_graph=
     of enough steps to fill `min_seconds` is timed and reported instead (`timed_steps` says how many).
     same_batch: every rank trains on RANK 0's batch (--dp-parity); single: no gradient exchange even when the job has
     several ranks (the 1-GPU replica --dp-parity compares with); keep_params: rec["_flat_param"] = the parameters after
-    the last step."""
+    the last step; dump: rec["_dump"] = the arrays the last timed step left to its caller (host float32 copies)."""
     import pytorch_generative_amd as pg
     from pytorch_generative_amd import graph, ops, optim, parallel
 
@@ -353,6 +359,10 @@ def run_workload(env, name, batch, steps, warmup, use_graph=True, require_graph=
     if keep_params:
         torch.cuda.synchronize()
         rec["_flat_param"] = opt.flat_param.detach().clone()
+    if dump:  # the step's return value and what it updated in place (the gradient stays in the flat buffer until the next step)
+        torch.cuda.synchronize()
+        rec["_dump"] = {"loss": loss.detach().float().reshape(1).cpu(), "params": opt.flat_param.detach().cpu(),
+                        "grads": opt.flat_grad.detach().cpu()}
     if "gflop_causal" in w:  # attention counted on the allowed pairs only (what the kernels execute)
         rec["step_tflops"] = value * w["gflop_causal"] / 1e3
         rec["step_frac_of_fp32_peak"] = rec["step_tflops"] / env.world / FP32_PEAK_TFLOPS
@@ -726,6 +736,30 @@ OTHER_CONFIGS = [  # (record key, workload, per-GPU batch, BASELINE.json config)
 ]
 
 
+def write_dump(directory, arrays):
+    """--dump-outputs: arrays (name -> float32 CPU tensor) as directory/<name>.npy. Past DUMP_MAX_BYTES in all, every
+    array above an equal share of the budget is replaced by a fixed sample of its entries (seeded, sorted indices: the
+    same positions in every run of the same arguments). Returns {name: what was written}."""
+    import numpy as np
+
+    os.makedirs(directory, exist_ok=True)
+    share = DUMP_MAX_BYTES // max(len(arrays), 1)
+    total = sum(t.numel() * 4 for t in arrays.values())
+    info = {}
+    for name, t in arrays.items():
+        flat = t.detach().float().reshape(-1)
+        n = flat.numel()
+        if total > DUMP_MAX_BYTES and n * 4 > share:
+            keep = share // 4
+            idx = torch.randperm(n, generator=torch.Generator().manual_seed(0))[:keep].sort().values
+            t = flat[idx]
+            info[name] = {"shape": [keep], "sampled_from": n}
+        else:
+            info[name] = {"shape": list(t.shape)}
+        np.save(os.path.join(directory, name + ".npy"), t.float().numpy())
+    return info
+
+
 def _self_spawn(n):
     """`python bench.py --gpus N` without a launcher: start one process per GPU ourselves (the same command with
     RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set, rendezvous on 127.0.0.1), forward rank 0's JSON line, return the
@@ -782,7 +816,7 @@ def dp_parity(env, args, run):
 
     was = ops.set_deterministic(True)
     name = args.model or "image_gpt"
-    dp = run(name, args.batch, same_batch=True, keep_params=True)
+    dp = run(name, args.batch, same_batch=True, keep_params=True, dump=bool(args.dump_outputs))
     one = run(name, args.batch, same_batch=True, single=True, keep_params=True)
     ops.set_deterministic(was)
     # SURVEY.md section 8(e)'s second equality: N DISTINCT shards == the 1-GPU step on the concatenated batch (loss = mean of the
@@ -817,7 +851,9 @@ def dp_parity(env, args, run):
     vs_root, vs_one, pmax = (float(v) for v in stats)
     pow2 = env.world & (env.world - 1) == 0
     ok = vs_root == 0.0 and (vs_one == 0.0 if pow2 else vs_one <= 1e-6 * pmax) and shard_ok
+    dumped = dp.pop("_dump", None)
     if env.rank == 0:
+        dump_info = write_dump(args.dump_outputs, dumped) if dumped is not None else None
         digest = lambda t: hashlib.sha256(t.cpu().numpy().tobytes()).hexdigest()[:16]  # noqa: E731
         print(json.dumps({
             "metric": f"training images/sec ({w['ctor']}, {w['chw'][1]}x{w['chw'][2]}x{w['chw'][0]}) with the data-parallel "
@@ -847,6 +883,7 @@ def dp_parity(env, args, run):
             "launch_by_rank": dp["launch_by_rank"],
             "one_rank_run": {"images_per_s": one["images_per_s"], "ms_per_step": one["ms_per_step"], "launch": one["launch"]},
             "scaling_efficiency_vs_n1": dp["images_per_s"] / (env.world * one["images_per_s"]),
+            **({"dump_outputs": {"dir": args.dump_outputs, "files": dump_info}} if dump_info is not None else {}),
         }), flush=True)
     if not ok:
         raise SystemExit(f"--dp-parity FAILED on rank {env.rank}: |p - p_rank0| = {vs_root:.3e}, |p - p_1rank| = {vs_one:.3e}, "
@@ -876,6 +913,9 @@ def main():
                          "of the same steps; prints ONE JSON line with dp_parity and the job's rate")
     ap.add_argument("--require-graph", action="store_true",
                     help="exit non-zero if hipGraph capture fails on any rank instead of falling back to eager")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, rank 0 writes the last timed step's loss, updated parameters and gradient "
+                         "of the line's `value` record as DIR/<name>.npy (float32, at most 64 MB in all)")
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(_self_spawn(args.gpus))
@@ -893,8 +933,10 @@ def main():
 
     if args.model is not None:  # single-workload helper line
         w = WORKLOADS[args.model]
-        rec = run(args.model, args.batch)
+        rec = run(args.model, args.batch, dump=bool(args.dump_outputs))
+        dumped = rec.pop("_dump", None)
         if env.rank == 0:
+            dump_info = write_dump(args.dump_outputs, dumped) if dumped is not None else None
             print(json.dumps({
                 "metric": f"training images/sec ({w['ctor']}, {w['chw'][1]}x{w['chw'][2]}x{w['chw'][0]})",
                 "value": rec["images_per_s"], "unit": "images/s", "n_gpus": env.world, "steps": args.steps,
@@ -905,12 +947,17 @@ def main():
                            "per_gpu_batch": args.batch, "global_batch": args.batch * env.world,
                            "parallelism": f"dp{env.world}", "launch": rec["launch"],
                            "graph_fallback": rec["graph_fallback"]},
-                "record": rec}), flush=True)
+                "record": rec,
+                **({"dump_outputs": {"dir": args.dump_outputs, "files": dump_info}} if dump_info is not None else {})}),
+                flush=True)
         if env.world > 1:
             dist.destroy_process_group()
         return
 
-    head = run("image_gpt", args.batch)
+    head = run("image_gpt", args.batch, dump=bool(args.dump_outputs))
+    dumped = head.pop("_dump", None)
+    if dumped is not None and env.rank == 0:
+        head_dump = {"dir": args.dump_outputs, "files": write_dump(args.dump_outputs, dumped)}
     extras = {}
     if not args.no_extras:
         extras["imagegpt_b64"] = run("image_gpt", 64)
@@ -958,6 +1005,8 @@ def main():
             "grad_exchange": head["grad_exchange"],
             "per_rank_images_per_s": head["per_rank_images_per_s"],
         }
+        if dumped is not None:
+            out["dump_outputs"] = head_dump
         if args.n1_value:  # the driver computes efficiency itself; this is a convenience for manual runs
             out["scaling_efficiency_vs_n1"] = head["images_per_s"] / (env.world * args.n1_value)
         if "imagegpt_b64" in extras:

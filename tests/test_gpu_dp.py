@@ -55,7 +55,9 @@ def _run_world2(mode, out, kind="igpt"):
 @pytest.mark.parametrize("mode,kind", [("same", "igpt"), ("shard", "igpt"), ("shard", "gated"), ("same", "snail"),
                                        ("shard", "snail"), ("same", "vd_vae")])
 def test_two_ranks_equal_one_gpu(tmp_path, mode, kind):
-    want, want_losses, want_lr = _single_gpu_reference(kind, deterministic=mode == "same")
+    # both modes on the bit-reproducible kernels: the fused attention backwards' arrival-order dQ sums would add run-to-run
+    # noise that Adam amplifies on top of the summation-order difference the "shard" tolerance below accounts for
+    want, want_losses, want_lr = _single_gpu_reference(kind, deterministic=True)
     got = _run_world2(mode, str(tmp_path / f"dp_{mode}.pt"), kind)
     if kind == "gated":  # parameters that never receive a gradient stay exactly where the broadcast put them
         import dp_worker
@@ -77,7 +79,7 @@ def test_two_ranks_equal_one_gpu(tmp_path, mode, kind):
             assert float((g - w).abs().max()) <= 3 * 2 * 5e-3, k
             continue
         d, pmax = float((g - w).abs().max()), float(w.abs().max().clamp_min(1e-12))
-        # "same" (bit-reproducible kernels on both sides): equal up to the rounding of the flat all-reduce; "shard": the two
+        # "same": equal up to the rounding of the flat all-reduce; "shard": the two
         # half-batch gradients are summed in another order than the 1-GPU kernels sum the whole batch (~1e-6 of a tensor's
         # max), and Adam's normalised update turns a RELATIVE change e of a gradient entry into e * lr per step — small
         # entries (1e-3 of the max) therefore move by a few 1e-3 * lr per step, independent of the parameter's own scale
@@ -156,7 +158,9 @@ def test_bench_py_dp_parity_mode():
     env = dict(os.environ, PG_FORCE_DEVICE="0", PG_DIST_BACKEND="gloo")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
-    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
+    # 20 timed steps: scaling_efficiency_vs_n1 is the ratio of two timed windows, and a window of a few steps at batch 16
+    # (a few ms) is at the mercy of how the two processes sharing the GPU happen to be scheduled
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "1",
                         "--batch", "16", "--dp-parity"],
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert p.returncode == 0, p.stderr.decode(errors="replace")[-4000:]

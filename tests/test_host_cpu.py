@@ -322,6 +322,34 @@ def test_bench_self_spawn_watches_all_ranks(tmp_path, monkeypatch):
     assert time.monotonic() - t0 < 30, "a dead rank must not leave the launcher waiting for the survivors"
 
 
+
+def test_bench_dump_outputs_files_and_budget(tmp_path, monkeypatch):
+    """bench.py --dump-outputs (bench.write_dump): one float32 DIR/<name>.npy per array, exact when the arrays fit the
+    budget; past it, every array above its share is a seeded sample of its entries — the same positions in every call
+    (and in every array of that length), and all files together stay under 64 MB."""
+    import importlib.util
+
+    import numpy as np
+
+    spec = importlib.util.spec_from_file_location("pg_bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    g = torch.Generator().manual_seed(5)
+    small = {"loss": torch.tensor([1.5]), "params": torch.randn(1000, generator=g), "grads": torch.randn(1000, generator=g)}
+    info = bench.write_dump(str(tmp_path / "a"), small)
+    for k, v in small.items():
+        got = np.load(tmp_path / "a" / f"{k}.npy")
+        assert got.dtype == np.float32 and info[k] == {"shape": list(v.shape)} and np.array_equal(got, v.numpy())
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 3 * 4 * 100)  # a 300-entry budget: 100 entries per array
+    big = {"loss": torch.tensor([2.0]), "params": torch.arange(1000.0), "grads": -torch.arange(1000.0)}
+    for d in ("b", "c"):
+        info = bench.write_dump(str(tmp_path / d), big)
+    assert info["loss"] == {"shape": [1]} and info["params"] == {"shape": [100], "sampled_from": 1000}
+    p_b, p_c = np.load(tmp_path / "b" / "params.npy"), np.load(tmp_path / "c" / "params.npy")
+    assert np.array_equal(p_b, p_c) and np.array_equal(np.load(tmp_path / "b" / "grads.npy"), -p_b)
+    assert len(np.unique(p_b)) == 100 and np.all(np.diff(p_b) > 0)  # distinct entries, kept in order
+    assert sum(np.load(f).nbytes for f in (tmp_path / "b").glob("*.npy")) <= 3 * 4 * 100
+
 # Which kernel family a convolution shape is sent to (csrc/conv_mfma.hip pg_conv_mfma_supported: a host function, no GPU needed).
 # 0 = the VALU tap kernel, 1 = fp32 MFMA fragments (conv_mfma_kernel), 2 = bf16x3 fragments (conv_b3*). The shapes are the layers the
 # eight bench workloads launch (DESIGN.md section 3's kernel table); a change here moves a model onto another kernel, so it should be a
