@@ -240,6 +240,35 @@ int pg_causal_attn_bwd_dkv(const float* q, const float* k, const float* v, const
  * Initial value: 1, or the environment's PG_ATTN_FUSED_BWD at load time. */
 int pg_attn_fused_bwd(int enable);
 
+/* ---------------------------------------------------------------------------------------
+ * Linear causal attention (O(L) memory).  nn/attention.py:168-195 (_UnnormalizedLinearCausalAttention
+ * forward / backward: the per-position loops) and :256-275 (LinearCausalAttention.forward):
+ *   num[l] = phi(q[l]) . sum_{j <= l} phi(k[j])^T v[j]            (inclusive of j = l)
+ *   den[n,h,l] = 1 / (sum_i phi(q)[n,h,l,i] * sum_{h' <= h} phi(k)[n,h',l,i] + 1e-10)
+ *   out = num * den
+ * The denominator's cumsum runs over the HEADS axis, as the reference's
+ * einsum("nlhi,nlhi->nlh", Q, K.cumsum(1)) on (N, heads, L, d) tensors does (not causal over positions).
+ * q: (N, heads*dk, L), k / v: views of the _kv output (N, heads*dk + heads*dv, L), out: (N, heads*dv, L);
+ * head h owns channels [h*d, (h+1)*d) (_to_multihead). *_bs = batch stride in floats (k, v, dk, dv share
+ * kv_bs; g shares o_bs; dq shares q_bs). den: (N, heads, L), written by _fwd, read by _bwd.
+ * feature: PG_FEATURE_ELU1 applies phi = elu + 1 to q and k inside the kernels (the reference's default
+ * feature_fn; the backward recomputes phi and phi' from the raw q, k); PG_FEATURE_IDENTITY takes q and k as
+ * already mapped (a custom feature_fn applied by the caller). Chunked prefix-state scans on fp32 MFMAs
+ * (linear_attention.hip); deterministic (no atomics). dk, dv in [1, 64] (PG_ESHAPE otherwise), any L >= 1.
+ * ws: workspace of pg_linear_attn_workspace_floats(..., backward) floats, caller-allocated (0 floats: may be NULL).
+ * _bwd writes dq, dk, dv (not accumulated).
+ * ------------------------------------------------------------------------------------- */
+#define PG_FEATURE_IDENTITY 0
+#define PG_FEATURE_ELU1 1
+size_t pg_linear_attn_workspace_floats(int N, int heads, int L, int dk, int dv, int backward);
+int pg_linear_attn_fwd(const float* q, const float* k, const float* v, float* out, float* den, float* ws,
+                       size_t ws_floats, int N, int heads, int L, int dk, int dv, long q_bs, long kv_bs,
+                       long o_bs, int feature, void* stream);
+int pg_linear_attn_bwd(const float* q, const float* k, const float* v, const float* out, const float* den,
+                       const float* g, float* dq, float* dk, float* dv, float* ws, size_t ws_floats, int N,
+                       int heads, int L, int dk_dim, int dv_dim, long q_bs, long kv_bs, long o_bs, int feature,
+                       void* stream);
+
 /* (N,2,H,W) pixel-coordinate encoding, nn/attention.py:37-57 (torch.arange(-.5,.5,1/h)). */
 int pg_image_positional_encoding(float* out, int N, int H, int W, void* stream);
 

@@ -1,6 +1,6 @@
 """MI355X-native building blocks with the pytorch_generative.nn operator surface."""
 
-from pytorch_generative_amd.nn.attention import CausalAttention, image_positional_encoding
+from pytorch_generative_amd.nn.attention import CausalAttention, LinearCausalAttention, image_positional_encoding
 from pytorch_generative_amd.nn.convolution import (
     CausalConv2d,
     Conv2d,
@@ -13,6 +13,7 @@ from pytorch_generative_amd.nn.utils import VectorQuantizer
 
 __all__ = [
     "CausalAttention",
+    "LinearCausalAttention",
     "image_positional_encoding",
     "CausalConv2d",
     "Conv2d",

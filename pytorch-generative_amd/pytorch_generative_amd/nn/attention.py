@@ -1,13 +1,14 @@
 """Attention-side operators of the hot path, on hand-written gfx950 kernels.
 
-Mirrors CausalAttention (reference nn/attention.py:66-161) and image_positional_encoding
-(:37-57). The L x L score / mask tensors of the reference are never materialised.
+Mirrors CausalAttention (reference nn/attention.py:66-161), LinearCausalAttention (:168-275) and
+image_positional_encoding (:37-57). The L x L score / mask tensors of the reference are never materialised.
 """
 
 import functools
 
 import torch
 from torch import nn
+from torch.nn import functional as F
 
 from pytorch_generative_amd import ops
 from pytorch_generative_amd.nn.convolution import Conv2d
@@ -128,3 +129,55 @@ class CausalAttention(nn.Module):
             q, kv, self._n_heads, self._embed_channels, self._out_channels, self._mask_center
         )
         return self._proj(out, res=res)
+
+
+def _elu_plus_one(x):
+    """The reference's default feature map, `lambda x: F.elu(x) + 1` (nn/attention.py:225)."""
+    return F.elu(x) + 1
+
+
+class LinearCausalAttention(nn.Module):
+    """Causal attention in O(L) memory with a kernel feature map (reference nn/attention.py:207-275, [2] there).
+
+    Same signature, parameters and state_dict keys as the reference (`_query`, `_kv`; no output projection; the
+    output has out_channels channels). The reference's denominator is kept as it is: its cumsum runs over the heads
+    axis (include/pg_hip.h, pg_linear_attn_fwd). With the default feature_fn the kernels apply elu + 1 themselves;
+    any other callable is applied to Q and K — (N, n_heads, H*W, head dim) views, as in the reference — under
+    autograd, and the kernels take the mapped tensors as they are.
+    """
+
+    def __init__(
+        self,
+        in_channels,
+        feature_fn=_elu_plus_one,
+        n_heads=1,
+        embed_channels=None,
+        out_channels=None,
+    ):
+        super().__init__()
+        self._feature_fn = feature_fn
+        self._n_heads = n_heads
+        self._embed_channels = embed_channels or in_channels
+        self._out_channels = out_channels or in_channels
+        self._query = Conv2d(in_channels=in_channels, out_channels=self._embed_channels, kernel_size=1)
+        self._kv = Conv2d(
+            in_channels=in_channels,
+            out_channels=self._embed_channels + self._out_channels,
+            kernel_size=1,
+        )
+
+    def _mapped(self, t):
+        """feature_fn on the (N, n_heads, L, head dim) view of an (N, C, H, W) tensor, back in (N, C, H, W)."""
+        n, c, h, w = t.shape
+        m = t.reshape(n, self._n_heads, c // self._n_heads, h * w).transpose(2, 3)
+        return self._feature_fn(m).transpose(2, 3).reshape(n, c, h, w)
+
+    def forward(self, x):
+        q = self._query(x)
+        kv = self._kv(x)
+        e, o = self._embed_channels, self._out_channels
+        if self._feature_fn is _elu_plus_one:
+            return ops.linear_causal_attention(q, kv, self._n_heads, e, o, "elu1")
+        q = self._mapped(q).contiguous()
+        kv = torch.cat((self._mapped(kv[:, :e]), kv[:, e:]), dim=1)
+        return ops.linear_causal_attention(q, kv, self._n_heads, e, o, "identity")

@@ -111,6 +111,12 @@ from pytorch_generative_amd.ops.attention import (  # noqa: F401
     _pad16,
     causal_attention,
 )
+from pytorch_generative_amd.ops.linear_attention import (  # noqa: F401
+    _LinearCausalAttention,
+    FEATURE_IDENTITY,
+    FEATURE_ELU1,
+    linear_causal_attention,
+)
 from pytorch_generative_amd.ops.losses import (  # noqa: F401
     _BCEWithLogitsSumMean,
     _DmolLossSumMean,
