@@ -8,17 +8,21 @@
 One "step" = the reference's Trainer._train_one_batch (trainer.py:173-193): zero_grad, forward,
 BCE-with-logits loss, backward, global grad norm, Adam, lr decay — on one resident batch of
 synthetic images, replayed from a hipGraph (two graphs with one flat RCCL all-reduce between them
-when data parallel). Rank 0 prints ONE JSON line:
+when data parallel). Rank 0 prints ONE JSON line. A plain run times the headline and nothing else:
 
   * headline (`value`, `config.workload`): BASELINE.json configs[1], ImageGPT 8 blocks / 4 heads /
     16 embedding channels on 28x28x1 at the saturating per-GPU batch 1024, fp32 (the reference is
-    fp32 end to end and parity is gated at 1e-4; DESIGN.md has the bf16 note);
+    fp32 end to end and parity is gated at 1e-4; DESIGN.md has the bf16 note).
+
+`--full` adds, after the headline's timed steps and in runs of their own:
   * `imagegpt_b64`: the same model at the reference's default batch 64 (image_gpt.py:114);
   * `pixel_snail`: the other half of BASELINE.json's metric — configs[3] PixelSNAIL(3, 3, 64, 8, 2,
     4, 32) on 32x32x3 — at a saturating batch and at the reference default 128, with its own
     dominant-kernel roofline;
-  * `roofline`: the headline's dominant kernel timed live with HIP events; `cpu_baseline`: the
-    oracle's restatement of the same step on the host cores.
+  * `other_configs`: compact records of the other BASELINE.json configurations;
+  * `roofline`: the headline's dominant kernel timed live with HIP events; `parity`: the errors of the
+    timed kernels against the CPU oracle, measured in the run; `cpu_baseline`: the oracle's
+    restatement of the same step on the host cores.
 `python bench.py --model <name>` benches one workload only (profiling helper; not the driver line).
 `--dump-outputs DIR`: rank 0 writes what the last timed step of the line's `value` record computed — loss, parameters
 after the update and the gradient of the flat buffer — as DIR/<name>.npy (float32), so that two builds can be compared
@@ -902,8 +906,11 @@ def main():
                     help="per-GPU batch of the PixelSNAIL record (saturating; the reference default 128 is reported beside it)")
     ap.add_argument("--model", default=None, choices=sorted(WORKLOADS),
                     help="bench this one workload only (profiling helper)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="headline only (no batch-64 / PixelSNAIL records)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the batch-64, PixelSNAIL and other-config records, the kernel rooflines, "
+                         "the parity measured against the CPU oracle and the CPU baselines (a plain run times the headline only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no measured parity and no CPU baselines")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: no batch-64 / PixelSNAIL / other-config records")
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of hipGraph replay")
     ap.add_argument("--n1-value", type=float, default=None,
                     help="images/s of the same headline at --gpus 1: adds scaling_efficiency_vs_n1 to the line")
@@ -959,7 +966,7 @@ def main():
     if dumped is not None and env.rank == 0:
         head_dump = {"dir": args.dump_outputs, "files": write_dump(args.dump_outputs, dumped)}
     extras = {}
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         extras["imagegpt_b64"] = run("image_gpt", 64)
         snail = run("pixel_snail", args.snail_batch)
         snail["reference_default_batch_128"] = run("pixel_snail", 128)
@@ -1001,7 +1008,7 @@ def main():
             },
             "loss_nats_per_image": head["loss_nats_per_image"],
             "bits_per_dim": head["bits_per_dim"],
-            "parity": PARITY_GATE_TEXT,  # replaced below by the errors measured in this run (rank 0, unless --no-cpu-baseline)
+            "parity": PARITY_GATE_TEXT,  # replaced below by the errors measured in this run (rank 0, --full without --no-cpu-baseline)
             "grad_exchange": head["grad_exchange"],
             "per_rank_images_per_s": head["per_rank_images_per_s"],
         }
@@ -1022,7 +1029,7 @@ def main():
                                             "(timed_steps / timed_seconds per record); ceilings: BASELINE.md §3 (pixel_cnn_pp: the "
                                             "same formula on bench._pixelcnnpp_gflop_per_img)", "unit": "images/s",
                                     **extras["other_configs"]}
-        if env.world == 1:
+        if args.full and env.world == 1:
             r = attention_kernel_roofline(args.batch, env.device, 4, 4, 4, 28, False)
             dom = "bwd" if "bwd" in r else "dkv"
             traffic, traffic_src, counters = measured_traffic(args.batch, "attn_bwd_m44_kernel" if dom == "bwd" else "attn_dkv_m44_kernel",
