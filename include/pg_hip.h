@@ -269,6 +269,36 @@ int pg_linear_attn_bwd(const float* q, const float* k, const float* v, const flo
                        int heads, int L, int dk_dim, int dv_dim, long q_bs, long kv_bs, long o_bs, int feature,
                        void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * MaskedLinear / MADE (models/autoregressive/made.py:21-33: `self.weight.data *= self.mask` then
+ * nn.Linear.forward; :39-145: the masks MADE draws from integer "degrees", _sample_masks :71-102).
+ * x: (N, in), w: (out, in), b: (out), y / dy: (N, out), dx: (N, in), all dense row-major.
+ * The mask is M[o][i] = deg_in[i] <= deg_out[o] (strict != 0: deg_in[i] < deg_out[o], MADE's output layer),
+ * evaluated from the two int32 degree vectors (device, lengths in / out) inside the kernels: no dense mask is
+ * read. deg_in = deg_out = NULL: unmasked (plain F.linear); exactly one of them NULL: PG_EINVAL.
+ * Masked GEMMs on v_mfma_f32_16x16x4_f32 (masked_linear.hip): fp32-exact, deterministic (no atomics). _fwd / _dgrad
+ * split k when the output has too few tiles to fill the chip; ws is then a caller-allocated workspace of
+ * pg_masked_linear_workspace_floats(N, in, out, dgrad) floats (0 floats: no split, ws may be NULL).
+ * Any N, in, out >= 1 (PG_ESHAPE otherwise, and for N or out above 65535 * 64).
+ *  _fwd    y = x (w o M)^T + b (b may be NULL), relu != 0 fuses nn.ReLU into the epilogue; with degrees it also
+ *          writes w o M back into w (the reference's in-place masking; made.py:32).
+ *  _dgrad  dx = dy (w o M), times (relu_out > 0) if relu_out (N, in) is given: the ReLU' of the PREVIOUS layer,
+ *          whose stored output is this layer's input (nn.ReLU's backward, made.py:63). dx is written.
+ *  _wgrad  dw += dy^T x, db += sum_n dy (db may be NULL): the UNMASKED weight gradient of the reference (the mask
+ *          is applied to weight.data outside autograd); the results are ADDED (gradient sinks / zeroed buffers).
+ *  _mask   mask = M as 0. / 1. floats (out, in): the layer's `mask` buffer (made.py:24, set_mask :27-28).
+ * ------------------------------------------------------------------------------------- */
+size_t pg_masked_linear_workspace_floats(int N, int in, int out, int dgrad);
+int pg_masked_linear_fwd(const float* x, float* w, const float* b, const int* deg_in, const int* deg_out, int strict,
+                         float* y, int N, int in, int out, int relu, float* ws, size_t ws_floats, void* stream);
+int pg_masked_linear_dgrad(const float* dy, const float* w, const int* deg_in, const int* deg_out, int strict,
+                           const float* relu_out, float* dx, int N, int in, int out, float* ws, size_t ws_floats,
+                           void* stream);
+int pg_masked_linear_wgrad(const float* x, const float* dy, float* dw, float* db, int N, int in, int out,
+                           void* stream);
+int pg_masked_linear_mask(float* mask, const int* deg_in, const int* deg_out, int strict, int in, int out,
+                          void* stream);
+
 /* (N,2,H,W) pixel-coordinate encoding, nn/attention.py:37-57 (torch.arange(-.5,.5,1/h)). */
 int pg_image_positional_encoding(float* out, int N, int H, int W, void* stream);
 

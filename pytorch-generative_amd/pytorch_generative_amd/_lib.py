@@ -105,6 +105,11 @@ SIGNATURES = {
     "pg_linear_attn_workspace_floats": (c_z, [c_i] * 6),
     "pg_linear_attn_fwd": (c_i, [c_f] * 6 + [c_z] + [c_i] * 5 + [c_l] * 3 + [c_i, c_s]),
     "pg_linear_attn_bwd": (c_i, [c_f] * 10 + [c_z] + [c_i] * 5 + [c_l] * 3 + [c_i, c_s]),
+    "pg_masked_linear_workspace_floats": (c_z, [c_i] * 4),
+    "pg_masked_linear_fwd": (c_i, [c_f] * 5 + [c_i, c_f] + [c_i] * 4 + [c_f, c_z, c_s]),
+    "pg_masked_linear_dgrad": (c_i, [c_f] * 4 + [c_i, c_f, c_f] + [c_i] * 3 + [c_f, c_z, c_s]),
+    "pg_masked_linear_wgrad": (c_i, [c_f] * 4 + [c_i] * 3 + [c_s]),
+    "pg_masked_linear_mask": (c_i, [c_f] * 3 + [c_i] * 3 + [c_s]),
     "pg_image_positional_encoding": (c_i, [c_f, c_i, c_i, c_i, c_s]),
     "pg_act_fwd": (c_i, [c_f, c_f, c_z, c_i, c_s]),
     "pg_act_bwd": (c_i, [c_f, c_f, c_f, c_z, c_i, c_s]),

@@ -7,7 +7,7 @@
 Code written against the reference's public surface (pytorch_generative/__init__.py:1-3,
 nn/__init__.py:3-13, models/__init__.py:3-24, models/<family>/<module>.reproduce, trainer.Trainer)
 then runs unmodified on the HIP operator path for the components this package covers; names of
-out-of-scope components (NADE, MADE, NICE, KDE, mixtures, `models.flow`) resolve to
+out-of-scope components (NADE, NICE, KDE, mixtures, `models.flow`) resolve to
 placeholders that raise on use.
 """
 
@@ -18,9 +18,9 @@ import pytorch_generative_amd as _pkg
 
 _OUT_OF_SCOPE_MODULES = {
     "pytorch_generative.models.flow": ("nice",),
-    "pytorch_generative.models.autoregressive": ("nade", "made", "fvbn"),
+    "pytorch_generative.models.autoregressive": ("nade", "fvbn"),
 }
-_OUT_OF_SCOPE_MODELS = ("NADE", "MADE", "FullyVisibleBeliefNetwork", "NICE", "GaussianKernel", "ParzenWindowKernel",
+_OUT_OF_SCOPE_MODELS = ("NADE", "FullyVisibleBeliefNetwork", "NICE", "GaussianKernel", "ParzenWindowKernel",
                         "KernelDensityEstimator", "BernoulliMixtureModel", "GaussianMixtureModel")
 
 

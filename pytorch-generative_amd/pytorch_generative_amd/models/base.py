@@ -7,9 +7,24 @@
 """
 
 import abc
+import functools
 
 import torch
 from torch import distributions, nn
+
+
+def auto_reshape(fn):
+    """Flattens (N, ...) inputs to (N, -1) for `fn` and gives its result the input's shape back (reference
+    models/base.py:13-25): non-convolutional models (MADE) then take (N, 1, H, W) images as they are."""
+
+    @functools.wraps(fn)
+    def wrapped_fn(self, x, *args, **kwargs):
+        original_shape = x.shape
+        x = x.view(original_shape[0], -1)
+        y = fn(self, x, *args, **kwargs)
+        return y.view(original_shape)
+
+    return wrapped_fn
 
 
 def _bernoulli_from_logits(logits):

@@ -117,6 +117,13 @@ from pytorch_generative_amd.ops.linear_attention import (  # noqa: F401
     FEATURE_ELU1,
     linear_causal_attention,
 )
+from pytorch_generative_amd.ops.masked_linear import (  # noqa: F401
+    _MaskedMLP,
+    mask_from_degrees,
+    masked_linear,
+    masked_mlp,
+    mul_mask_,
+)
 from pytorch_generative_amd.ops.losses import (  # noqa: F401
     _BCEWithLogitsSumMean,
     _DmolLossSumMean,

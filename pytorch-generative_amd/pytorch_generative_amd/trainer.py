@@ -250,6 +250,12 @@ class Trainer:
         if g is None:
             if len(self._graphs) >= 4:  # e.g. ragged batch sizes: do not hoard graphs
                 return None
+            refusal = getattr(self.model, "graph_capture_refusal", lambda: None)()
+            if refusal:  # known before the warm-up steps (which would be real forwards): train eagerly
+                warnings.warn(f"hipGraph capture of the training step skipped ({refusal}); "
+                              "falling back to eager kernel launches")
+                self._use_graph = False
+                return None
             try:
                 g = pg_graph.GraphedTrainStep(
                     self.model, self.optimizer, None, x, reducer=self._reducer, example_y=y,

@@ -23,6 +23,7 @@ MODEL_DICT = {
     "beta_vae": vae.beta_vae,
     "gated_pixel_cnn": autoregressive.gated_pixel_cnn,
     "image_gpt": autoregressive.image_gpt,
+    "made": autoregressive.made,
     "pixel_cnn": autoregressive.pixel_cnn,
     "pixel_cnn_pp": autoregressive.pixel_cnn_pp,
     "pixel_snail": autoregressive.pixel_snail,
