@@ -495,6 +495,14 @@ int pg_attn_decode(const float* qkv, float* k_cache, float* v_cache, float* o, i
  * ------------------------------------------------------------------------------------- */
 int pg_sumsq_accum(const float* g, size_t n, float* state, void* stream);
 int pg_adam_prepare(float* state, void* stream);
+/* The same two steps with a run-to-run reproducible norm (what FlatAdam launches): the norm kernel's
+ * blocks store their partial sums to partials[0 .. pg_sumsq_partial_count(n)) (at most 1024 floats, no
+ * atomics, nothing to zero) and the prepare kernel adds them in a fixed order. state[2] is not used.
+ * nparts MUST be pg_sumsq_partial_count(n) of the n just given to pg_sumsq_partials: entries beyond it
+ * were not written by that launch. */
+int pg_sumsq_partial_count(size_t n);
+int pg_sumsq_partials(const float* g, size_t n, float* partials, void* stream);
+int pg_adam_prepare_ordered(float* state, const float* partials, int nparts, void* stream);
 int pg_adam_step(float* p, const float* g, float* m, float* v, size_t n, const float* state,
                  float beta1, float beta2, float eps, void* stream);
 

@@ -144,6 +144,9 @@ SIGNATURES = {
     "pg_fill_scaled": (c_i, [c_f, c_flt, c_f, c_i, c_s]),
     "pg_sumsq_accum": (c_i, [c_f, c_z, c_f, c_s]),
     "pg_adam_prepare": (c_i, [c_f, c_s]),
+    "pg_sumsq_partial_count": (c_i, [c_z]),
+    "pg_sumsq_partials": (c_i, [c_f, c_z, c_f, c_s]),
+    "pg_adam_prepare_ordered": (c_i, [c_f, c_f, c_i, c_s]),
     "pg_adam_step": (c_i, [c_f, c_f, c_f, c_f, c_z, c_f, c_flt, c_flt, c_flt, c_s]),
     "pg_attn_fused_bwd": (c_i, [c_i]),
     "pg_concat_elu_fwd": (c_i, [c_f, c_f, c_i, c_l, c_s]),

@@ -171,8 +171,8 @@ def set_deterministic(on=True):
     PixelSNAIL, round 4) — dQ is summed over key blocks in arrival order: last-bit differences run to run;
     `on` selects the two-kernel backward, and the per-sample KL sums of the Gaussian heads are then reduced by one
     workgroup per sample (fixed order). Still summed with fp32 atomics in arrival order, because they feed no gradient
-    and no parameter: the scalar loss values (BCE / DMOL / VQ) and the squared gradient norm that `FlatAdam` reports
-    (it only scales the step above max_norm = 1e50).
+    and no parameter: the scalar loss values (BCE / DMOL / VQ). (The squared gradient norm of `FlatAdam` is summed in a
+    fixed order in both modes: with a finite max_norm it scales every gradient.)
     Returns the previous setting."""
     prev = _lib.load().pg_attn_fused_bwd(0 if on else 1)
     return prev == 0

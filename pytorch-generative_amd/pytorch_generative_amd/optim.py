@@ -104,6 +104,10 @@ class FlatAdam(torch.optim.Optimizer):
         st[_MAXNORM] = float("inf") if max_norm is None else max_norm  # 1e50 overflows fp32: never clips
         st[_PRESCALE] = 1.0
         self.state_block = st.to(dev)
+        # per-block partial sums of the squared norm, added in a fixed order by the prepare kernel: the norm and
+        # with it every clipped gradient is bit-reproducible run to run (an atomic sum is arrival-ordered)
+        self._norm_parts = self._lib.pg_sumsq_partial_count(total)
+        self._norm_partials = torch.zeros(max(1, self._norm_parts), device=dev, dtype=torch.float32)
         self._host_lr = lr
         self._lr_decay = float(lr_decay)
 
@@ -164,9 +168,10 @@ class FlatAdam(torch.optim.Optimizer):
         lib, s = self._lib, _stream()
         b1, b2 = self.param_groups[0]["betas"]
         eps = self.param_groups[0]["eps"]
-        _lib.check(lib.pg_sumsq_accum(self.flat_grad.data_ptr(), self._numel,
-                                      self.state_block.data_ptr(), s), "pg_sumsq_accum")
-        _lib.check(lib.pg_adam_prepare(self.state_block.data_ptr(), s), "pg_adam_prepare")
+        _lib.check(lib.pg_sumsq_partials(self.flat_grad.data_ptr(), self._numel,
+                                         self._norm_partials.data_ptr(), s), "pg_sumsq_partials")
+        _lib.check(lib.pg_adam_prepare_ordered(self.state_block.data_ptr(), self._norm_partials.data_ptr(),
+                                               self._norm_parts, s), "pg_adam_prepare_ordered")
         _lib.check(
             lib.pg_adam_step(self.flat_param.data_ptr(), self.flat_grad.data_ptr(),
                              self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), self._numel,

@@ -95,6 +95,12 @@ def _as_metrics(out):
     return metrics
 
 
+def should_step(norm, skip_grad_norm):
+    """The reference's decision (trainer.py:188), written its way round: step unless `skip_grad_norm` is set
+    and the norm is NOT <= it — a NaN norm (and +inf) drops the step, which `norm > skip_grad_norm` would take."""
+    return not skip_grad_norm or norm <= skip_grad_norm
+
+
 class Trainer:
     def __init__(
         self,
@@ -302,7 +308,7 @@ class Trainer:
             if self.skip_grad_norm:  # the decision needs the norm on the host (reference :188)
                 norm = opt.measure_grad_norm()
                 metrics["grad_norm"] = norm
-                if float(norm) > self.skip_grad_norm:
+                if not should_step(float(norm), self.skip_grad_norm):
                     return metrics, False
             opt.step()
             metrics.setdefault("grad_norm", opt.grad_norm().clone())
@@ -310,7 +316,7 @@ class Trainer:
         limit = self.clip_grad_norm or self.skip_grad_norm or 1e50
         norm = torch.nn.utils.clip_grad_norm_(self.model.parameters(), limit)
         metrics["grad_norm"] = norm
-        if self.skip_grad_norm and float(norm) > self.skip_grad_norm:
+        if self.skip_grad_norm and not should_step(float(norm), self.skip_grad_norm):
             return metrics, False
         opt.step()
         return metrics, True

@@ -237,3 +237,163 @@ def test_row_cached_sampling_equals_full_forward(dev, ctor, kw, hw):
     canvas2, ref = model.sample(conditioned_on=torch.full_like(x, -1.0), incremental=False, return_logits=True)
     assert torch.equal(canvas2, x)
     _util.assert_close(ref, full, 1e-5, f"{ctor}: per-pixel full forwards vs one full forward")
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# clip_grad_norm / skip_grad_norm
+# ---------------------------------------------------------------------------------------------------------------
+def _make_plain(dev):
+    import pytorch_generative_amd as pg
+
+    torch.manual_seed(0)
+    return pg.models.PixelCNN(1, 1, n_residual=2, residual_channels=4, head_channels=4).to(dev)
+
+
+def _clip_twins(dev, max_norm):
+    from pytorch_generative_amd import optim
+
+    m1, m2 = _make_plain(dev), _make_plain(dev)
+    return (m1, optim.FlatAdam(m1.parameters(), lr=1e-3, max_norm=max_norm),
+            m2, optim.FlatAdam(m2.parameters(), lr=1e-3, max_norm=max_norm))
+
+
+def test_clipping_inside_a_captured_step_equals_eager(dev):
+    """FlatAdam(max_norm=c) with c below every gradient norm (the batches' norms are ~16): K = 4 replays of the captured
+    step against K eager steps, bit-identical — the norm is summed in a fixed order, so the clip coefficient that scales
+    every gradient has the same bits in both."""
+    from pytorch_generative_amd import graph, ops
+
+    c = 5.0
+    xs = [b.to(dev) for b in _Loader((4, 1, 8, 8), n_batches=4, seed=3).batches]
+    loss_fn = lambda x, preds: ops.bce_with_logits_sum_mean(preds, x)  # noqa: E731
+    was = ops.set_deterministic(True)
+    try:
+        m1, o1, m2, o2 = _clip_twins(dev, c)
+        eager_norms, graph_norms = [], []
+        for x in xs:
+            o1.zero_grad()
+            loss_fn(x, m1(x)).backward()
+            o1.step()
+            eager_norms.append(float(o1.grad_norm()))
+            assert float(o1.state_block[4]) < 0.5  # coef: this step was clipped
+        step = graph.GraphedTrainStep(m2, o2, loss_fn, xs[0], preserve_state=True)
+        for x in xs:
+            step(x)
+            graph_norms.append(float(o2.grad_norm()))
+        torch.cuda.synchronize()
+        assert min(eager_norms) > 2 * c and eager_norms == graph_norms
+        assert torch.equal(o1.flat_param, o2.flat_param), "clipped graph replays differ from clipped eager steps"
+        assert torch.equal(o1.exp_avg, o2.exp_avg) and torch.equal(o1.exp_avg_sq, o2.exp_avg_sq)
+        assert float(o2.state_block[0]) == 4.0
+    finally:
+        ops.set_deterministic(was)
+
+
+def test_set_max_norm_after_capture_changes_the_next_replay(dev):
+    """max_norm lives in the device state block: changing it AFTER capture takes effect in the next replay, no recapture,
+    no host round trip. Replay with c, None, c, c against an eager twin doing the same, compared after every step."""
+    from pytorch_generative_amd import graph, ops
+
+    c = 5.0
+    xs = [b.to(dev) for b in _Loader((4, 1, 8, 8), n_batches=4, seed=4).batches]
+    loss_fn = lambda x, preds: ops.bce_with_logits_sum_mean(preds, x)  # noqa: E731
+    was = ops.set_deterministic(True)
+    try:
+        m1, o1, m2, o2 = _clip_twins(dev, c)
+        step = graph.GraphedTrainStep(m2, o2, loss_fn, xs[0], preserve_state=True)
+        for x, mn in zip(xs, [c, None, c, c]):
+            o1.set_max_norm(mn)
+            o2.set_max_norm(mn)
+            o1.zero_grad()
+            loss_fn(x, m1(x)).backward()
+            o1.step()
+            step(x)
+            torch.cuda.synchronize()
+            coef = float(o2.state_block[4])
+            assert (coef == 1.0) if mn is None else (coef < 0.5), (mn, coef)
+            assert float(o1.state_block[4]) == coef
+            assert torch.equal(o1.flat_param, o2.flat_param), f"max_norm={mn}: replay differs from the eager twin"
+    finally:
+        ops.set_deterministic(was)
+
+
+def _clip_fixture():
+    return torch.load(os.path.join(_util.GOLDEN_DIR, "ref_trainer_clip", "steps.pt"), map_location="cpu",
+                      weights_only=False)
+
+
+@pytest.mark.parametrize("mode", ["flat_graph", "flat_eager", "torch_adam"])
+@pytest.mark.parametrize("config", ["clip", "skip", "both"])
+def test_clip_and_skip_follow_the_reference_trainer(dev, tmp_path, config, mode):
+    """tests/golden/ref_trainer_clip/steps.pt: the reference's Trainer._train_one_batch with clip_grad_norm / skip_grad_norm
+    over eight batches (ordinary, above the clip threshold, out-of-range targets far above the skip threshold, one with
+    NaN; generator make_clip_golden.py, every finite norm >= 10 % away from its thresholds). The same batches through
+    this Trainer, per step: the same step / skip decision (on a skipped step parameters bit-unchanged — but for the
+    masked taps the forward zeroes, as in the reference —, lr unchanged, Adam's counter not advanced), loss and grad_norm
+    at 1e-4 (NaN where the reference has NaN), the scheduler's lr, and the parameters at the post-Adam rule of
+    DESIGN.md §2 (1e-4 of the tensor's maximum where the gradient has been above its noise floor on every step so far,
+    Adam's step bound elsewhere). A NaN norm must be SKIPPED: `norm > skip` is False for NaN and took that step."""
+    import math
+
+    import pytorch_generative_amd as pg
+    from pytorch_generative_amd import optim, trainer
+
+    fx = _clip_fixture()
+    cfg = fx["configs"][config]
+    model = pg.models.PixelCNN(**fx["model_kwargs"])
+    model.load_state_dict(cfg["state0"], strict=True)
+    model = model.to(dev)
+    flat = mode != "torch_adam"
+    opt = optim.FlatAdam(model.parameters(), lr=fx["lr"]) if flat else torch.optim.Adam(model.parameters(), lr=fx["lr"])
+    sched = torch.optim.lr_scheduler.MultiplicativeLR(opt, lr_lambda=lambda _: fx["decay"])
+    t = trainer.Trainer(model, _loss_fn, opt, [], [], lr_scheduler=sched, log_dir=str(tmp_path), n_gpus=1,
+                        graph=(mode != "flat_eager"), **cfg["kwargs"])
+    # skip_grad_norm needs the norm on the host: eager launches; clip_grad_norm alone keeps the captured path
+    assert t._use_graph == (mode == "flat_graph" and "skip_grad_norm" not in cfg["kwargs"])
+    first = next(iter(model.parameters()))
+
+    def adam_step():
+        if flat:
+            return float(opt.state_block[0])
+        return float(opt.state[first]["step"]) if opt.state else 0.0
+
+    def lr_now():
+        return opt.current_lr() if flat else opt.param_groups[0]["lr"]
+
+    above, taken = {}, 0
+    for i, ref in enumerate(cfg["steps"]):
+        what = f"{config}/{mode} step {i} ({ref['kind']})"
+        before = {k: p.detach().clone() for k, p in model.named_parameters()}
+        step_before, lr_before = adam_step(), lr_now()
+        m = t._train_one_batch(ref["x"], None)
+        stepped = adam_step() == step_before + 1
+        print(f"[clip/skip] {what}: loss {m['loss']!r} (ref {ref['metrics']['loss']!r}) grad_norm {m['grad_norm']!r} "
+              f"(ref {ref['metrics']['grad_norm']!r}) stepped {stepped} (ref {ref['stepped']})")
+        assert stepped == ref["stepped"], what
+        assert adam_step() == ref["adam_step"], what
+        for key in ("loss", "grad_norm"):
+            want = ref["metrics"][key]
+            if math.isnan(want):
+                assert math.isnan(m[key]), f"{what}: {key} {m[key]} where the reference has NaN"
+            else:
+                assert abs(m[key] - want) <= 1e-4 * abs(want), f"{what}: {key} {m[key]} vs {want}"
+        assert abs(lr_now() - ref["lr"]) < 1e-10, what
+        named = dict(model.named_parameters())
+        if not stepped:
+            assert lr_now() == lr_before, what
+            for k, p in named.items():
+                assert bool(((p == before[k]) | (p == 0)).all()), f"{what}: {k} moved on a skipped step"
+        else:
+            taken += 1
+            for k, g in ref["grads"].items():
+                ok = g.abs() > 1e-5 * float(g.abs().max())
+                above[k] = ok if k not in above else (above[k] & ok)
+        for k, p in named.items():
+            got, want = p.detach().double().cpu(), ref["state"][k].double()
+            d = (got - want).abs()
+            assert bool(torch.isfinite(got).all()), f"{what}: {k} is not finite"
+            if k in above and bool(above[k].any()):
+                assert float(d[above[k]].max()) <= 1e-4 * float(want.abs().max()) + 1e-7, f"{what}: {k} after Adam"
+            assert float(d.max()) <= 2 * taken * fx["lr"] + 1e-6, f"{what}: {k} beyond Adam's step bound"
+    assert all(bool(torch.isfinite(p).all()) for p in model.parameters())
+    assert taken == sum(1 for s in cfg["steps"] if s["stepped"])
