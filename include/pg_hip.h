@@ -299,6 +299,44 @@ int pg_masked_linear_wgrad(const float* x, const float* dy, float* dw, float* db
 int pg_masked_linear_mask(float* mask, const int* deg_in, const int* deg_out, int strict, int in, int out,
                           void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Density estimators (models/mixture_models.py, models/kde.py) on streaming log-density kernels (density.hip):
+ * the pairwise log-density c[n][k] = sum_d f(x[n][d], theta[k][d]) is one or two fp32-MFMA GEMMs plus a per-column
+ * constant, reduced by a running logsumexp over column tiles; nothing of size N x K (x F) is written to memory.
+ * x / test: (N, F), parameters / train: (K, F), dense row-major. Deterministic (no atomics).
+ * Any N, K, F >= 1 (PG_ESHAPE otherwise, and for N above 65535 * 64 or K above 65535 * 32). ws is a caller-allocated
+ * workspace of the matching _workspace_floats() floats (a shorter one: PG_EINVAL).
+ *  pg_mixture_fwd  lse[n] = logsumexp_k (log_softmax(mixture_logits)_k + log p_k(x_n)).
+ *                  kind PG_MIXTURE_BERNOULLI: p1 = logits (K, F), p2 unused, log p_k(x) = sum_d x l - softplus(l)
+ *                  (binary_cross_entropy_with_logits: real-valued x allowed);
+ *                  kind PG_MIXTURE_GAUSSIAN: p1 = mean, p2 = log_std (diagonal normal).
+ *                  mixture_logits all -inf gives lse = -inf (torch's log_softmax gives NaN there).
+ *                  stats (N, 2) receives, per row, the running (max, sum) of the logsumexp relative to component 0:
+ *                  what the backward needs (it never sees lse).
+ *  pg_mixture_bwd  from x, the forward's stats and the upstream gradient g (N): the gradients of mixture_logits (K), p1
+ *                  and p2 (K, F) are ADDED to d_logits / d1 / d2 (gradient sinks / zeroed buffers; each may be NULL).
+ *                  The responsibilities are recomputed tile by tile; the Gaussian sums are formed from (x - mean).
+ *                  No input gradient.
+ *  pg_kde_gaussian out[n] = logsumexp_k (-|x_n - y_k|^2 / (2 h^2)) - (F/2 log 2 pi + F log h + log K)
+ *                  (kde.py GaussianKernel.forward), as alpha x.y - alpha/2 |y|^2 - alpha/2 |x|^2 with alpha = 1 / h^2.
+ *  pg_kde_parzen   out[n] = log(coef * #{k: |x_n[d] - y_k[d]| / h <= 0.5 for all d} / K) in the reference's fp32
+ *                  order (kde.py ParzenWindowKernel.forward); coef = 1 / h^F as the caller computed it. count 0: -inf;
+ *                  coef = inf (it overflowed): +inf if every window contains x_n, NaN otherwise, as the reference.
+ * ------------------------------------------------------------------------------------- */
+#define PG_MIXTURE_BERNOULLI 0
+#define PG_MIXTURE_GAUSSIAN 1
+size_t pg_mixture_workspace_floats(int kind, int N, int K, int F, int backward);
+int pg_mixture_fwd(int kind, const float* x, const float* mixture_logits, const float* p1, const float* p2, float* lse,
+                   float* stats, int N, int K, int F, float* ws, size_t ws_floats, void* stream);
+int pg_mixture_bwd(int kind, const float* x, const float* mixture_logits, const float* p1, const float* p2,
+                   const float* stats, const float* g, float* d_logits, float* d1, float* d2, int N, int K, int F,
+                   float* ws, size_t ws_floats, void* stream);
+size_t pg_kde_workspace_floats(int N, int K, int F);
+int pg_kde_gaussian(const float* test, const float* train, float bandwidth, float* out, int N, int K, int F, float* ws,
+                    size_t ws_floats, void* stream);
+int pg_kde_parzen(const float* test, const float* train, float bandwidth, float coef, float* out, int N, int K, int F,
+                  void* stream);
+
 /* (N,2,H,W) pixel-coordinate encoding, nn/attention.py:37-57 (torch.arange(-.5,.5,1/h)). */
 int pg_image_positional_encoding(float* out, int N, int H, int W, void* stream);
 

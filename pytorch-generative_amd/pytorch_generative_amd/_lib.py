@@ -110,6 +110,12 @@ SIGNATURES = {
     "pg_masked_linear_dgrad": (c_i, [c_f] * 4 + [c_i, c_f, c_f] + [c_i] * 3 + [c_f, c_z, c_s]),
     "pg_masked_linear_wgrad": (c_i, [c_f] * 4 + [c_i] * 3 + [c_s]),
     "pg_masked_linear_mask": (c_i, [c_f] * 3 + [c_i] * 3 + [c_s]),
+    "pg_mixture_workspace_floats": (c_z, [c_i] * 5),
+    "pg_mixture_fwd": (c_i, [c_i] + [c_f] * 6 + [c_i] * 3 + [c_f, c_z, c_s]),
+    "pg_mixture_bwd": (c_i, [c_i] + [c_f] * 9 + [c_i] * 3 + [c_f, c_z, c_s]),
+    "pg_kde_workspace_floats": (c_z, [c_i] * 3),
+    "pg_kde_gaussian": (c_i, [c_f, c_f, c_flt, c_f] + [c_i] * 3 + [c_f, c_z, c_s]),
+    "pg_kde_parzen": (c_i, [c_f, c_f, c_flt, c_flt, c_f] + [c_i] * 3 + [c_s]),
     "pg_image_positional_encoding": (c_i, [c_f, c_i, c_i, c_i, c_s]),
     "pg_act_fwd": (c_i, [c_f, c_f, c_z, c_i, c_s]),
     "pg_act_bwd": (c_i, [c_f, c_f, c_f, c_z, c_i, c_s]),

@@ -7,8 +7,8 @@
 Code written against the reference's public surface (pytorch_generative/__init__.py:1-3,
 nn/__init__.py:3-13, models/__init__.py:3-24, models/<family>/<module>.reproduce, trainer.Trainer)
 then runs unmodified on the HIP operator path for the components this package covers; names of
-out-of-scope components (NADE, NICE, KDE, mixtures, `models.flow`) resolve to
-placeholders that raise on use.
+out-of-scope components (NADE, NICE, FullyVisibleBeliefNetwork, `models.flow`, `models.autoregressive.nade` / `.fvbn`)
+resolve to placeholders that raise on use.
 """
 
 import sys
@@ -20,8 +20,7 @@ _OUT_OF_SCOPE_MODULES = {
     "pytorch_generative.models.flow": ("nice",),
     "pytorch_generative.models.autoregressive": ("nade", "fvbn"),
 }
-_OUT_OF_SCOPE_MODELS = ("NADE", "FullyVisibleBeliefNetwork", "NICE", "GaussianKernel", "ParzenWindowKernel",
-                        "KernelDensityEstimator", "BernoulliMixtureModel", "GaussianMixtureModel")
+_OUT_OF_SCOPE_MODELS = ("NADE", "FullyVisibleBeliefNetwork", "NICE")
 
 
 class _NotOnThisPath:
@@ -53,6 +52,8 @@ def install_alias(name="pytorch_generative"):
         f"{name}.models.base": _pkg.models.base,
         f"{name}.models.autoregressive": _pkg.models.autoregressive,
         f"{name}.models.vae": _pkg.models.vae,
+        f"{name}.models.kde": _pkg.models.kde,
+        f"{name}.models.mixture_models": _pkg.models.mixture_models,
         f"{name}.trainer": _pkg.trainer,
         f"{name}.datasets": _pkg.datasets,
     }

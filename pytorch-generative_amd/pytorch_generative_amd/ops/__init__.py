@@ -124,6 +124,14 @@ from pytorch_generative_amd.ops.masked_linear import (  # noqa: F401
     masked_mlp,
     mul_mask_,
 )
+from pytorch_generative_amd.ops.density import (  # noqa: F401
+    _MixtureLogProb,
+    MIXTURE_BERNOULLI,
+    MIXTURE_GAUSSIAN,
+    kde_gaussian,
+    kde_parzen,
+    mixture_log_prob,
+)
 from pytorch_generative_amd.ops.losses import (  # noqa: F401
     _BCEWithLogitsSumMean,
     _DmolLossSumMean,
