@@ -14,10 +14,13 @@
 // v_mfma_f32_16x16x4_f32 (K-step r contracts channels {4g + r}), so the whole chain — projection,
 // residual, LayerNorm, fc1, GELU, fc2, residuals — never leaves the register file. Per layer the
 // kernels read x, o (resp. d x_new, d qkv) once and write qkv, x_new (resp. d o, d x) once.
-// Weight gradients contract over pixels: the computed operand goes through a per-wave LDS transpose,
-// the other one is re-read from L2 in the transposed order; partial sums live in registers for all the
+// Weight gradients contract over pixels: both operands go through per-wave LDS transposes (the loaded ones,
+// d qkv / d x_new / o, are written from the registers that already hold them instead of being read from
+// global memory a second time in transposed order); partial sums live in registers for all the
 // tiles of a wave, are reduced per workgroup in LDS and summed by a small second kernel (deterministic).
 // Backward recomputes x_mid, both LayerNorms and the hidden activations instead of storing them.
+// The tile loops are software-pipelined: a wave issues the global loads of its next tile before the
+// MFMA/VALU chain of the tile in hand and touches them after its stores (see prefetch_fence below).
 #include <stdlib.h>
 
 #include "common.h"
@@ -32,6 +35,7 @@ constexpr int GB_THREADS = 256;  // 4 waves
 constexpr int TS = 20;           // LDS row stride (floats) of a transposed [channel][16 px] tile
 constexpr float INV_C = 1.f / 16.f;
 
+constexpr int TB_WAVE_ROWS = 2 * HD + 4 * C;  // tail_bwd's per-wave LDS tiles: G, dH [64] + LN2, dx_mid, D, o [16] rows of TS
 // partial-row layouts (floats)
 constexpr int T_W1 = 0, T_B1 = T_W1 + HD * C, T_W2 = T_B1 + HD, T_B2 = T_W2 + C * HD, T_WP = T_B2 + C,
               T_BP = T_WP + C * C, T_G2 = T_BP + C, T_BE2 = T_G2 + C, T_PART = T_BE2 + C;          // 2432
@@ -95,6 +99,47 @@ __device__ __forceinline__ f32x4 load_vec(const float* __restrict__ v, int g) {
 
 __device__ __forceinline__ float gelu_f(float x) { return pg_gelu(x); }
 
+// A wave's walk over its tiles (wave, wave + nwaves, ...) as (image n, tile t within the image), all wave-uniform so
+// that the address arithmetic stays on the scalar unit; one division before the loop, none inside it.
+struct TileWalk {
+  int n, t, dn, dt, tpi;
+  __device__ __forceinline__ TileWalk(const BlockArgs& a, int wave, int nwaves)
+      : n(wave / a.tiles_per_img), t(wave % a.tiles_per_img), dn(nwaves / a.tiles_per_img),
+        dt(nwaves % a.tiles_per_img), tpi(a.tiles_per_img) {}
+  __device__ __forceinline__ TileWalk next() const {
+    TileWalk w = *this;
+    w.n += dn; w.t += dt;
+    if (w.t >= tpi) { w.t -= tpi; ++w.n; }
+    return w;
+  }
+  // float offset of the tile's pixel 0 in an (N, chans, L) tensor
+  __device__ __forceinline__ size_t base(int chans, int L) const { return ((size_t)n * chans) * L + t * 16; }
+};
+// Software pipeline of the tile loops: the loads of the wave's next tile are issued at the top of an iteration and
+// first touched at its bottom, behind the whole MFMA chain and the stores. prefetch_fence() pins them there;
+// wait_prologue_loads() lets the first tile land before the loop, so that the loop's own waits (which the compiler
+// derives from every way into the loop) never cover loads that were issued a moment ago.
+__device__ __forceinline__ void prefetch_fence() { __builtin_amdgcn_sched_barrier(0); }
+// s_waitcnt immediate of gfx9 (gfx950 included): vmcnt = bits [15:14] and [3:0], expcnt [6:4], lgkmcnt [11:8]
+constexpr int waitcnt_gfx9(int vm, int exp, int lgkm) { return ((vm & 0x30) << 10) | (vm & 0xF) | ((exp & 7) << 4) | ((lgkm & 0xF) << 8); }
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(__GFX9__)
+#error "wait_prologue_loads() encodes s_waitcnt for gfx9; re-derive the immediate for another target"
+#endif
+__device__ __forceinline__ void wait_prologue_loads() {
+  constexpr int VMCNT0_ONLY = waitcnt_gfx9(/*vmcnt*/ 0, /*expcnt: no wait*/ 7, /*lgkmcnt: no wait*/ 15);
+  static_assert(VMCNT0_ONLY == 0x0F70, "gfx9 s_waitcnt vmcnt(0)");
+  __builtin_amdgcn_s_waitcnt(VMCNT0_ONLY);
+}
+// D-layout tile -> per-wave LDS tile [channel][TS] (conflict-free ds_write_b32), read back transposed with
+// lds_row4: channel `row`, pixels 4g..4g+3 (one ds_read_b128)
+__device__ __forceinline__ void lds_put_tile(float* t, int j, int g, const f32x4& v) {
+#pragma unroll
+  for (int r = 0; r < 4; ++r) t[(4 * g + r) * TS + j] = v[r];
+}
+__device__ __forceinline__ f32x4 lds_row4(const float* t, int row, int g) {
+  return *reinterpret_cast<const f32x4*>(t + row * TS + 4 * g);
+}
+
 // row `ch` of the merged [W_q; W_kv] matrix (each row has C entries)
 __device__ __forceinline__ const float* qkv_row(const BlockArgs& a, int ch) {
   return ch < C ? a.wq + ch * C : a.wkv + (ch - C) * C;
@@ -103,7 +148,7 @@ __device__ __forceinline__ const float* qkv_row(const BlockArgs& a, int ch) {
 // ---------------------------------------------------------------------------------- head, forward
 __global__ void __launch_bounds__(GB_THREADS) head_fwd_kernel(const BlockArgs a) {
   const int lane = threadIdx.x & 63, j = lane & 15, g = lane >> 4;
-  const int wave = blockIdx.x * (GB_THREADS / 64) + (threadIdx.x >> 6);
+  const int wave = blockIdx.x * (GB_THREADS / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int nwaves = gridDim.x * (GB_THREADS / 64);
   float wf[3][4];  // A[i = out channel 16m+j][k = g <-> in channel 4g+r]
   f32x4 bias[3];
@@ -117,15 +162,21 @@ __global__ void __launch_bounds__(GB_THREADS) head_fwd_kernel(const BlockArgs a)
     }
   }
   const f32x4 gam = load_vec(a.g1, g), bet = load_vec(a.be1, g);
-  for (int tile = wave; tile < a.total_tiles; tile += nwaves) {
-    const int n = tile / a.tiles_per_img;
-    const int p = (tile - n * a.tiles_per_img) * 16 + j;
-    const f32x4 xv = load_tile(a.x + (size_t)n * C * a.L + p, a.L, g);
+  if (wave >= a.total_tiles) return;  // a wave without a tile loads nothing
+  TileWalk tw(a, wave, nwaves);
+  f32x4 xv = load_tile(a.x + tw.base(C, a.L) + j, a.L, g);
+  wait_prologue_loads();
+  for (;;) {
+    // the last iteration re-reads its own tile instead of branching around the prefetch
+    const TileWalk nx = tw.next();
+    const bool more = nx.n < a.N;
+    const f32x4 xn = load_tile(a.x + (more ? nx : tw).base(C, a.L) + j, a.L, g);
+    prefetch_fence();
     const Ln s = ln_stats(xv, a.eps);
     f32x4 y;
 #pragma unroll
     for (int r = 0; r < 4; ++r) y[r] = fmaf(s.xhat[r], gam[r], bet[r]);
-    float* qb = a.qkv + (size_t)n * QKV * a.L + p;
+    float* qb = a.qkv + tw.base(QKV, a.L) + j;
 #pragma unroll
     for (int m = 0; m < 3; ++m) {
       f32x4 out = bias[m];
@@ -133,19 +184,25 @@ __global__ void __launch_bounds__(GB_THREADS) head_fwd_kernel(const BlockArgs a)
       for (int r = 0; r < 4; ++r) out = MFMA16(wf[m][r], y[r], out);
       store_tile(qb + (size_t)(16 * m) * a.L, a.L, g, out);
     }
+    if (!more) break;
+    xv = xn;
+    tw = nx;
   }
 }
 
 // ---------------------------------------------------------------------------------- head, backward
 // dx = LN1'(W^T dqkv) + gx ; dW += dqkv^T LN1(x) ; db += sum dqkv ; dgamma1, dbeta1
+// only x and gx of the next tile are prefetched (8 registers): with d qkv prefetched as well (12 more) the kernel leaves the
+// four-waves-per-SIMD budget (143 registers) unless the allocator is forced, and measured within run-to-run spread of this form
 __global__ void __launch_bounds__(GB_THREADS) head_bwd_kernel(const BlockArgs a) {
   extern __shared__ float4 lds4[];
   float* lds = reinterpret_cast<float*>(lds4);
   const int lane = threadIdx.x & 63, j = lane & 15, g = lane >> 4;
-  const int wv = threadIdx.x >> 6;
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int wave = blockIdx.x * (GB_THREADS / 64) + wv;
   const int nwaves = gridDim.x * (GB_THREADS / 64);
-  float* ty = lds + (size_t)wv * C * TS;  // LN1(x)^T [16 c][TS]
+  float* ty = lds + (size_t)wv * (C + QKV) * TS;  // LN1(x)^T [16 c][TS]
+  float* tq = ty + C * TS;                         // dqkv^T   [48 ch][TS]
 
   float wt[3][4];  // A[i = in channel j][k = g <-> out channel 16m+4g+r]
 #pragma unroll
@@ -159,53 +216,69 @@ __global__ void __launch_bounds__(GB_THREADS) head_bwd_kernel(const BlockArgs a)
 #pragma unroll
   for (int m = 0; m < 3; ++m) { accw[m] = zero4; accb[m] = zero4; }
 
-  for (int tile = wave; tile < a.total_tiles; tile += nwaves) {
-    const int n = tile / a.tiles_per_img;
-    const int p0 = (tile - n * a.tiles_per_img) * 16;
-    const size_t off = (size_t)n * C * a.L + p0 + j;
-    const float* dq = a.dqkv + (size_t)n * QKV * a.L + p0;
-    const f32x4 xv = load_tile(a.x + off, a.L, g);
-    const f32x4 gxv = load_tile(a.gx + off, a.L, g);
-    f32x4 dqv[3], dqt[3];
+  if (wave < a.total_tiles) {  // a wave without a tile loads nothing
+    TileWalk tw(a, wave, nwaves);
+    size_t off = tw.base(C, a.L) + j;
+    f32x4 xv = load_tile(a.x + off, a.L, g);
+    f32x4 gxv = load_tile(a.gx + off, a.L, g);
+    wait_prologue_loads();
+    for (;;) {
+      // d qkv of the tile in hand goes first, so that waiting for it leaves the prefetch behind it in flight
+      f32x4 dqv[3];
+      {
+        const float* dqp = a.dqkv + tw.base(QKV, a.L) + j;
 #pragma unroll
-    for (int m = 0; m < 3; ++m) {
-      dqv[m] = load_tile(dq + (size_t)(16 * m) * a.L + j, a.L, g);
-      // the same tile transposed: channel 16m+j, pixels 4g..4g+3 (A operand of the weight gradient)
-      dqt[m] = *reinterpret_cast<const f32x4*>(dq + (size_t)(16 * m + j) * a.L + 4 * g);
-    }
-    const Ln s = ln_stats(xv, a.eps);
-    f32x4 dy = zero4;
+        for (int m = 0; m < 3; ++m) dqv[m] = load_tile(dqp + (size_t)(16 * m) * a.L, a.L, g);
+      }
+      // the last iteration re-reads its own tile instead of branching around the prefetch
+      const TileWalk nx = tw.next();
+      const bool more = nx.n < a.N;
+      const size_t offn = (more ? nx : tw).base(C, a.L) + j;
+      const f32x4 xn = load_tile(a.x + offn, a.L, g);
+      const f32x4 gxn = load_tile(a.gx + offn, a.L, g);
+      prefetch_fence();
 #pragma unroll
-    for (int m = 0; m < 3; ++m) {
+      for (int m = 0; m < 3; ++m) lds_put_tile(tq + 16 * m * TS, j, g, dqv[m]);
+      const Ln s = ln_stats(xv, a.eps);
+      f32x4 dy = zero4;
+#pragma unroll
+      for (int m = 0; m < 3; ++m) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          dy = MFMA16(wt[m][r], dqv[m][r], dy);
+          accb[m][r] += dqv[m][r];
+        }
+      }
+      // LayerNorm backward (dy is the gradient of y = xhat * gamma + beta)
+      f32x4 gy;
+      float s1 = 0.f, s2 = 0.f;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        dy = MFMA16(wt[m][r], dqv[m][r], dy);
-        accb[m][r] += dqv[m][r];
+        gy[r] = dy[r] * gam[r];
+        s1 += gy[r];
+        s2 = fmaf(gy[r], s.xhat[r], s2);
+        dgam[r] = fmaf(dy[r], s.xhat[r], dgam[r]);
+        dbet[r] += dy[r];
+        ty[(4 * g + r) * TS + j] = fmaf(s.xhat[r], gam[r], bet[r]);
       }
-    }
-    // LayerNorm backward (dy is the gradient of y = xhat * gamma + beta)
-    f32x4 gy;
-    float s1 = 0.f, s2 = 0.f;
+      const float m1 = gsum4(s1) * INV_C, m2 = gsum4(s2) * INV_C;
+      f32x4 dxv;
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      gy[r] = dy[r] * gam[r];
-      s1 += gy[r];
-      s2 = fmaf(gy[r], s.xhat[r], s2);
-      dgam[r] = fmaf(dy[r], s.xhat[r], dgam[r]);
-      dbet[r] += dy[r];
-      ty[(4 * g + r) * TS + j] = fmaf(s.xhat[r], gam[r], bet[r]);
-    }
-    const float m1 = gsum4(s1) * INV_C, m2 = gsum4(s2) * INV_C;
-    f32x4 dxv;
+      for (int r = 0; r < 4; ++r) dxv[r] = s.rs * (gy[r] - m1 - s.xhat[r] * m2) + gxv[r];
+      store_tile(a.dx + off, a.L, g, dxv);
+      // dW[ch][c] += sum_px dqkv[px][ch] y[px][c]
+      const f32x4 yt = lds_row4(ty, j, g);  // B[k = px 4g+e][c = j]
 #pragma unroll
-    for (int r = 0; r < 4; ++r) dxv[r] = s.rs * (gy[r] - m1 - s.xhat[r] * m2) + gxv[r];
-    store_tile(a.dx + off, a.L, g, dxv);
-    // dW[ch][c] += sum_px dqkv[px][ch] y[px][c]
-    const f32x4 yt = *reinterpret_cast<const f32x4*>(ty + j * TS + 4 * g);  // B[k = px 4g+e][c = j]
+      for (int m = 0; m < 3; ++m) {
+        const f32x4 dqtm = lds_row4(tq, 16 * m + j, g);  // A[i = ch 16m+j][k = px 4g+e]
 #pragma unroll
-    for (int m = 0; m < 3; ++m) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) accw[m] = MFMA16(dqt[m][e], yt[e], accw[m]);
+        for (int e = 0; e < 4; ++e) accw[m] = MFMA16(dqtm[e], yt[e], accw[m]);
+      }
+      if (!more) break;
+      xv = xn;
+      gxv = gxn;
+      off = offn;
+      tw = nx;
     }
   }
 
@@ -235,7 +308,7 @@ __global__ void __launch_bounds__(GB_THREADS) head_bwd_kernel(const BlockArgs a)
 // ---------------------------------------------------------------------------------- tail, forward
 __global__ void __launch_bounds__(GB_THREADS) tail_fwd_kernel(const BlockArgs a) {
   const int lane = threadIdx.x & 63, j = lane & 15, g = lane >> 4;
-  const int wave = blockIdx.x * (GB_THREADS / 64) + (threadIdx.x >> 6);
+  const int wave = blockIdx.x * (GB_THREADS / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int nwaves = gridDim.x * (GB_THREADS / 64);
   float wpf[4], w1f[4][4], w2f[4][4];
   f32x4 b1r[4];
@@ -252,11 +325,20 @@ __global__ void __launch_bounds__(GB_THREADS) tail_fwd_kernel(const BlockArgs a)
   }
   const f32x4 bpv = load_vec(a.bp, g), b2v = load_vec(a.b2, g);
   const f32x4 gam = load_vec(a.g2, g), bet = load_vec(a.be2, g);
-  for (int tile = wave; tile < a.total_tiles; tile += nwaves) {
-    const int n = tile / a.tiles_per_img;
-    const size_t off = (size_t)n * C * a.L + (tile - n * a.tiles_per_img) * 16 + j;
-    const f32x4 xv = load_tile(a.x + off, a.L, g);
-    const f32x4 ov = load_tile(a.o + off, a.L, g);
+  if (wave >= a.total_tiles) return;  // a wave without a tile loads nothing
+  TileWalk tw(a, wave, nwaves);
+  size_t off = tw.base(C, a.L) + j;
+  f32x4 xv = load_tile(a.x + off, a.L, g);
+  f32x4 ov = load_tile(a.o + off, a.L, g);
+  wait_prologue_loads();
+  for (;;) {
+    // the last iteration re-reads its own tile instead of branching around the prefetch
+    const TileWalk nx = tw.next();
+    const bool more = nx.n < a.N;
+    const size_t offn = (more ? nx : tw).base(C, a.L) + j;
+    const f32x4 xn = load_tile(a.x + offn, a.L, g);
+    const f32x4 on = load_tile(a.o + offn, a.L, g);
+    prefetch_fence();
     f32x4 xm = xv + bpv;
 #pragma unroll
     for (int r = 0; r < 4; ++r) xm = MFMA16(wpf[r], ov[r], xm);
@@ -278,6 +360,11 @@ __global__ void __launch_bounds__(GB_THREADS) tail_fwd_kernel(const BlockArgs a)
       for (int r = 0; r < 4; ++r) out = MFMA16(w2f[m][r], gelu_f(h[m][r]), out);
     }
     store_tile(a.xnew + off, a.L, g, out);
+    if (!more) break;
+    xv = xn;
+    ov = on;
+    off = offn;
+    tw = nx;
   }
 }
 
@@ -288,13 +375,15 @@ __global__ void __launch_bounds__(GB_THREADS) tail_bwd_kernel(const BlockArgs a)
   extern __shared__ float4 lds4[];
   float* lds = reinterpret_cast<float*>(lds4);
   const int lane = threadIdx.x & 63, j = lane & 15, g = lane >> 4;
-  const int wv = threadIdx.x >> 6;
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int wave = blockIdx.x * (GB_THREADS / 64) + wv;
   const int nwaves = gridDim.x * (GB_THREADS / 64);
-  float* tg = lds + (size_t)wv * (2 * HD + 2 * C) * TS;  // G^T     [64][TS]
+  float* tg = lds + (size_t)wv * TB_WAVE_ROWS * TS;       // G^T     [64][TS]
   float* th = tg + HD * TS;                              // dH^T    [64][TS]
   float* ty = th + HD * TS;                              // LN2^T   [16][TS]
   float* tx = ty + C * TS;                               // dx_mid^T[16][TS]
+  float* td = tx + C * TS;                               // D^T     [16][TS]
+  float* to = td + C * TS;                               // o^T     [16][TS]
 
   // Weight fragments depend on the lane only, not on the wave or the tile: the workgroup keeps ONE
   // copy in LDS ([fragment][lane], conflict-free ds_read_b32) instead of 64 VGPRs per lane — with
@@ -303,7 +392,7 @@ __global__ void __launch_bounds__(GB_THREADS) tail_bwd_kernel(const BlockArgs a)
   //   w2t[m][r] = W2[4g+r][16m+j]      A[i = hidden 16m+j][k <-> co 4g+r]      (dG = W_2^T D)
   //   w1t[m][r] = W1[16m+4g+r][j]      A[i = c j][k <-> hidden 16m+4g+r]       (dY = W_1^T dH)
   //   b1r[m][r] = b1[16m+4g+r]
-  float* wl = lds + (size_t)4 * (2 * HD + 2 * C) * TS;  // [64 fragments][64 lanes]
+  float* wl = lds + (size_t)4 * TB_WAVE_ROWS * TS;  // [64 fragments][64 lanes]
   if (wv == 0) {
 #pragma unroll
     for (int m = 0; m < 4; ++m) {
@@ -335,98 +424,114 @@ __global__ void __launch_bounds__(GB_THREADS) tail_bwd_kernel(const BlockArgs a)
 #pragma unroll
   for (int m = 0; m < 4; ++m) { acc1[m] = zero4; acc2[m] = zero4; db1[m] = zero4; }
 
-  for (int tile = wave; tile < a.total_tiles; tile += nwaves) {
-    const int n = tile / a.tiles_per_img;
-    const int p0 = (tile - n * a.tiles_per_img) * 16;
-    const size_t img = (size_t)n * C * a.L + p0;
-    const size_t off = img + j;
-    const f32x4 xv = load_tile(a.x + off, a.L, g);
-    const f32x4 ov = load_tile(a.o + off, a.L, g);
-    const f32x4 dv = load_tile(a.dxnew + off, a.L, g);
-    // transposed fragments (channel j, pixels 4g..4g+3) for the weight gradients: L2 hits
-    const f32x4 dvt = *reinterpret_cast<const f32x4*>(a.dxnew + img + (size_t)j * a.L + 4 * g);
-    const f32x4 ot = *reinterpret_cast<const f32x4*>(a.o + img + (size_t)j * a.L + 4 * g);
+  if (wave < a.total_tiles) {  // a wave without a tile loads nothing
+    TileWalk tw(a, wave, nwaves);
+    size_t off = tw.base(C, a.L) + j;
+    f32x4 xv = load_tile(a.x + off, a.L, g);
+    f32x4 ov = load_tile(a.o + off, a.L, g);
+    f32x4 dv = load_tile(a.dxnew + off, a.L, g);
+    wait_prologue_loads();
+    for (;;) {
+      // the last iteration re-reads its own tile instead of branching around the prefetch
+      const TileWalk nx = tw.next();
+      const bool more = nx.n < a.N;
+      const size_t offn = (more ? nx : tw).base(C, a.L) + j;
+      const f32x4 xn = load_tile(a.x + offn, a.L, g);
+      const f32x4 on = load_tile(a.o + offn, a.L, g);
+      const f32x4 dn = load_tile(a.dxnew + offn, a.L, g);
+      prefetch_fence();
+      lds_put_tile(td, j, g, dv);
+      lds_put_tile(to, j, g, ov);
 
-    // ---- recompute the forward: x_mid, LN2, hidden
-    f32x4 xm = xv + bpv;
+      // ---- recompute the forward: x_mid, LN2, hidden
+      f32x4 xm = xv + bpv;
 #pragma unroll
-    for (int r = 0; r < 4; ++r) xm = MFMA16(wpf[r], ov[r], xm);
-    const Ln s = ln_stats(xm, a.eps);
-    f32x4 y;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      y[r] = fmaf(s.xhat[r], gam[r], bet[r]);
-      ty[(4 * g + r) * TS + j] = y[r];
-      db2[r] += dv[r];
-    }
-    f32x4 h[4], dg[4];
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-      h[m] = f32x4{B1R(m, 0), B1R(m, 1), B1R(m, 2), B1R(m, 3)};
-      dg[m] = zero4;
+      for (int r = 0; r < 4; ++r) xm = MFMA16(wpf[r], ov[r], xm);
+      const Ln s = ln_stats(xm, a.eps);
+      f32x4 y;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        h[m] = MFMA16(W1F(m, r), y[r], h[m]);
-        dg[m] = MFMA16(W2T(m, r), dv[r], dg[m]);
+        y[r] = fmaf(s.xhat[r], gam[r], bet[r]);
+        ty[(4 * g + r) * TS + j] = y[r];
+        db2[r] += dv[r];
       }
-    }
-    // ---- G, dH = dG * gelu'(H); dY = W_1^T dH
-    f32x4 dy = zero4;
+      f32x4 h[4], dg[4];
 #pragma unroll
-    for (int m = 0; m < 4; ++m) {
+      for (int m = 0; m < 4; ++m) {
+        h[m] = f32x4{B1R(m, 0), B1R(m, 1), B1R(m, 2), B1R(m, 3)};
+        dg[m] = zero4;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          h[m] = MFMA16(W1F(m, r), y[r], h[m]);
+          dg[m] = MFMA16(W2T(m, r), dv[r], dg[m]);
+        }
+      }
+      // ---- G, dH = dG * gelu'(H); dY = W_1^T dH
+      f32x4 dy = zero4;
+#pragma unroll
+      for (int m = 0; m < 4; ++m) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float hv = h[m][r];
+          float cdf, ee;
+          pg_gelu_parts(hv, cdf, ee);
+          const float pdf = 0.39894228040143267794f * ee;
+          const float dh = dg[m][r] * (cdf + hv * pdf);
+          const int hid = 16 * m + 4 * g + r;
+          tg[hid * TS + j] = hv * cdf;
+          th[hid * TS + j] = dh;
+          db1[m][r] += dh;
+          dy = MFMA16(W1T(m, r), dh, dy);
+        }
+      }
+      // ---- LN2 backward, d x_mid = D + LN2'(dY)
+      f32x4 gy, dxm;
+      float s1 = 0.f, s2 = 0.f;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const float hv = h[m][r];
-        float cdf, ee;
-        pg_gelu_parts(hv, cdf, ee);
-        const float pdf = 0.39894228040143267794f * ee;
-        const float dh = dg[m][r] * (cdf + hv * pdf);
-        const int hid = 16 * m + 4 * g + r;
-        tg[hid * TS + j] = hv * cdf;
-        th[hid * TS + j] = dh;
-        db1[m][r] += dh;
-        dy = MFMA16(W1T(m, r), dh, dy);
+        gy[r] = dy[r] * gam[r];
+        s1 += gy[r];
+        s2 = fmaf(gy[r], s.xhat[r], s2);
+        dgam[r] = fmaf(dy[r], s.xhat[r], dgam[r]);
+        dbet[r] += dy[r];
       }
-    }
-    // ---- LN2 backward, d x_mid = D + LN2'(dY)
-    f32x4 gy, dxm;
-    float s1 = 0.f, s2 = 0.f;
+      const float m1 = gsum4(s1) * INV_C, m2 = gsum4(s2) * INV_C;
+      f32x4 dov = zero4, gxv;
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      gy[r] = dy[r] * gam[r];
-      s1 += gy[r];
-      s2 = fmaf(gy[r], s.xhat[r], s2);
-      dgam[r] = fmaf(dy[r], s.xhat[r], dgam[r]);
-      dbet[r] += dy[r];
-    }
-    const float m1 = gsum4(s1) * INV_C, m2 = gsum4(s2) * INV_C;
-    f32x4 dov = zero4, gxv;
+      for (int r = 0; r < 4; ++r) {
+        dxm[r] = dv[r] + s.rs * (gy[r] - m1 - s.xhat[r] * m2);
+        tx[(4 * g + r) * TS + j] = dxm[r];
+        dbp[r] += dxm[r];
+        gxv[r] = dv[r] + dxm[r];
+      }
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      dxm[r] = dv[r] + s.rs * (gy[r] - m1 - s.xhat[r] * m2);
-      tx[(4 * g + r) * TS + j] = dxm[r];
-      dbp[r] += dxm[r];
-      gxv[r] = dv[r] + dxm[r];
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) dov = MFMA16(wpt[r], dxm[r], dov);
-    store_tile(a.d_o + off, a.L, g, dov);
-    store_tile(a.gx_out + off, a.L, g, gxv);
+      for (int r = 0; r < 4; ++r) dov = MFMA16(wpt[r], dxm[r], dov);
+      store_tile(a.d_o + off, a.L, g, dov);
+      store_tile(a.gx_out + off, a.L, g, gxv);
 
-    // ---- weight gradients: contraction over the tile's pixels (pixel 4g+e in K-step e)
-    const f32x4 yt = *reinterpret_cast<const f32x4*>(ty + j * TS + 4 * g);   // B[k = px][c = j]
-    const f32x4 xt = *reinterpret_cast<const f32x4*>(tx + j * TS + 4 * g);   // A[i = co j][k = px]
+      // ---- weight gradients: contraction over the tile's pixels (pixel 4g+e in K-step e)
+      const f32x4 yt = lds_row4(ty, j, g);   // B[k = px][c = j]
+      const f32x4 xt = lds_row4(tx, j, g);   // A[i = co j][k = px]
+      const f32x4 dvt = lds_row4(td, j, g);  // A[i = co j][k = px]
+      const f32x4 ot = lds_row4(to, j, g);   // B[k = px][ci = j]
 #pragma unroll
-    for (int e = 0; e < 4; ++e) accp = MFMA16(xt[e], ot[e], accp);            // dWp[co][ci]
+      for (int e = 0; e < 4; ++e) accp = MFMA16(xt[e], ot[e], accp);            // dWp[co][ci]
 #pragma unroll
-    for (int m = 0; m < 4; ++m) {
-      const f32x4 gt = *reinterpret_cast<const f32x4*>(tg + (16 * m + j) * TS + 4 * g);  // B[k = px][hidden]
-      const f32x4 ht = *reinterpret_cast<const f32x4*>(th + (16 * m + j) * TS + 4 * g);  // A[hidden][k = px]
+      for (int m = 0; m < 4; ++m) {
+        const f32x4 gt = *reinterpret_cast<const f32x4*>(tg + (16 * m + j) * TS + 4 * g);  // B[k = px][hidden]
+        const f32x4 ht = *reinterpret_cast<const f32x4*>(th + (16 * m + j) * TS + 4 * g);  // A[hidden][k = px]
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        acc2[m] = MFMA16(dvt[e], gt[e], acc2[m]);  // dW2[co][hidden] += D[px][co] G[px][hidden]
-        acc1[m] = MFMA16(ht[e], yt[e], acc1[m]);   // dW1[hidden][c]  += dH[px][hidden] y[px][c]
+        for (int e = 0; e < 4; ++e) {
+          acc2[m] = MFMA16(dvt[e], gt[e], acc2[m]);  // dW2[co][hidden] += D[px][co] G[px][hidden]
+          acc1[m] = MFMA16(ht[e], yt[e], acc1[m]);   // dW1[hidden][c]  += dH[px][hidden] y[px][c]
+        }
       }
+      if (!more) break;
+      xv = xn;
+      ov = on;
+      dv = dn;
+      off = offn;
+      tw = nx;
     }
   }
 
@@ -565,16 +670,16 @@ __global__ void __launch_bounds__(256) seg_reduceN_kernel(const SegArgsN an) {
   }
 }
 
-// Workgroups per launch: whole rounds of resident waves (256 CUs x 4 SIMDs; the kernels hold 5 / 3 / 4 / 2
-// waves per SIMD by their register counts), at least `min_tiles` tiles per wave. which: 0 head fwd,
-// 1 head bwd, 2 tail fwd, 3 tail bwd. PG_BLOCK_GRID="a,b,c,d" overrides the caps (tuning).
+// Workgroups per launch, at least `min_tiles` tiles per wave. which: 0 head fwd, 1 head bwd, 2 tail fwd, 3 tail bwd.
+// Resident waves per SIMD by register count (75 / 126 / 123 / 248 VGPRs): 6 / 4 / 4 / 2; tail bwd is also held at two
+// workgroups per CU by its 76 KiB of LDS. PG_BLOCK_GRID="a,b,c,d" overrides the caps (tuning).
 int grid_blocks(int which, int N, int L) {
   // immutable init-once tables (function-local static with an initialiser: thread-safe; the library
   // is entered from the main thread and from the autograd thread)
   struct Cfg { int cap[4]; int mt[2]; };
   static const Cfg cfg = []() {
-    Cfg c = {{2048, 1024, 2048, 512},  // measured: head bwd 79.8 us at 512, 68.9 at 768; round 5 (122 registers = four waves per SIMD since the
-                                      // VGPR-form build): 1024 = one full round, ImageGPT 99.16 -> 99.88 k img/s on one box (sweep in profiles/README.md)
+    Cfg c = {{2048, 1024, 2048, 512},  // the backward caps are one full round of resident waves; the re-sweep with the pipelined
+                                      // loops moved nothing beyond spread (profiles/gpt_block_pipeline.json, "grid_sweep_us_per_launch")
              {1, 2}};                 // tiles per wave below which the grid shrinks (forward, backward);
                                       // measured at batch 64: (4, 8) 1.82 ms/step, (2, 4) 1.59, (1, 2) 1.53, (1, 1) 1.56
     if (const char* e = PG_AB_ENV("PG_BLOCK_GRID")) {
@@ -683,7 +788,7 @@ int head_bwd_impl(const float* x, const float* ln_w, const float* ln_b, const fl
   set_geometry(a, N, L, eps);
   const int blocks = grid_blocks(1, N, L);
   hipStream_t st = (hipStream_t)stream;
-  const size_t tr = (size_t)4 * C * TS, rd = (size_t)4 * H_PART;
+  const size_t tr = (size_t)4 * (C + QKV) * TS, rd = (size_t)4 * H_PART;
   hipLaunchKernelGGL(head_bwd_kernel, dim3((unsigned)blocks), dim3(GB_THREADS), (tr > rd ? tr : rd) * sizeof(float), st, a);
   PG_LAUNCH_CHECK("pg_gpt_block_head_bwd");
   if (defer) return 0;
@@ -800,8 +905,8 @@ int tail_bwd_impl(const float* o, const float* x, const float* wp, const float* 
   set_geometry(a, N, L, eps);
   const int blocks = bwd_blocks(N, L);
   hipStream_t st = (hipStream_t)stream;
-  const size_t tr = (size_t)4 * (2 * HD + 2 * C) * TS + 64 * 64, rd = (size_t)4 * T_PART;
-  const size_t shmem = (tr > rd ? tr : rd) * sizeof(float);  // 66.4 KB: above the 64 KB default
+  const size_t tr = (size_t)4 * TB_WAVE_ROWS * TS + 64 * 64, rd = (size_t)4 * T_PART;
+  const size_t shmem = (tr > rd ? tr : rd) * sizeof(float);  // 76 KiB: above the 64 KB default, two workgroups per CU (160 KB)
   static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(tail_bwd_kernel),
                                                      hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
   (void)attr;  // thread-safe one-time opt-in
