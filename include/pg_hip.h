@@ -240,6 +240,16 @@ int pg_causal_attn_bwd_dkv(const float* q, const float* k, const float* v, const
  * Initial value: 1, or the environment's PG_ATTN_FUSED_BWD at load time. */
 int pg_attn_fused_bwd(int enable);
 
+/* Host only, launches nothing: how the d_k = d_v = 4 matrix-core kernels (attention_mfma.hip) split a sequence of L
+ * positions into blocks and hand them to the `waves` (1..8) waves of a workgroup; the launch reads the same plan.
+ * which: 0 forward, 1 dQ (query blocks; a ragged L puts its short block FIRST), 2 dK/dV, 3 fused backward (64-key
+ * blocks from 0). Entry e, wave by wave in the order a wave walks its list: block index, first row, 16-row groups
+ * owned, wave, cost (group evaluations for which 0 / 1; 4 * rank + 5 for 2 / 3). The arrays hold ceil(L / 64)
+ * entries. Returns the number of blocks, 0 if a wave's list would exceed 16 entries (the launch then leaves the
+ * shape to the VALU kernels), PG_EINVAL for bad arguments. */
+int pg_attn_block_plan(int which, int L, int waves, int* out_blk, int* out_q0, int* out_ngrp, int* out_wave,
+                       int* out_cost);
+
 /* ---------------------------------------------------------------------------------------
  * Linear causal attention (O(L) memory).  nn/attention.py:168-195 (_UnnormalizedLinearCausalAttention
  * forward / backward: the per-position loops) and :256-275 (LinearCausalAttention.forward):

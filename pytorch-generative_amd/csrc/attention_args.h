@@ -20,7 +20,20 @@ struct PgAttnArgs {
   // every SIMD — gets the same share of the causal triangle)
   unsigned char bcount[8];
   unsigned char blist[8][16];
+  // MFMA query-owner kernels (forward, dQ): when the 16-query groups do not fill whole 64-query blocks, the
+  // short block is block 0 and every later block starts qshift = 64 - 16 * (groups of block 0) queries early
+  // (0: whole blocks). Wave-uniform; pg_attn_query_block() is the only place that reads it.
+  int qshift;
 };
+
+// Queries [q0, q0 + 16 * ngrp) of block blk of the forward / dQ kernels (device and host planner alike).
+struct PgAttnQueryBlock { int q0, ngrp; };
+__host__ __device__ inline PgAttnQueryBlock pg_attn_query_block(int blk, int qshift) {
+  PgAttnQueryBlock b;
+  b.q0 = blk == 0 ? 0 : 64 * blk - qshift;
+  b.ngrp = blk == 0 ? 4 - (qshift >> 4) : 4;
+  return b;
+}
 
 enum { PG_ATTN_FWD = 0, PG_ATTN_DQ = 1, PG_ATTN_DKV = 2, PG_ATTN_BWD = 3 /* fused dQ + dK + dV (d_k = d_v = 4) */ };
 

@@ -31,10 +31,20 @@
 // workgroups per CU, and resident bf16x3 operands for k and v would not fit 128 registers; dP stays on
 // the fp32 16x16x4 tile, -lse2 / -delta in the C operands.)
 // A wave works on a 64-row block = four 16-row groups at a time (one K/V fragment feeds four
-// independent MFMA/exp chains). Each wave walks a host-made longest-processing-time list of blocks;
+// independent MFMA/exp chains). Each wave walks a host-made list of blocks (attn_plan() below);
 // workgroups have 4 (forward) or 8 (dQ, dK/dV) waves so that a CU's four SIMDs carry equal loads.
-// Measured (N=1024, 4 heads, L=784): fwd 0.37 ms, dQ 0.42 ms, dK/dV 0.52 ms vs 0.62 / 0.65 / 0.69 ms
-// for the VALU row-owner kernels; ~0.1 ms of each is staging, per-block set-up and the diagonal.
+// Block walk of the query owners (forward, dQ): a block streams every key tile below it with all four
+// groups, so a block that is not full must not be the one with the most keys below it. With
+// G = ceil(L / 16) groups and F = G mod 4 != 0, block 0 is queries [0, 16 F) — one to three diagonal
+// steps, nothing below — and block b >= 1 is [16 F + 64 (b - 1), + 64), always full (PgAttnArgs::qshift,
+// pg_attn_query_block()). L = 784 (49 groups): 1 + 12 blocks, 307 tile steps of four groups per (n, head)
+// where blocks cut at multiples of 64 ran 343, 36.75 of them for the three groups that the last
+// block, behind 48 key tiles, did not have. The key owners (dK/dV, fused backward) keep blocks from 0:
+// their short block is the LAST key block, which streams the fewest queries.
+// Measured (N=1024, 4 heads, L=784) with blocks cut at multiples of 64: fwd 0.37 ms (0.33 in the step),
+// dQ 0.42 ms, dK/dV 0.52 ms vs 0.62 / 0.65 / 0.69 ms for the VALU row-owner kernels; ~0.1 ms of each is
+// staging, per-block set-up and the diagonal. The short-block-first walk issues 10.5 % fewer tile steps in
+// fwd and dQ; it has not been timed yet (profiles/attn_fwd_partition.json).
 #include <stdio.h>
 #include <stdlib.h>
 
@@ -247,9 +257,9 @@ __global__ void __launch_bounds__(512) attn_fwd_m44_kernel(const PgAttnArgs a) {
   const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll 1
   for (int it = 0; it < nmine; ++it) {
-    const int blk = a.blist[d.wave][it];
-    const int q0 = 64 * blk;
-    const int ngrp = min(4, (L - q0 + 15) >> 4);  // 16-query groups of this block that exist
+    const PgAttnQueryBlock qb = pg_attn_query_block(a.blist[d.wave][it], a.qshift);
+    const int q0 = qb.q0;
+    const int ngrp = qb.ngrp;  // 16-query groups this block owns (fewer than 4: block 0 of a ragged L only)
 
     float mcur[4], lsum[4];
     bf16x8 bq[4];
@@ -349,8 +359,9 @@ __global__ void __launch_bounds__(512) attn_fwd_m44_kernel(const PgAttnArgs a) {
       step(k0, kf, vf, I<0>{}, I<0>{}, B<false>{});
     }
 
-    // ---- the block's own 64 keys: tile u meets groups t >= u, group u on its diagonal. (Groups
-    //      beyond L in the last block run along on zero queries; they are never stored.)
+    // ---- the block's own keys: tile u meets groups t >= u, group u on its diagonal. (Block 0 of a
+    //      ragged L owns ngrp < 4 groups; the others run along on block 1's queries through its ngrp
+    //      tiles and are never stored.)
     if (q0 != 0) step(q0, frag_k(q0), frag_v(q0), I<0>{}, I<1>{}, B<false>{});
     if (ngrp > 1) step(q0 + 16, frag_k(q0 + 16), frag_v(q0 + 16), I<1>{}, I<1>{}, B<false>{});
     if (ngrp > 2) step(q0 + 32, frag_k(q0 + 32), frag_v(q0 + 32), I<2>{}, I<1>{}, B<false>{});
@@ -433,9 +444,9 @@ __global__ void __launch_bounds__(512) attn_dq_m44_kernel(const PgAttnArgs a) {
   const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll 1
   for (int it = 0; it < nmine; ++it) {
-    const int blk = a.blist[d.wave][it];
-    const int q0 = 64 * blk;
-    const int ngrp = min(4, (L - q0 + 15) >> 4);
+    const PgAttnQueryBlock qb = pg_attn_query_block(a.blist[d.wave][it], a.qshift);
+    const int q0 = qb.q0;
+    const int ngrp = qb.ngrp;
 
     bf16x8 bq[4], bg[4];  // resident operands: q (constant -lse2) and dO (constant -delta)
     f32x4 acc[4];
@@ -454,7 +465,7 @@ __global__ void __launch_bounds__(512) attn_dq_m44_kernel(const PgAttnArgs a) {
         qv[dd] *= a.scale2;
         dl = fmaf(gv[dd], ov[dd], dl);
       }
-      if (ok && g == 0) a.delta[row + qidx[t]] = dl;
+      if (ok && g == 0 && t < ngrp) a.delta[row + qidx[t]] = dl;  // groups >= ngrp of block 0 belong to block 1
       bq[t] = resident_operand(qv, -lse, g);
       bg[t] = resident_operand(gv, -dl, g);
       acc[t] = zero4;
@@ -1019,6 +1030,175 @@ PG_EXPORT int pg_attn_fused_bwd(int enable) {
   return fused_bwd_flag().exchange(enable ? 1 : 0, std::memory_order_relaxed);
 }
 
+// ---- which wave walks which blocks ---------------------------------------------------------------
+// Key-owner kernels (dK/dV, fused backward): 64-key blocks from 0, cost 4 * rank + 5 (earlier key blocks
+// stream more queries), each block in decreasing cost to the least loaded wave (LPT).
+// Query-owner kernels (forward, dQ): blocks as pg_attn_query_block() cuts them, cost = the 16-query group
+// evaluations the kernel issues for the block (quarter tile steps): 4 per streamed tile below the block
+// plus 4 + 3 + 2 + 1 on its diagonal, and 4 + .. + (5 - ngrp) for a short block 0. LPT as above, then
+// (a) moves and swaps between the most loaded wave and any other wave while one lowers the larger of
+// the two loads, (b) a depth-first search over assignments below that bound. The block costs of one L
+// share a 16-unit lattice on which (a) alone stalls (L = 784, 4 waves: LPT 330, optimum 312); (b) is
+// exact whenever it finishes within its node budget, which it does for every L that fits the kernels' LDS
+// at 8 waves and far beyond the bench shapes at 4. A wave's list stays sorted heaviest first.
+struct AttnPlan {
+  int nb, waves, qshift;  // nb = 0: a wave's list would exceed 16 entries (the caller falls back)
+  unsigned char bcount[8], blist[8][16];
+  int cost[128];          // per block
+};
+
+struct AttnPlanSearch {
+  const int* cost;  // decreasing
+  int n, W;
+  long best, lower, nodes, load[8], rest[129];
+  int count[8], cur[128], found[128];
+  bool improved;
+};
+static void attn_plan_dfs(AttnPlanSearch& s, int i) {
+  if (i == s.n) {  // every assignment on the way kept its wave below s.best
+    s.best = 0;
+    for (int w = 0; w < s.W; ++w) s.best = s.load[w] > s.best ? s.load[w] : s.best;
+    for (int k = 0; k < s.n; ++k) s.found[k] = s.cur[k];
+    s.improved = true;
+    return;
+  }
+  if (++s.nodes > (1L << 18)) return;  // node budget: tens of milliseconds, once per (kernel, L, waves)
+  long room = 0;
+  for (int w = 0; w < s.W; ++w) room += s.best - 1 - s.load[w];
+  if (room < s.rest[i]) return;
+  for (int w = 0; w < s.W; ++w) {
+    if (s.count[w] >= 16 || s.load[w] + s.cost[i] >= s.best) continue;
+    bool twin = false;  // an earlier wave in the same state: the same subtree
+    for (int v = 0; v < w; ++v) twin = twin || (s.load[v] == s.load[w] && s.count[v] == s.count[w]);
+    if (twin) continue;
+    s.cur[i] = w; s.load[w] += s.cost[i]; ++s.count[w];
+    attn_plan_dfs(s, i + 1);
+    s.load[w] -= s.cost[i]; --s.count[w];
+    if (s.best <= s.lower) return;
+  }
+}
+
+static AttnPlan attn_make_plan(int which, int L, int W) {
+  AttnPlan p = {};
+  const int NB = (L + 63) / 64;
+  if (W > NB) W = NB;
+  if (L < 1 || W < 1 || (NB + W - 1) / W > 16) return p;
+  p.waves = W;
+  long load[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  if (which == PG_ATTN_DKV || which == PG_ATTN_BWD) {
+    for (int rank = NB - 1; rank >= 0; --rank) {
+      const int blk = NB - 1 - rank;
+      int best = 0;
+      for (int w = 1; w < W; ++w)
+        if (load[w] < load[best] && p.bcount[w] < 16) best = w;
+      if (p.bcount[best] >= 16) return p;
+      p.blist[best][p.bcount[best]++] = (unsigned char)blk;
+      p.cost[blk] = 4 * rank + 5;
+      load[best] += 4 * rank + 5;
+    }
+    p.nb = NB;
+    return p;
+  }
+  const int groups = (L + 15) / 16;
+  p.qshift = groups % 4 ? 64 - 16 * (groups % 4) : 0;
+  int order[128], cost[128], wave_of[128];  // order[i]: the i-th heaviest block, cost[i] its cost
+  for (int blk = 0; blk < NB; ++blk) {
+    const PgAttnQueryBlock b = pg_attn_query_block(blk, p.qshift);
+    int c = 4 * (b.q0 / 16);
+    for (int u = 0; u < b.ngrp; ++u) c += 4 - u;
+    p.cost[blk] = c;
+  }
+  for (int i = 0; i < NB; ++i) order[i] = NB - 1 - i;  // costs grow with the block index
+  for (int i = 0; i < NB; ++i) cost[i] = p.cost[order[i]];
+  int count[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  long total = 0;
+  for (int i = 0; i < NB; ++i) {
+    int best = 0;
+    for (int w = 1; w < W; ++w)
+      if (load[w] < load[best] && count[w] < 16) best = w;
+    if (count[best] >= 16) return p;
+    wave_of[i] = best; ++count[best];
+    load[best] += cost[i];
+    total += cost[i];
+  }
+  // (a) moves and swaps out of the most loaded wave
+  for (;;) {
+    int m = 0;
+    for (int w = 1; w < W; ++w) m = load[w] > load[m] ? w : m;
+    long gain = load[m];
+    int gi = -1, gj = -1, gw = -1;
+    for (int i = 0; i < NB; ++i) {
+      if (wave_of[i] != m) continue;
+      for (int w = 0; w < W; ++w) {
+        if (w == m) continue;
+        for (int j = -1; j < NB; ++j) {  // j = -1: move block i to wave w; otherwise swap it with block j of w
+          if (j < 0 ? count[w] >= 16 : wave_of[j] != w) continue;
+          const int cj = j < 0 ? 0 : cost[j];
+          const long lm = load[m] - cost[i] + cj, lw = load[w] + cost[i] - cj;
+          const long worst = lm > lw ? lm : lw;
+          if (worst < gain) { gain = worst; gi = i; gj = j; gw = w; }
+        }
+      }
+    }
+    if (gi < 0) break;
+    load[m] -= cost[gi]; load[gw] += cost[gi]; wave_of[gi] = gw;
+    if (gj >= 0) { load[gw] -= cost[gj]; load[m] += cost[gj]; wave_of[gj] = m; }
+    else { --count[m]; ++count[gw]; }
+  }
+  // (b) anything strictly better
+  AttnPlanSearch s = {};
+  s.cost = cost; s.n = NB; s.W = W;
+  for (int w = 0; w < W; ++w) s.best = load[w] > s.best ? load[w] : s.best;
+  s.lower = (total + W - 1) / W > cost[0] ? (total + W - 1) / W : cost[0];
+  for (int i = NB - 1; i >= 0; --i) s.rest[i] = s.rest[i + 1] + cost[i];
+  if (s.best > s.lower) attn_plan_dfs(s, 0);
+  for (int i = 0; i < NB; ++i) {  // in decreasing cost: every wave's list comes out heaviest first
+    const int w = s.improved ? s.found[i] : wave_of[i];
+    p.blist[w][p.bcount[w]++] = (unsigned char)order[i];
+  }
+  p.nb = NB;
+  return p;
+}
+
+// the plan of (which, L, waves), made once: function-local statics (thread-safe one-time init, as in
+// attn_waves) and a lock around the table; entries are never removed, so the pointer stays valid
+#include <map>
+#include <mutex>
+#include <tuple>
+static const AttnPlan* attn_plan(int which, int L, int W) {
+  static std::mutex mu;
+  static std::map<std::tuple<int, int, int>, AttnPlan> table;
+  std::lock_guard<std::mutex> lock(mu);
+  const auto key = std::make_tuple(which, L, W);
+  auto it = table.find(key);
+  if (it == table.end()) it = table.emplace(key, attn_make_plan(which, L, W)).first;
+  return &it->second;
+}
+
+// Host only, launches nothing: the blocks pg_attn_mfma_launch hands to a workgroup of `waves` waves
+// (clamped to the block count as the launch does), wave by wave in list order. Returns the number of
+// blocks, 0 if the lists do not hold them (the launch then declines), PG_EINVAL for bad arguments.
+PG_EXPORT int pg_attn_block_plan(int which, int L, int waves, int* out_blk, int* out_q0, int* out_ngrp,
+                                 int* out_wave, int* out_cost) {
+  if (which < PG_ATTN_FWD || which > PG_ATTN_BWD || L < 1 || waves < 1 || waves > 8 || !out_blk || !out_q0 ||
+      !out_ngrp || !out_wave || !out_cost) {
+    pg_set_error("pg_attn_block_plan: bad argument");
+    return PG_EINVAL;
+  }
+  const AttnPlan* p = attn_plan(which, L, waves);
+  const bool key_owner = which == PG_ATTN_DKV || which == PG_ATTN_BWD;
+  int n = 0;
+  for (int w = 0; w < p->waves && p->nb; ++w) {
+    for (int i = 0; i < p->bcount[w]; ++i, ++n) {
+      const int blk = p->blist[w][i];
+      PgAttnQueryBlock b = pg_attn_query_block(blk, p->qshift);
+      if (key_owner) { b.q0 = 64 * blk; b.ngrp = (L - b.q0 + 15) / 16 < 4 ? (L - b.q0 + 15) / 16 : 4; }
+      out_blk[n] = blk; out_q0[n] = b.q0; out_ngrp[n] = b.ngrp; out_wave[n] = w; out_cost[n] = p->cost[blk];
+    }
+  }
+  return n;
+}
+
 int pg_attn_mfma_launch(int which, const PgAttnArgs& a0, hipStream_t st) {
   if (which == PG_ATTN_BWD) {
     // fused backward: d_k = d_v = 4 only; PG_ATTN_FUSED_BWD=0 keeps the two-kernel backward (A/B, and
@@ -1056,23 +1236,16 @@ int pg_attn_mfma_launch(int which, const PgAttnArgs& a0, hipStream_t st) {
   if (which == PG_ATTN_DKV && dkv_bf16 && !PG_AB_ENV("PG_ATTN_WAVES")) W = 8;
   // few (n, head) units (the reference's default batch 64 x 4 heads = one workgroup per CU): the launch
   // lasts as long as its most loaded wave, so the forward kernel also spreads its 13 query blocks over
-  // 8 waves (longest list 94 -> 58 cost units; with many units per CU 4-wave workgroups pack better)
+  // 8 waves (longest list 78 -> 47.5 tile steps; with many units per CU 4-wave workgroups pack better)
   if (which == PG_ATTN_FWD && (long)a.N * a.heads <= 512 && !PG_AB_ENV("PG_ATTN_WAVES")) W = 8;
-  if (W > NB) W = NB;
-  if ((NB + W - 1) / W > 16) return 0;  // block lists hold 16 entries per wave
-  // LPT: blocks by decreasing cost (later query blocks / earlier key blocks stream more), each to
-  // the least loaded wave
-  long load[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  for (int w = 0; w < 8; ++w) a.bcount[w] = 0;
-  for (int rank = NB - 1; rank >= 0; --rank) {
-    const int blk = (which == PG_ATTN_DKV || which == PG_ATTN_BWD) ? NB - 1 - rank : rank;
-    int best = 0;
-    for (int w = 1; w < W; ++w)
-      if (load[w] < load[best] && a.bcount[w] < 16) best = w;
-    if (a.bcount[best] >= 16) return 0;
-    a.blist[best][a.bcount[best]++] = (unsigned char)blk;
-    load[best] += 4 * rank + 5;
+  const AttnPlan* plan = attn_plan(which, a.L, W);
+  if (!plan->nb) return 0;  // block lists hold 16 entries per wave
+  W = plan->waves;
+  for (int w = 0; w < 8; ++w) {
+    a.bcount[w] = plan->bcount[w];
+    for (int i = 0; i < 16; ++i) a.blist[w][i] = plan->blist[w][i];
   }
+  a.qshift = plan->qshift;
   a.vec = a.L % 4 == 0 ? 1 : 0;
   if (which == PG_ATTN_FWD)
     a.vec = a.vec && aligned16(a.o_out) && a.o_bs % 4 == 0;
