@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define PG_ABI_VERSION 1
+#define PG_ABI_VERSION 2
 
 #define PG_EINVAL (-1)  /* bad argument */
 #define PG_ESHAPE (-2)  /* shape outside what the kernels support (no silent fallback) */
@@ -574,6 +574,21 @@ int pg_vq_ema_update(const float* x, const int* idx, float* cluster_size, float*
 /* dx = d_st + g_loss[0] * 2 (x - q) / n  (straight-through + commitment loss) */
 int pg_vq_bwd(const float* x, const float* q, const float* d_st, const float* g_loss, float* dx,
               size_t n, void* stream);
+/* pg_vq_assign for any D >= 1 (csrc/vq_mfma.hip): the distances as a tiled fp32-MFMA GEMM with a running
+ * (best, index) per position, codes visited in ascending order with a strict '<' (first minimum). Same
+ * operands and outputs as pg_vq_assign. PG_ESHAPE for a non-positive dimension, D > 2^20, K > 65535 * 64,
+ * N * L > 2^31 - 65 or K * D >= 2^31; PG_EINVAL for a null operand. */
+int pg_vq_assign_tiled(const float* x, const float* embedding, int* idx, float* q, float* st, float* loss,
+                       int N, int D, int L, int K, void* stream);
+/* Gradient of the embedding loss mse(q, x.detach()) of a codebook trained by gradient descent (nn/utils.py:93):
+ *   d_embedding[k][d] (+)= g_loss[0] * (2 / (N L D)) * sum_{p : idx[p] = k} (q[p][d] - x[p][d])
+ * as onehot(idx)^T (q - x) over ranges of positions into `ws` (pg_vq_codebook_grad_workspace_floats floats; every word
+ * that is read is written first), merged in range order: no float atomics, bit-reproducible. accumulate != 0 adds
+ * into d_embedding (a flat-gradient sink). Shape errors as pg_vq_assign_tiled; PG_EINVAL for a null operand or a
+ * short workspace. The query returns 0 for shapes the launch refuses. */
+size_t pg_vq_codebook_grad_workspace_floats(int N, int D, int L, int K);
+int pg_vq_codebook_grad(const float* x, const float* q, const int* idx, const float* g_loss, float* d_embedding,
+                        int accumulate, int N, int D, int L, int K, float* ws, size_t ws_floats, void* stream);
 /* loss[0] += mean((a - b)^2) (zeroed by caller); da = g_loss[0] * 2 (a - b) / n, db = -da
  * (either may be NULL) */
 int pg_mse_fwd(const float* a, const float* b, float* loss, size_t n, void* stream);

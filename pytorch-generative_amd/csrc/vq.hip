@@ -1,11 +1,10 @@
 // vq.hip — vector quantisation (reference nn/utils.py:53-96) and the MSE loss of
 // the VQ-VAE recipes (models/vae/vq_vae.py:127-136).
 //
-// STATUS: written at the end of round 2 after the round's GPU budget was spent — compiled for gfx950,
-// NOT yet run on hardware. Nothing on the measured path calls these entry points; they are reached only
-// through pytorch_generative_amd/experimental/vq.py, whose GPU tests are opt-in (PG_TEST_F4=1).
-// The oracle they will be checked against is pinned already (oracle.ops.vector_quantize vs reference
-// outputs, tests/golden/vq_*.pt).
+// STATUS: on the public surface (pytorch_generative_amd/nn/utils.py: VectorQuantizer, mse_loss) and validated on
+// MI355X against outputs of the reference (tests/golden/vq_*.pt, tests/test_gpu_f4.py). pg_vq_assign here serves
+// embedding widths up to 64; wider codes take pg_vq_assign_tiled and the gradient-trained codebook takes
+// pg_vq_codebook_grad, both in vq_mfma.hip (tests/test_gpu_vq_codebook.py; tools/vq_bench.py times both assignments).
 //
 // Work shape: N*H*W positions x K codes x D dims of multiply-add with K*D <= 32768 and at most a few
 // 10^4 positions (8x8 .. 32x32 latent maps): HBM / launch bound byte work, not a GEMM worth the matrix

@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # HIP library, still loaded or the import fails; the default is the production library
 LIB_PATH = os.environ.get("PG_HIP_LIB") or os.path.join(_HERE, "lib", "libpg_hip.so")
 
-ABI_VERSION = 1
+ABI_VERSION = 2
 
 c_f = ctypes.c_void_p  # device float* (passed as integer address)
 c_i = ctypes.c_int
@@ -135,6 +135,9 @@ SIGNATURES = {
     "pg_vq_assign": (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_s]),
     "pg_vq_ema_update": (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, ctypes.c_float, c_s]),
     "pg_vq_bwd": (c_i, [c_f, c_f, c_f, c_f, c_f, c_z, c_s]),
+    "pg_vq_assign_tiled": (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_s]),
+    "pg_vq_codebook_grad_workspace_floats": (c_z, [c_i, c_i, c_i, c_i]),
+    "pg_vq_codebook_grad": (c_i, [c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_f, c_z, c_s]),
     "pg_mse_fwd": (c_i, [c_f, c_f, c_f, c_z, c_s]),
     "pg_mse_bwd": (c_i, [c_f, c_f, c_f, c_f, c_f, c_z, c_s]),
     "pg_bce_logits_fwd": (c_i, [c_f, c_f, c_f, c_i, c_z, c_s]),
