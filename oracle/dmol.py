@@ -60,14 +60,16 @@ def component_log_probs(x, means, log_scales, coeffs):
     inv_s = torch.exp(-log_scales)
     plus_in = inv_s * (centered + BIN)
     min_in = inv_s * (centered - BIN)
-    cdf_plus, cdf_min = torch.sigmoid(plus_in), torch.sigmoid(min_in)
     log_cdf_plus = plus_in - F.softplus(plus_in)          # log sigmoid: the value 0 takes everything below
     log_one_minus_cdf_min = -F.softplus(min_in)           # the value 255 takes everything above
-    cdf_delta = cdf_plus - cdf_min
+    # log of the bin mass sigmoid(plus_in) - sigmoid(min_in) without the difference (which cancels when the pixel is
+    # several scales ABOVE the mean and both sigmoids are near 1):
+    #   sigmoid(a) - sigmoid(b) = sigmoid(a) * sigmoid(-b) * (1 - exp(-(a - b))),   a - b = 2 h,  h = BIN / scale
+    two_h = 2.0 * BIN * inv_s
+    log_mass = -F.softplus(-plus_in) - F.softplus(min_in) + torch.log((-torch.expm1(-two_h)).clamp(min=MASS_FLOOR))
     mid_in = inv_s * centered
     log_pdf_mid = mid_in - log_scales - 2.0 * F.softplus(mid_in)
-    inner = torch.where(cdf_delta > MASS_SWITCH, torch.log(cdf_delta.clamp(min=MASS_FLOOR)),
-                        log_pdf_mid - math.log(127.5))
+    inner = torch.where(log_mass > math.log(MASS_SWITCH), log_mass, log_pdf_mid - math.log(127.5))
     return torch.where(xx < -0.999, log_cdf_plus, torch.where(xx > 0.999, log_one_minus_cdf_min, inner))
 
 

@@ -19,8 +19,7 @@ namespace {
 constexpr int DM_THREADS = 256;
 constexpr float LOG_SCALE_MIN = -7.0f;
 constexpr float BIN = 1.0f / 255.0f;
-constexpr float MASS_SWITCH = 1e-5f;
-constexpr float MASS_FLOOR = 1e-12f;
+constexpr float LOG_MASS_SWITCH = -11.512925465f;  // log 1e-5: below this bin mass, the density at the bin centre
 constexpr float LOG_127_5 = 4.8481163885f;
 
 __device__ __forceinline__ float softplusf_(float z) { return fmaxf(z, 0.f) + log1pf(expf(-fabsf(z))); }
@@ -43,12 +42,16 @@ __device__ __forceinline__ float subpixel(float x, float m, float s, float& dm, 
     ds = -nin * d;
     return -softplusf_(nin);
   }
-  const float cp = sigmoidf2_(pin), cm = sigmoidf2_(nin), delta = cp - cm;
-  if (delta > MASS_SWITCH) {
-    const float dp = cp * (1.f - cp) / delta, dn = -cm * (1.f - cm) / delta;  // d / d pin, d / d nin
+  // interior bin: log(sigmoid(pin) - sigmoid(nin)) WITHOUT the difference, which keeps only a few digits when the pixel
+  // lies several scales above the mean and both sigmoids are near 1 (relative loss error 6e-4 just before the fallback):
+  //   sigmoid(a) - sigmoid(b) = sigmoid(a) * sigmoid(-b) * (1 - exp(-(a - b))),   a - b = pin - nin = 2 h,  h = BIN / scale
+  const float two_h = 2.f * BIN * inv_s;
+  const float lmass = -softplusf_(-pin) - softplusf_(nin) + logf(-expm1f(-two_h));
+  if (lmass > LOG_MASS_SWITCH) {
+    const float dp = sigmoidf2_(-pin), dn = -sigmoidf2_(nin);  // d / d pin, d / d nin
     dm = -inv_s * (dp + dn);
-    ds = -(pin * dp + nin * dn);
-    return logf(fmaxf(delta, MASS_FLOOR));
+    ds = -(pin * dp + nin * dn) - two_h / expm1f(two_h);      // h depends on s too: d log(1 - e^{-2h}) / ds
+    return lmass;
   }
   const float d = 1.f - 2.f * sigmoidf2_(mid);  // log-density at the bin centre - log 127.5
   dm = -inv_s * d;
