@@ -610,6 +610,30 @@ int pg_dmol_fwd(const float* l, const float* x, float* loss, int N, int K, int L
 int pg_dmol_bwd(const float* l, const float* x, const float* gscale, float* dl, int N, int K, int L,
                 void* stream);
 
+/* One pixel's draw from the logistic mixture for all N images, in ONE launch (the per-pixel step of PixelCNN++'s row-cached
+ * sampler; the arithmetic of PixelCNNpp.sample_from_mixture followed by where(unknown, drawn, canvas)):
+ *   component = argmax_k (logit_k - log(-log u_k)), u clamped to [1e-5, 1 - 1e-5]; per sub-pixel a logistic variate
+ *   mean + exp(max(log_scale, -7)) * (log v - log1p(-v)); G and B shifted by tanh(coefficient) times the DRAWN R / G (also
+ *   where a given value is kept); each clamped to [-1, 1].
+ * params: the row's (N, 10 K, 1, W) parameters in the channel layout of pg_dmol_fwd, read at column c through its strides
+ * sp_n / sp_c / sp_w (in floats); uniforms (H * W, N, K + 3): K for the component, 3 for the sub-pixels, read at raster
+ * position p = r * W + c; canvas (N, 3, H, W) and its byte mask `unknown` (non-zero = draw): canvas[n, :, r, c] is
+ * replaced where unknown; row_buf (N, 3, 1, W) or NULL: receives canvas[n, :, r, c] as it stands after the draw.
+ * pos_dev (device int, or NULL): the raster position, as for pg_sample_embed (clamped to the image; r, c are then ignored
+ * but must still be valid). Any N >= 1; H, W multiples of 4; 1 <= K <= PG_DMOL_SAMPLE_MAX_K (PG_ESHAPE otherwise);
+ * PG_EINVAL for a null operand, a non-positive stride or a pixel outside the image. No device call before these checks. */
+#define PG_DMOL_SAMPLE_MAX_K 32
+int pg_dmol_sample(const float* params, long sp_n, long sp_c, long sp_w, const float* uniforms, float* canvas,
+                   const unsigned char* unknown, float* row_buf, int N, int K, int H, int W, int r, int c,
+                   const int* pos_dev, void* stream);
+
+/* Column resampling of `rows` dense rows (the strided levels of PixelCNN++ on ONE image row):
+ *   pg_col_subsample2:   y[row][q] = x[row][2 q], x rows of W floats (W even), y rows of W / 2
+ *   pg_col_zero_insert2: y[row][2 q] = x[row][q], y[row][2 q + 1] = 0, x rows of W floats, y rows of 2 W
+ * PG_ESHAPE for rows <= 0, W <= 0 or an odd W to sub-sample; PG_EINVAL for a null operand. */
+int pg_col_subsample2(const float* x, float* y, long rows, int W, void* stream);
+int pg_col_zero_insert2(const float* x, float* y, long rows, int W, void* stream);
+
 /* dst[r * dst_stride + i] (+)= src[r * src_stride + i] for r < rows, i < row_len (strides in floats).
  * The channel concatenation in front of a merged projection (nn/attention.py:139-143
  * torch.cat((x, extra_x), dim=1): a row = the channels of one image) and the assembly / gradient split

@@ -154,6 +154,79 @@ __global__ void __launch_bounds__(DM_THREADS) dmol_kernel(const DmArgs a) {
   }
 }
 
+
+// ---- one pixel's draw from the mixture (the sampler's per-pixel step; models/autoregressive/pixel_cnn_pp.py) -----------------
+// 32 lanes per image: lane k perturbs logit k with Gumbel noise, a 5-step butterfly picks the largest (ties: the smaller k, as
+// torch.argmax), then lane 0 of the group reads the chosen component's nine parameters and makes the three dependent draws.
+// Everything is a plain vector load / store; the per-image work is two dependent rounds of loads.
+constexpr int DS_GROUP = 32;                       // lanes per image = the largest K
+constexpr int DS_THREADS = 256;
+constexpr float DS_U_LO = (float)1e-5, DS_U_HI = (float)(1.0 - 1e-5);  // the clamp bounds as torch rounds them to fp32
+
+struct DsArgs {
+  const float* params; long sp_n, sp_c, sp_w;      // (N, 10 K, 1, W) row parameters, strides in floats
+  const float* uniforms;                           // (H * W, N, K + 3)
+  float* canvas; const unsigned char* unknown;     // (N, 3, H, W)
+  float* row_buf;                                  // (N, 3, 1, W) or NULL
+  const int* pos_dev;
+  int N, K, H, W, r, c;
+};
+
+__device__ __forceinline__ float ds_clamp_u(float u) { return fminf(fmaxf(u, DS_U_LO), DS_U_HI); }
+
+__global__ void __launch_bounds__(DS_THREADS) dmol_sample_kernel(const DsArgs a) {
+  const int gid = blockIdx.x * (DS_THREADS / DS_GROUP) + (threadIdx.x / DS_GROUP);
+  const int k = threadIdx.x & (DS_GROUP - 1);
+  const int n = min(gid, a.N - 1);                 // surplus groups redo the last image and store nothing
+  int r = a.r, c = a.c;
+  if (a.pos_dev) {                                 // raster position kept on the device: one captured graph serves every pixel
+    const int q = min(max(*a.pos_dev, 0), a.H * a.W - 1);
+    r = q / a.W;
+    c = q - r * a.W;
+  }
+  const int K = a.K;
+  const size_t p = (size_t)r * a.W + c;
+  const float* lp = a.params + (size_t)n * a.sp_n + (size_t)c * a.sp_w;
+  const float* up = a.uniforms + (p * a.N + n) * (size_t)(K + 3);
+  const int kc = min(k, K - 1);                    // lanes >= K load lane K-1's operands and are masked out of the argmax
+  const float logit = lp[(size_t)kc * a.sp_c];
+  const float u = ds_clamp_u(up[kc]);
+  float best = k < K ? logit - logf(-logf(u)) : -INFINITY;
+  int sel = k < K ? k : K;
+#pragma unroll
+  for (int off = DS_GROUP / 2; off > 0; off >>= 1) {
+    const float ob = __shfl_xor(best, off, 64);
+    const int os = __shfl_xor(sel, off, 64);
+    const bool take = ob > best || (ob == best && os < sel);
+    best = take ? ob : best;
+    sel = take ? os : sel;
+  }
+  sel = min(sel, K - 1);                           // (all NaN logits: still a valid address)
+  if (k != 0 || gid >= a.N) return;
+  // channel of (sub-pixel j, field f, component sel): K + j * 3K + f * K + sel, as in the loss
+  auto at = [&](int j, int f) { return lp[(size_t)(K + j * 3 * K + f * K + sel) * a.sp_c]; };
+  const float m0 = at(0, 0), m1 = at(1, 0), m2 = at(2, 0);
+  const float s0 = fmaxf(at(0, 1), LOG_SCALE_MIN), s1 = fmaxf(at(1, 1), LOG_SCALE_MIN), s2 = fmaxf(at(2, 1), LOG_SCALE_MIN);
+  const float c0 = tanhf(at(0, 2)), c1 = tanhf(at(1, 2)), c2 = tanhf(at(2, 2));
+  const float v0 = ds_clamp_u(up[K]), v1 = ds_clamp_u(up[K + 1]), v2 = ds_clamp_u(up[K + 2]);
+  const float y0 = m0 + expf(s0) * (logf(v0) - log1pf(-v0));
+  const float y1 = m1 + expf(s1) * (logf(v1) - log1pf(-v1));
+  const float y2 = m2 + expf(s2) * (logf(v2) - log1pf(-v2));
+  const float x0 = fminf(fmaxf(y0, -1.f), 1.f);
+  const float x1 = fminf(fmaxf(y1 + c0 * x0, -1.f), 1.f);
+  const float x2 = fminf(fmaxf(y2 + c1 * x0 + c2 * x1, -1.f), 1.f);  // G and B follow the DRAWN R / G, also where a given one is kept
+  const size_t plane = (size_t)a.H * a.W;
+  const size_t ci = (size_t)n * 3 * plane + p;
+  const float xs[3] = {x0, x1, x2};
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    float val = xs[j];
+    if (a.unknown[ci + j * plane]) a.canvas[ci + j * plane] = val;
+    else val = a.canvas[ci + j * plane];
+    if (a.row_buf) a.row_buf[((size_t)n * 3 + j) * a.W + c] = val;
+  }
+}
+
 int dm_check(const char* who, int N, int K, int L) {
   PG_REQUIRE(N > 0 && L > 0, PG_EINVAL, "%s: non-positive dimension", who);
   PG_REQUIRE(K >= 1 && K <= 16, PG_ESHAPE, "%s: %d mixture components not in [1, 16]", who, K);
@@ -184,5 +257,25 @@ PG_EXPORT int pg_dmol_bwd(const float* l, const float* x, const float* gscale, f
   if (blocks > 4096) blocks = 4096;
   hipLaunchKernelGGL(dmol_kernel<true>, dim3((unsigned)blocks), dim3(DM_THREADS), 0, (hipStream_t)stream, a);
   PG_LAUNCH_CHECK("pg_dmol_bwd");
+  return 0;
+}
+
+PG_EXPORT int pg_dmol_sample(const float* params, long sp_n, long sp_c, long sp_w, const float* uniforms, float* canvas,
+                             const unsigned char* unknown, float* row_buf, int N, int K, int H, int W, int r, int c,
+                             const int* pos_dev, void* stream) {
+  PG_REQUIRE(N > 0 && K > 0 && H > 0 && W > 0, PG_ESHAPE, "pg_dmol_sample: non-positive dimension");
+  PG_REQUIRE(H % 4 == 0 && W % 4 == 0, PG_ESHAPE, "pg_dmol_sample: H, W (%d, %d) must be multiples of 4", H, W);
+  PG_REQUIRE(K <= PG_DMOL_SAMPLE_MAX_K, PG_ESHAPE, "pg_dmol_sample: %d mixture components > %d", K, PG_DMOL_SAMPLE_MAX_K);
+  PG_REQUIRE(params && uniforms && canvas && unknown, PG_EINVAL, "pg_dmol_sample: null pointer");
+  PG_REQUIRE(sp_n > 0 && sp_c > 0 && sp_w > 0, PG_EINVAL, "pg_dmol_sample: bad parameter strides");
+  PG_REQUIRE(r >= 0 && r < H && c >= 0 && c < W, PG_EINVAL, "pg_dmol_sample: pixel outside the image");
+  static_assert(PG_DMOL_SAMPLE_MAX_K == DS_GROUP, "one lane per mixture component");
+  DsArgs a = {};
+  a.params = params; a.sp_n = sp_n; a.sp_c = sp_c; a.sp_w = sp_w; a.uniforms = uniforms; a.canvas = canvas;
+  a.unknown = unknown; a.row_buf = row_buf; a.pos_dev = pos_dev; a.N = N; a.K = K; a.H = H; a.W = W; a.r = r; a.c = c;
+  const int per_block = DS_THREADS / DS_GROUP;
+  hipLaunchKernelGGL(dmol_sample_kernel, dim3((unsigned)((N + per_block - 1) / per_block)), dim3(DS_THREADS), 0,
+                     (hipStream_t)stream, a);
+  PG_LAUNCH_CHECK("pg_dmol_sample");
   return 0;
 }

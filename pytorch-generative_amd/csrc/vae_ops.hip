@@ -79,6 +79,24 @@ __global__ void phase_split_kernel(float* x, float* xs, size_t total,
   }
 }
 
+// ---- column resampling of single rows (PixelCNN++'s row-cached sampler): y[row][q] = x[row][2q], and its adjoint
+// y[row][2q] = x[row][q], y[row][2q + 1] = 0. W = the width of the NARROW side.
+__global__ void col_resample2_kernel(const float* __restrict__ x, float* __restrict__ y, size_t total, int W, int up) {
+  const size_t stride = (size_t)gridDim.x * blockDim.x;  // total = elements of y
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
+    if (up) {
+      const size_t row = i / (2 * (size_t)W);
+      const int c2 = (int)(i - row * 2 * W);
+      const float v = x[row * W + (c2 >> 1)];
+      y[i] = (c2 & 1) ? 0.f : v;
+    } else {
+      const size_t row = i / (size_t)W;
+      const int q = (int)(i - row * W);
+      y[i] = x[row * 2 * W + 2 * q];
+    }
+  }
+}
+
 struct Phase4 { float* p[4]; };
 
 __global__ void phase_merge4_kernel(float* x, const Phase4 ph, size_t total, int H, int W, int merge) {
@@ -282,6 +300,24 @@ PG_EXPORT int pg_phase_merge4(float* x, float* const* p, int planes, int H, int 
   const size_t total = (size_t)planes * 4 * H * W;
   hipLaunchKernelGGL(phase_merge4_kernel, dim3(vblocks(total)), dim3(VT), 0, VST, x, ph, total, H, W, merge);
   PG_LAUNCH_CHECK("pg_phase_merge4");
+  return 0;
+}
+
+PG_EXPORT int pg_col_subsample2(const float* x, float* y, long rows, int W, void* stream) {
+  PG_REQUIRE(rows > 0 && W > 0 && W % 2 == 0, PG_ESHAPE, "pg_col_subsample2: rows > 0 and an even W > 0 expected");
+  PG_REQUIRE(x && y, PG_EINVAL, "pg_col_subsample2: null pointer");
+  const size_t total = (size_t)rows * (W / 2);
+  hipLaunchKernelGGL(col_resample2_kernel, dim3(vblocks(total)), dim3(VT), 0, VST, x, y, total, W / 2, 0);
+  PG_LAUNCH_CHECK("pg_col_subsample2");
+  return 0;
+}
+
+PG_EXPORT int pg_col_zero_insert2(const float* x, float* y, long rows, int W, void* stream) {
+  PG_REQUIRE(rows > 0 && W > 0 && W < (1 << 30), PG_ESHAPE, "pg_col_zero_insert2: rows > 0 and 0 < W < 2^30 expected");
+  PG_REQUIRE(x && y, PG_EINVAL, "pg_col_zero_insert2: null pointer");
+  const size_t total = (size_t)rows * 2 * W;
+  hipLaunchKernelGGL(col_resample2_kernel, dim3(vblocks(total)), dim3(VT), 0, VST, x, y, total, W, 1);
+  PG_LAUNCH_CHECK("pg_col_zero_insert2");
   return 0;
 }
 

@@ -163,6 +163,9 @@ SIGNATURES = {
     "pg_concat_elu_bwd": (c_i, [c_f, c_f, c_f, c_i, c_l, c_s]),
     "pg_dmol_fwd": (c_i, [c_f, c_f, c_f, c_i, c_i, c_i, c_s]),
     "pg_dmol_bwd": (c_i, [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_s]),
+    "pg_dmol_sample": (c_i, [c_f, c_l, c_l, c_l, c_f, c_f, c_f, c_f] + [c_i] * 6 + [c_f, c_s]),
+    "pg_col_subsample2": (c_i, [c_f, c_f, c_l, c_i, c_s]),
+    "pg_col_zero_insert2": (c_i, [c_f, c_f, c_l, c_i, c_s]),
     "pg_copy_rows": (c_i, [c_f, c_f, c_l, c_l, c_l, c_l, c_i, c_s]),
     "pg_comm_unique_id": (c_i, [ctypes.c_char_p]),
     "pg_comm_init": (c_i, [c_i, c_i, ctypes.c_char_p]),

@@ -22,6 +22,7 @@ How the pieces map onto this package's kernels:
 import torch
 from torch import nn
 
+from pytorch_generative_amd import _lib
 from pytorch_generative_amd import nn as pg_nn
 from pytorch_generative_amd import ops
 from pytorch_generative_amd.models import base
@@ -65,12 +66,25 @@ class GatedResnet(nn.Module):
         return self._gate(c2, res=x_res)
 
 
+def row_schedule(h):
+    """Which resolution level is evaluated at which image row, for row-by-row evaluation of the three-level network:
+    entry y is the tuple of (level, row of that level) pairs of image row y, finest level first. Level s (H / 2**s rows)
+    is evaluated at image row y iff y % 2**s == 0, on its row y >> s: row r of a sub-sampled down convolution is row 2r
+    of the stride-1 convolution (reading fine rows 2r - 1 and 2r), and row r of an up convolution reads rows r - 1 and r
+    of the zero-inserted tensor, whose even rows 2q are coarse row q and whose odd rows are zeros."""
+    h = int(h)
+    if h <= 0 or h % 4:
+        raise ValueError("row_schedule: H must be a positive multiple of 4 (two stride-2 levels)")
+    return [tuple((s, y >> s) for s in range(3) if y % (1 << s) == 0) for y in range(h)]
+
+
 class PixelCNNpp(base.AutoregressiveModel):
     """forward(x) -> (N, 10 * n_mix, H, W) mixture parameters for images x in [-1, 1] with 3 channels
     (H, W multiples of 4). Paper configuration: n_filters=160, n_resnet=5, n_mix=10."""
 
     def __init__(self, in_channels=3, n_filters=160, n_resnet=5, n_mix=10, sample_fn=None):
         super().__init__(sample_fn)
+        self._pixel_sample_fn = sample_fn  # None: the mixture draw (ops.dmol_sample); else fn(params (N, 10 K)) -> (N, 3)
         if in_channels != 3:
             raise ValueError("PixelCNNpp: the discretized logistic mixture conditions R, G, B sub-pixels (3 channels)")
         f, cin = n_filters, in_channels + 1  # + a channel of ones (so that the shifted convolutions see the border)
@@ -131,6 +145,69 @@ class PixelCNNpp(base.AutoregressiveModel):
         assert not u and not ul
         return self._out(hul, in_act="elu")
 
+    # ---- row-cached incremental sampling -----------------------------------------------------------------------------
+    def _row_const(self, key, shape, value, device):
+        """A constant (ones channel, rows of zeros) of the row step, filled once by the library's own kernel and never written."""
+        cache = self.__dict__.setdefault("_row_consts", {})
+        k = (key, tuple(shape), str(device))
+        if k not in cache:
+            t = torch.empty(shape, device=device, dtype=torch.float32)
+            _lib.check(_lib.load().pg_fill(t.data_ptr(), float(value), t.numel(), ops._stream()), "pg_fill")
+            cache[k] = t
+        return cache[k]
+
+    def _row_net(self, ctx, row_in):
+        """_net on ONE image row under ops.RowDecode: row_in (N, 3, 1, W) is row ctx.row of an image in [-1, 1]; returns
+        the (N, 10 K, 1, W) parameters of that row. The network is row-causal level by level (row_schedule): every
+        convolution is a stride-1 shifted convolution with kh <= 2 whose band of earlier input rows nn.Conv2d keeps;
+        sub-sampling keeps the even columns of the rows that survive it, zero insertion feeds a column-stuffed row at
+        even rows of the finer level and a row of zeros at odd ones. Layers of a level that is not evaluated at this
+        row are not called, so their bands do not move; a down convolution whose output row is dropped (odd rows of its
+        input level) is called in the commit pass only, to push its band."""
+        y = ctx.row
+        deepest = row_schedule(ctx.height)[y][-1][0]
+        n, _, _, w = row_in.shape
+        dev = row_in.device
+        xp = ops.concat_channels([row_in, self._row_const("ones", (n, 1, 1, w), 1.0, dev)])
+        u_cur = self._u_in(xp)
+        ul_cur = self._ul_in_b(xp, res=self._ul_in_a(xp))
+        us, uls = [[u_cur]], [[ul_cur]]  # the short-cut stacks, one per evaluated level
+        for s in range(deepest + 1):  # up pass
+            for ru, rul in zip(self._up_u[s], self._up_ul[s]):
+                u_cur = ru(u_cur)
+                ul_cur = rul(ul_cur, aux=u_cur)
+                us[s].append(u_cur)
+                uls[s].append(ul_cur)
+            if s < 2:
+                used = s < deepest  # row y >> s of level s is even: it survives the sub-sampling
+                if used or ctx.commit:
+                    du, dul = self._down_u_conv[s](u_cur), self._down_ul_conv[s](ul_cur)
+                if used:
+                    u_cur, ul_cur = ops.col_subsample2(du), ops.col_subsample2(dul)
+                    us.append([u_cur])
+                    uls.append([ul_cur])
+        hu = hul = None
+        for s in range(3):  # down pass; _dn_*[s] live at level 2 - s
+            lvl = 2 - s
+            if lvl > deepest:
+                continue
+            if lvl == 2:
+                hu, hul = us[2].pop(), uls[2].pop()
+            else:
+                if lvl < deepest:  # the coarser level was evaluated at this row: its row, zeros between the columns
+                    zu, zul = ops.col_zero_insert2(hu), ops.col_zero_insert2(hul)
+                else:              # an odd row of the zero-inserted tensor
+                    zu = zul = self._row_const("zeros", (n, self._up_u_conv[s - 1].in_channels, 1, w >> lvl), 0.0, dev)
+                hu, hul = self._up_u_conv[s - 1](zu), self._up_ul_conv[s - 1](zul)
+            for ru, rul in zip(self._dn_u[s], self._dn_ul[s]):
+                hu = ru(hu, aux=us[lvl].pop())
+                hul = rul(hul, aux=ops.concat_channels([hu, uls[lvl].pop()]))
+            assert not us[lvl] and not uls[lvl]
+        return self._out(hul, in_act="elu")
+
+    def _row_reset(self):
+        self._row_consts = {}
+
     @staticmethod
     def sample_from_mixture(params, n_mix):
         """One draw per image from the discretized logistic mixture at ONE pixel: params (N, 10 K) in the channel
@@ -154,13 +231,33 @@ class PixelCNNpp(base.AutoregressiveModel):
         x2 = (x[:, 2] + coeffs[:, 1] * x0 + coeffs[:, 2] * x1).clamp(-1.0, 1.0)
         return torch.stack((x0, x1, x2), dim=1)
 
+    # Below this batch size sample() takes the full-forward procedure even when incremental=True (the rule of
+    # base.AutoregressiveModel._row_decode_min_batch). The comparison that would set it is NOT YET MEASURED: one MI355X run
+    # (profiles/pixelcnnpp_sampling.json) has the row-cached call at the paper configuration, 32 x 32, at 10.2 / 10.4 / 11.8 s
+    # for n = 1 / 16 / 64, but no whole-call figure of the full-forward sampler to hold against it
+    # (tools/pixelcnnpp_sample_bench.py measures both). Until it exists every batch size takes the row-cached path.
+    _incremental_min_batch = 1
+    _row_graph = True  # capture the row steps into hipGraphs (False: launch them eagerly; tools/pixelcnnpp_sample_bench.py)
+
     @torch.no_grad()
-    def sample(self, n_samples=None, conditioned_on=None, *, image_size=None):
-        """Raster-order sampling as base.AutoregressiveModel.sample (reference models/base.py:97-120: one full
-        forward per pixel, only the unknown entries replaced), with the draw made from the logistic mixture.
-        Images live in [-1, 1]; entries of `conditioned_on` below -1 are the unknown ones. `image_size` (H, W)
-        is needed when the model has not seen a batch yet. (The strided levels make the network non-row-causal
-        for ops.RowDecode: full forwards only.)"""
+    def sample(self, n_samples=None, conditioned_on=None, *, image_size=None, incremental=True, return_params=False):
+        """Raster-order sampling as base.AutoregressiveModel.sample (reference models/base.py:97-120: only the unknown
+        entries replaced), with the draw made from the logistic mixture. Images live in [-1, 1]; entries of
+        `conditioned_on` below -1 are the unknown ones. `image_size` (H, W) is needed when the model has not seen a
+        batch yet.
+
+        incremental=True (extension): the network is evaluated on the CURRENT ROW only (_row_net: the levels due at that
+        row, against the convolutions' band caches) and a pixel is drawn by one kernel (ops.dmol_sample) from uniforms
+        drawn up front by ONE torch.rand of shape (H * W, N, K + 3); the row step is captured into at most three step
+        and three commit hipGraphs (rows with y % 4 == 0, y % 4 == 2, odd y) and replayed, eagerly launched when capture
+        is refused. Pixels at which no image has an unknown entry are skipped; a row without any runs its commit pass only.
+        incremental=False: one full forward per pixel and sample_from_mixture (the reference procedure).
+        return_params=True (incremental only): every pixel is evaluated and the call returns (canvas, params), params
+        the (N, 10 K, H, W) mixture parameters the draws were made from.
+        A `sample_fn` given to the constructor replaces the mixture draw on the incremental path:
+        sample_fn(params (N, 10 K)) -> (N, 3), called eagerly once per pixel."""
+        if return_params and not incremental:
+            raise ValueError("return_params requires incremental=True")
         if conditioned_on is not None:
             canvas = conditioned_on.clone()
         else:
@@ -170,6 +267,8 @@ class PixelCNNpp(base.AutoregressiveModel):
         n, _, h, w = canvas.shape
         unknown = canvas < -1.0
         canvas = torch.where(unknown, torch.zeros_like(canvas), canvas)  # any finite value: later pixels are never read
+        if incremental and (n >= self._incremental_min_batch or return_params):
+            return self._sample_rows(canvas, unknown, return_params)
         for row in range(h):
             for col in range(w):
                 if not bool(unknown[:, :, row, col].any()):
@@ -178,6 +277,101 @@ class PixelCNNpp(base.AutoregressiveModel):
                 drawn = self.sample_from_mixture(params, self._n_mix)
                 canvas[:, :, row, col] = torch.where(unknown[:, :, row, col], drawn, canvas[:, :, row, col])
         return canvas
+
+    def _sample_rows(self, canvas, unknown, return_params):
+        n, _, h, w = canvas.shape
+        if h % 4 or w % 4:
+            raise ValueError("PixelCNNpp: H and W must be multiples of 4 (two stride-2 levels)")
+        k, dev = self._n_mix, canvas.device
+        fn = self._pixel_sample_fn
+        canvas, unknown = canvas.contiguous(), unknown.contiguous()
+        wanted = unknown.any(dim=0).any(dim=0).cpu()  # (H, W): the ONE host sync of the call
+        wanted = [[True] * w for _ in range(h)] if return_params else wanted.tolist()
+        uniforms = torch.rand((h * w, n, k + 3), device=dev) if fn is None else None
+        params_map = torch.zeros((n, 10 * k, h, w), device=dev) if return_params else None
+        row_in = torch.zeros((n, 3, 1, w), device=dev)
+        pos_dev = torch.zeros(1, dtype=torch.int32, device=dev)  # the raster position the captured draw reads
+
+        def reset():
+            for m in self.modules():
+                if hasattr(m, "_row_reset"):
+                    m._row_reset()
+
+        def step(ctx, target, host_pos=None):
+            """The parameters of row ctx.row and (without a sample_fn) the draw of one pixel of `target` from them"""
+            out = self._row_net(ctx, row_in)
+            if fn is None and not ctx.commit:
+                r, c = host_pos if host_pos is not None else (0, 0)
+                ops.dmol_sample(out, uniforms, target, unknown, k, r, c, row_buf=row_in if target is canvas else None,
+                                pos_dev=pos_dev if host_pos is None else None)
+            return out
+
+        reset()
+        with ops.RowDecode(h) as ctx:
+            # The row step differs only by which levels are due: three row classes, each captured ONCE into a step graph
+            # (row forward + the draw at pos_dev) and a commit graph (the pattern of base.AutoregressiveModel.sample).
+            class_rows = {2: 0, 1: 2, 0: 1}  # deepest level evaluated -> a row of that class
+            graphs = None
+            if self._row_graph:
+                try:
+                    side = torch.cuda.Stream()
+                    side.wait_stream(torch.cuda.current_stream())
+                    scratch = canvas.clone()  # the warm-up's draws land here
+                    with torch.cuda.stream(side):  # warm-up: allocates every band buffer and constant
+                        for r0 in class_rows.values():
+                            ctx.row, ctx.commit = r0, False
+                            step(ctx, scratch)
+                            ctx.commit = True
+                            step(ctx, scratch)
+                    torch.cuda.current_stream().wait_stream(side)
+                    graphs = {}
+                    for cls, r0 in class_rows.items():
+                        sg, cg = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
+                        ctx.row, ctx.commit = r0, False
+                        with torch.cuda.graph(sg, capture_error_mode="thread_local"):
+                            out = step(ctx, canvas)
+                        ctx.commit = True
+                        with torch.cuda.graph(cg, capture_error_mode="thread_local"):
+                            step(ctx, canvas)
+                        graphs[cls] = (sg, cg, out)
+                    for m in self.modules():  # the warm-up pushed rows of zeros: start clean
+                        band = getattr(m, "_row_band", None)
+                        if band is not None:
+                            band.zero_()
+                except Exception as e:  # noqa: BLE001 — capture is an optimisation only
+                    import os
+                    if os.environ.get("PG_DEBUG"):
+                        print(f"[sample] row-step capture failed: {type(e).__name__}: {e}")
+                    graphs = None
+                    torch.cuda.synchronize()
+                    reset()
+            schedule = row_schedule(h)
+            for row in range(h):
+                cls = schedule[row][-1][0]
+                ctx.row, ctx.commit = row, False
+                row_in.copy_(canvas[:, :, row:row + 1, :])
+                for col in range(w):
+                    if not wanted[row][col]:
+                        continue
+                    if graphs is not None:
+                        pos_dev.fill_(row * w + col)
+                        graphs[cls][0].replay()
+                        out = graphs[cls][2]
+                    else:
+                        out = step(ctx, canvas, (row, col))
+                    if return_params:
+                        params_map[:, :, row, col] = out[:, :, 0, col]
+                    if fn is not None:
+                        drawn = fn(out[:, :, 0, col]).view(n, 3).to(canvas.dtype)
+                        canvas[:, :, row, col] = torch.where(unknown[:, :, row, col], drawn, canvas[:, :, row, col])
+                        row_in[:, :, 0, col] = canvas[:, :, row, col]
+                ctx.commit = True  # the row is final: push it into every band (row_in already holds it)
+                if graphs is not None:
+                    graphs[cls][1].replay()
+                else:
+                    step(ctx, canvas)
+        reset()
+        return (canvas, params_map) if return_params else canvas
 
 
 class PixelCNNppUnitRange(PixelCNNpp):
@@ -190,11 +384,14 @@ class PixelCNNppUnitRange(PixelCNNpp):
         return self._net(x * 2.0 - 1.0)
 
     @torch.no_grad()
-    def sample(self, n_samples=None, conditioned_on=None, *, image_size=None):
+    def sample(self, n_samples=None, conditioned_on=None, *, image_size=None, incremental=True, return_params=False):
         if conditioned_on is not None:
             conditioned_on = torch.where(conditioned_on < 0, torch.full_like(conditioned_on, -2.0),
                                          conditioned_on * 2.0 - 1.0)
-        out = super().sample(n_samples, conditioned_on, image_size=image_size)
+        out = super().sample(n_samples, conditioned_on, image_size=image_size, incremental=incremental,
+                             return_params=return_params)
+        if return_params:
+            return (out[0] + 1.0) * 0.5, out[1]
         return (out + 1.0) * 0.5
 
 

@@ -136,6 +136,8 @@ from pytorch_generative_amd.ops.losses import (  # noqa: F401
     _BCEWithLogitsSumMean,
     _DmolLossSumMean,
     dmol_loss_sum_mean,
+    DMOL_SAMPLE_MAX_K,
+    dmol_sample,
     bce_with_logits_sum_mean,
     _ElboMean,
     elbo_terms,
@@ -166,4 +168,6 @@ from pytorch_generative_amd.ops.vae import (  # noqa: F401
     _Resample2,
     subsample2,
     zero_insert2,
+    col_subsample2,
+    col_zero_insert2,
 )

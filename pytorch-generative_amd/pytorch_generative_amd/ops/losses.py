@@ -74,6 +74,49 @@ def dmol_loss_sum_mean(params, images, n_mix=10):
     return _DmolLossSumMean.apply(params, images, int(n_mix))
 
 
+DMOL_SAMPLE_MAX_K = 32  # include/pg_hip.h PG_DMOL_SAMPLE_MAX_K
+
+
+def dmol_sample(params, uniforms, canvas, unknown, n_mix, row=0, col=0, *, row_buf=None, pos_dev=None):
+    """Draws pixel (row, col) of every image from its logistic mixture, in one launch (pg_dmol_sample): the arithmetic of
+    PixelCNNpp.sample_from_mixture followed by where(unknown, drawn, canvas), in place.
+
+    params (N, 10 * n_mix, 1, W): the mixture parameters of image row `row` (any strides; column `col` is read);
+    uniforms (H * W, N, n_mix + 3) in [0, 1): raster position row * W + col is read; canvas (N, 3, H, W) float32 and
+    unknown (N, 3, H, W) bool, both contiguous: canvas[:, :, row, col] is replaced where unknown; row_buf (N, 3, 1, W),
+    optional: receives canvas[:, :, row, col] as it stands afterwards. pos_dev (int32 device scalar, optional): the
+    raster position is read from it instead of (row, col), so that one captured graph serves every pixel.
+    Sampling only: no gradient is defined."""
+    lib = _lib.load()
+    n, c, one, w = params.shape
+    h = canvas.shape[2]
+    k = int(n_mix)
+    if c != 10 * k or one != 1 or tuple(canvas.shape) != (n, 3, h, w) or tuple(unknown.shape) != (n, 3, h, w):
+        raise ValueError("dmol_sample: expected (N, 10 * n_mix, 1, W) parameters, an (N, 3, H, W) canvas and its mask")
+    if tuple(uniforms.shape) != (h * w, n, k + 3):
+        raise ValueError(f"dmol_sample: uniforms {tuple(uniforms.shape)} != {(h * w, n, k + 3)}")
+    for t, name in ((params, "params"), (uniforms, "uniforms"), (canvas, "canvas")) + (
+            ((row_buf, "row_buf"),) if row_buf is not None else ()):
+        if not t.is_cuda or t.dtype != torch.float32 or t.device != canvas.device:
+            raise RuntimeError(f"dmol_sample.{name}: expected a float32 tensor on the canvas's MI355X (cuda) device")
+    if canvas.device.index != torch.cuda.current_device():
+        raise RuntimeError("dmol_sample: the canvas does not live on the current device")
+    if unknown.dtype != torch.bool or unknown.device != canvas.device:
+        raise TypeError("dmol_sample.unknown: expected a bool tensor on the canvas's device")
+    if not (uniforms.is_contiguous() and canvas.is_contiguous() and unknown.is_contiguous()):
+        raise ValueError("dmol_sample: uniforms, canvas and unknown must be contiguous (they are updated / indexed in place)")
+    if row_buf is not None and (tuple(row_buf.shape) != (n, 3, 1, w) or not row_buf.is_contiguous()):
+        raise ValueError("dmol_sample: row_buf must be a contiguous (N, 3, 1, W) tensor")
+    if pos_dev is not None and (pos_dev.dtype != torch.int32 or pos_dev.numel() != 1 or pos_dev.device != canvas.device):
+        raise TypeError("dmol_sample.pos_dev: expected one int32 on the canvas's device")
+    sn, sc, _, sw = params.stride()
+    _lib.check(lib.pg_dmol_sample(params.data_ptr(), sn, sc, sw, uniforms.data_ptr(), canvas.data_ptr(),
+                                  unknown.data_ptr(), None if row_buf is None else row_buf.data_ptr(), n, k, h, w,
+                                  int(row), int(col), None if pos_dev is None else pos_dev.data_ptr(), _stream()),
+               "pg_dmol_sample")
+    return canvas
+
+
 def bce_with_logits_sum_mean(logits, targets):
     """F.binary_cross_entropy_with_logits(reduction='none').sum(pixels).mean(batch)
     (reference image_gpt.py:158-162 and every other AR reproduce())."""

@@ -460,3 +460,33 @@ def subsample2(x):
 
 def zero_insert2(x):
     return _Resample2.apply(x, True)
+
+
+def _col_resample2(x, up):
+    lib = _lib.load()
+    x = _chk(x, "col_resample2.x")
+    n, c, h, w = x.shape
+    if up:
+        y = torch.empty((n, c, h, 2 * w), device=x.device, dtype=torch.float32)
+        _lib.check(lib.pg_col_zero_insert2(x.data_ptr(), y.data_ptr(), n * c * h, w, _stream()), "pg_col_zero_insert2")
+        return y
+    if w % 2:
+        raise ValueError("col_subsample2: W must be even")
+    y = torch.empty((n, c, h, w // 2), device=x.device, dtype=torch.float32)
+    _lib.check(lib.pg_col_subsample2(x.data_ptr(), y.data_ptr(), n * c * h, w, _stream()), "pg_col_subsample2")
+    return y
+
+
+def col_subsample2(x):
+    """x[..., ::2] of an (N, C, 1, W) row (what subsample2 does to ONE image row that survives it). Sampling only: the
+    row-cached sampler runs under no_grad and no gradient is defined."""
+    if torch.is_grad_enabled() and x.requires_grad:
+        raise RuntimeError("col_subsample2: no gradient is defined (row-cached sampling only)")
+    return _col_resample2(x, False)
+
+
+def col_zero_insert2(x):
+    """The adjoint of col_subsample2: y[..., ::2] = x, zeros between (an even row of zero_insert2's output). Sampling only."""
+    if torch.is_grad_enabled() and x.requires_grad:
+        raise RuntimeError("col_zero_insert2: no gradient is defined (row-cached sampling only)")
+    return _col_resample2(x, True)
