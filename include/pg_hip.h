@@ -662,6 +662,37 @@ int pg_allreduce_sum(void* buf, size_t n, int dtype, void* stream);
 int pg_broadcast(void* buf, size_t n, int dtype, int root, void* stream);
 int pg_comm_destroy(void);
 
+/* ---------------------------------------------------------------------------------------
+ * ImageGPT's two ends (models/autoregressive/image_gpt.py: the first and the last line of forward), gpt_ends.hip.
+ * fp32; C = 16 embedding channels; 1 <= Cout <= 4. grid_cap: upper bound on the workgroups of the launch, 0 = the
+ * library's default (persistent workgroups walk the tiles). Reductions are deterministic: the backward kernels leave
+ * partial rows in `workspace`, pg_gpt_model_reduce adds them (to what the destinations hold).
+ *
+ * stem: x0 (N,16,H*W) = CausalConv2d type A 3x3, padding 1, of img (N,1,H,W) + pos (1,1,H,W); zero padding applies to the
+ * sum. The forward also zeroes the masked entries of `weight` (16,1,3,3) in place (taps 4..8 of every output channel), which
+ * it never reads. The backward leaves d weight for all nine taps, d bias and the position-wise sums d pos is gathered from;
+ * its workspace holds pg_gpt_stem_bwd_workspace_floats floats, laid out for the rows / slices of pg_gpt_stem_bwd_plan.
+ * head: logits (N,Cout,L) = Conv1x1(LayerNorm over channels of x (N,16,L)), LayerNorm as in the block kernels (biased
+ * variance, eps inside the root). The backward writes dx and pg_gpt_out_head_bwd_rows rows of 32 + 17 Cout floats. */
+int pg_gpt_stem_fwd(const float* img, const float* pos, float* weight, const float* bias, float* x0, int N, int H, int W,
+                    int grid_cap, void* stream);
+int pg_gpt_stem_bwd_plan(int N, int H, int W, int grid_cap, int* rows, int* slices);
+size_t pg_gpt_stem_bwd_workspace_floats(int N, int H, int W, int grid_cap);
+int pg_gpt_stem_bwd(const float* dx0, const float* img, const float* pos, const float* weight, int N, int H, int W,
+                    int grid_cap, float* workspace, size_t workspace_floats, void* stream);
+int pg_gpt_out_head_fwd(const float* x, const float* ln_w, const float* ln_b, const float* conv_w, const float* conv_b,
+                        float* logits, int N, int C, int Cout, int L, float eps, int grid_cap, void* stream);
+int pg_gpt_out_head_bwd_rows(int N, int L, int grid_cap);
+int pg_gpt_out_head_bwd(const float* x, const float* ln_w, const float* ln_b, const float* conv_w, const float* dlogits,
+                        float* dx, int N, int C, int Cout, int L, float eps, int grid_cap, float* workspace,
+                        size_t workspace_floats, void* stream);
+/* pg_gpt_blocks_reduce (n_blocks 0..8, same arguments) and both ends in ONE launch. out_ws / stem_ws may be null (that end is
+ * left out). out_grads: d ln.weight, d ln.bias, d conv.weight, d conv.bias; stem_grads: d weight, d bias, d pos. */
+int pg_gpt_model_reduce(int n_blocks, const float* const* head_ws, const float* const* tail_ws, float* const* grads, int N,
+                        int C, int L, const float* out_ws, int out_rows, int Cout, float* const* out_grads,
+                        const float* stem_ws, int stem_rows, int stem_slices, int H, int W, float* const* stem_grads,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,6 +24,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "gpt_ends.h"
 
 namespace {
 
@@ -670,6 +671,57 @@ __global__ void __launch_bounds__(256) seg_reduceN_kernel(const SegArgsN an) {
   }
 }
 
+// The whole model's reductions in ONE launch: the rows of up to 8 blocks (16 jobs) and of the two ends (gpt_ends.hip): the output
+// head's rows, the stem's d weight / d bias rows, and the stem's d pos — the one job that is not a plain column sum: column q
+// gathers the position-wise sums G[tap][q - off(tap)] of the four active taps (gpt_ends.h, region B).
+constexpr int SEGM_MAX_JOBS = SEG_MAX_JOBS + 3;
+struct SegArgsM { SegArgs j[SEGM_MAX_JOBS]; int first[SEGM_MAX_JOBS + 1]; int n, pos_job, H, W; };
+__global__ void __launch_bounds__(256) seg_reduceM_kernel(const SegArgsM an) {
+  __shared__ float red[32][9];
+  int job = 0;
+  while (job + 1 < an.n && (int)blockIdx.x >= an.first[job + 1]) ++job;
+  const SegArgs& a = an.j[job];
+  const int blk = blockIdx.x - an.first[job];
+  const int sl = threadIdx.x & 7, rg = threadIdx.x >> 3;
+  const int s = blk * 8 + sl;
+  const int ncol = a.end[a.nseg - 1];  // columns this job writes
+  int col[4] = {s, -1, -1, -1};
+  if (job == an.pos_job && s < ncol) {
+    // forward: x0[.., (r, c)] += w[.., tap] in(r + dr, c + dc), (dr, dc) = (-1,-1) (-1,0) (-1,1) (0,-1); so d pos[(r, c)]
+    // takes G[tap] at (r - dr, c - dc) where that pixel exists
+    const int L = an.H * an.W, r = s / an.W, c = s - r * an.W;
+    col[0] = (r + 1 < an.H && c + 1 < an.W) ? 0 * L + s + an.W + 1 : -1;
+    col[1] = (r + 1 < an.H) ? 1 * L + s + an.W : -1;
+    col[2] = (r + 1 < an.H && c >= 1) ? 2 * L + s + an.W - 1 : -1;
+    col[3] = (c + 1 < an.W) ? 3 * L + s + 1 : -1;
+  }
+  float a0 = 0.f, a1 = 0.f;
+  if (s < ncol) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      if (col[k] < 0) continue;
+      const float* p = a.part + col[k];
+      int r = rg;
+      for (; r + 32 < a.rows; r += 64) {
+        a0 += p[(size_t)r * a.stride];
+        a1 += p[(size_t)(r + 32) * a.stride];
+      }
+      if (r < a.rows) a0 += p[(size_t)r * a.stride];
+    }
+  }
+  red[rg][sl] = a0 + a1;
+  __syncthreads();
+  if (rg != 0 || s >= ncol) return;
+  float acc = 0.f;
+#pragma unroll
+  for (int r = 0; r < 32; ++r) acc += red[r][sl];
+  int begin = 0;
+  for (int k = 0; k < a.nseg; ++k) {
+    if (s < a.end[k]) { a.dst[k][s - begin] += acc; return; }
+    begin = a.end[k];
+  }
+}
+
 // Workgroups per launch, at least `min_tiles` tiles per wave. which: 0 head fwd, 1 head bwd, 2 tail fwd, 3 tail bwd.
 // Resident waves per SIMD by register count (75 / 126 / 123 / 248 VGPRs): 6 / 4 / 4 / 2; tail bwd is also held at two
 // workgroups per CU by its 76 KiB of LDS. PG_BLOCK_GRID="a,b,c,d" overrides the caps (tuning).
@@ -862,6 +914,66 @@ PG_EXPORT int pg_gpt_blocks_reduce(int n_blocks, const float* const* head_ws, co
   an.first[an.n] = nb;
   hipLaunchKernelGGL(seg_reduceN_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, an);
   PG_LAUNCH_CHECK("pg_gpt_blocks_reduce");
+  return 0;
+}
+
+// pg_gpt_blocks_reduce plus the model's two ends: ONE launch adds the partial rows of n_blocks (0..8) blocks, of the output head
+// (out_ws: out_rows rows left by pg_gpt_out_head_bwd; out_grads = d ln.weight, d ln.bias, d conv.weight, d conv.bias) and of
+// the stem (stem_ws as left by pg_gpt_stem_bwd with stem_rows / stem_slices of pg_gpt_stem_bwd_plan; stem_grads = d weight
+// (16, 1, 3, 3), d bias, d pos (H x W)). A null out_ws / stem_ws leaves that end out. Everything is added to.
+PG_EXPORT int pg_gpt_model_reduce(int n_blocks, const float* const* head_ws, const float* const* tail_ws, float* const* grads,
+                                  int N, int Cc, int L, const float* out_ws, int out_rows, int Cout, float* const* out_grads,
+                                  const float* stem_ws, int stem_rows, int stem_slices, int H, int W,
+                                  float* const* stem_grads, void* stream) {
+  PG_REQUIRE(n_blocks >= 0 && 2 * n_blocks <= SEG_MAX_JOBS, PG_ESHAPE, "pg_gpt_model_reduce: 0..8 blocks per launch, got %d", n_blocks);
+  PG_REQUIRE(n_blocks == 0 || (head_ws && tail_ws && grads), PG_EINVAL, "pg_gpt_model_reduce: null pointer");
+  PG_REQUIRE(n_blocks > 0 || out_ws || stem_ws, PG_EINVAL, "pg_gpt_model_reduce: nothing to reduce");
+  if (n_blocks > 0)
+    if (int rc = check_shape("pg_gpt_model_reduce", N, Cc, L)) return rc;
+  SegArgsM an = {};
+  an.pos_job = -1;
+  int nb = 0, nj = 0;
+  for (int b = 0; b < n_blocks; ++b) {
+    float* const* g = grads + 14 * b;
+    PG_REQUIRE(head_ws[b] && tail_ws[b], PG_EINVAL, "pg_gpt_model_reduce: null workspace of block %d", b);
+    for (int k = 0; k < 14; ++k) PG_REQUIRE(g[k], PG_EINVAL, "pg_gpt_model_reduce: null gradient %d of block %d", k, b);
+    an.j[nj] = head_seg_args(head_ws[b], grid_blocks(1, N, L), g[0], g[1], g[2], g[3], g[4], g[5]);
+    an.first[nj++] = nb; nb += (H_PART + 7) / 8;
+    an.j[nj] = tail_seg_args(tail_ws[b], bwd_blocks(N, L), g[6], g[7], g[8], g[9], g[10], g[11], g[12], g[13]);
+    an.first[nj++] = nb; nb += (T_PART + 7) / 8;
+  }
+  if (out_ws) {
+    PG_REQUIRE(out_rows >= 1 && Cout >= 1 && Cout <= pg_ends::MAX_COUT && out_grads && out_grads[0] && out_grads[1] &&
+                   out_grads[2] && out_grads[3], PG_EINVAL, "pg_gpt_model_reduce: bad output-head arguments");
+    SegArgs r = {};
+    r.part = out_ws; r.rows = out_rows; r.stride = pg_ends::out_row_floats(Cout); r.nseg = 4;
+    r.end[0] = pg_ends::O_BE; r.dst[0] = out_grads[0];
+    r.end[1] = pg_ends::O_W; r.dst[1] = out_grads[1];
+    r.end[2] = pg_ends::O_W + Cout * pg_ends::C; r.dst[2] = out_grads[2];
+    r.end[3] = r.stride; r.dst[3] = out_grads[3];
+    an.j[nj] = r;
+    an.first[nj++] = nb; nb += (r.stride + 7) / 8;
+  }
+  if (stem_ws) {
+    PG_REQUIRE(stem_rows >= 1 && stem_slices >= 1 && H >= 1 && W >= 1 && stem_grads && stem_grads[0] && stem_grads[1] &&
+                   stem_grads[2], PG_EINVAL, "pg_gpt_model_reduce: bad stem arguments");
+    SegArgs r = {};
+    r.part = stem_ws; r.rows = stem_rows; r.stride = pg_ends::S_PART; r.nseg = 2;
+    r.end[0] = pg_ends::S_B; r.dst[0] = stem_grads[0];
+    r.end[1] = pg_ends::S_PART; r.dst[1] = stem_grads[1];
+    an.j[nj] = r;
+    an.first[nj++] = nb; nb += (pg_ends::S_PART + 7) / 8;
+    SegArgs q = {};
+    q.part = stem_ws + (size_t)stem_rows * pg_ends::S_PART; q.rows = stem_slices; q.stride = pg_ends::ACTIVE * H * W; q.nseg = 1;
+    q.end[0] = H * W; q.dst[0] = stem_grads[2];
+    an.pos_job = nj; an.H = H; an.W = W;
+    an.j[nj] = q;
+    an.first[nj++] = nb; nb += (H * W + 7) / 8;
+  }
+  an.n = nj;
+  an.first[nj] = nb;
+  hipLaunchKernelGGL(seg_reduceM_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, an);
+  PG_LAUNCH_CHECK("pg_gpt_model_reduce");
   return 0;
 }
 

@@ -69,6 +69,17 @@ SIGNATURES = {
     "pg_gpt_block_head_bwd_partial": (c_i, [c_f] * 8 + [c_i, c_i, c_i, c_flt, c_f, c_z, c_s]),
     "pg_gpt_blocks_reduce": (c_i, [c_i, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p),
                                    ctypes.POINTER(ctypes.c_void_p), c_i, c_i, c_i, c_s]),
+    "pg_gpt_stem_fwd": (c_i, [c_f] * 5 + [c_i, c_i, c_i, c_i, c_s]),
+    "pg_gpt_stem_bwd_plan": (c_i, [c_i, c_i, c_i, c_i, c_ip, c_ip]),
+    "pg_gpt_stem_bwd_workspace_floats": (c_z, [c_i, c_i, c_i, c_i]),
+    "pg_gpt_stem_bwd": (c_i, [c_f] * 4 + [c_i, c_i, c_i, c_i, c_f, c_z, c_s]),
+    "pg_gpt_out_head_fwd": (c_i, [c_f] * 6 + [c_i, c_i, c_i, c_i, c_flt, c_i, c_s]),
+    "pg_gpt_out_head_bwd_rows": (c_i, [c_i, c_i, c_i]),
+    "pg_gpt_out_head_bwd": (c_i, [c_f] * 6 + [c_i, c_i, c_i, c_i, c_flt, c_i, c_f, c_z, c_s]),
+    "pg_gpt_model_reduce": (c_i, [c_i, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p),
+                                  ctypes.POINTER(ctypes.c_void_p), c_i, c_i, c_i, c_f, c_i, c_i,
+                                  ctypes.POINTER(ctypes.c_void_p), c_f, c_i, c_i, c_i, c_i,
+                                  ctypes.POINTER(ctypes.c_void_p), c_s]),
     "pg_gpt_block_tail_fwd": (c_i, [c_f] * 11 + [c_i, c_i, c_i, c_i, c_flt, c_s]),
     "pg_gpt_block_tail_bwd": (c_i, [c_f] * 20 + [c_i, c_i, c_i, c_i, c_flt, c_f, c_z, c_s]),
     "pg_gpt_block_tail_bwd_workspace_floats": (c_z, [c_i, c_i]),

@@ -198,16 +198,32 @@ class ImageGPT(base.AutoregressiveModel):
         return canvas
 
     def forward(self, x):
-        x = self._input(ops.add_broadcast_batch(x, self._pos))
-        # one queue for the blocks' weight-gradient partial rows, flushed by the FIRST block (its backward runs last) — only when
-        # every block takes the fused kernels and a backward pass with a gradient for the first block's input will run
-        blocks = list(self._transformer)
+        img, blocks, grad = x, list(self._transformer), torch.is_grad_enabled()
+        # the two ends on their own kernels (gpt_ends.hip) where the model has the BASELINE shape; PG_FUSE_ENDS=0 = generic operators
+        fuse_stem = ops.gpt_stem_supported(img, self._pos, self._input)
+        # The stem's backward runs last: a trainable fused stem flushes the chain on its only path, whichever blocks queued rows
+        stem_flushes = fuse_stem and grad and any(p.requires_grad for p in (self._pos, self._input.weight, self._input.bias))
+        if fuse_stem:
+            x0_grad = stem_flushes
+            probe = torch.empty(1, self._input.weight.shape[0], img.shape[2], img.shape[3], device="meta")
+        else:
+            x = probe = self._input(ops.add_broadcast_batch(img, self._pos))
+            x0_grad = x.requires_grad
+        # one queue for the weight-gradient partial rows of the blocks (and of the output head) — only when every block takes the
+        # fused kernels and a backward pass with a gradient for the first block's input will run. Without a flushing stem the
+        # FIRST block flushes (its backward runs last among the blocks); it queues only on its all-sinks path, so the chain is
+        # then declined unless every block parameter has a sink.
         chain = None
-        if (ops.DEFER_BLOCK_REDUCE and _BLOCK_CHAIN and torch.is_grad_enabled() and x.requires_grad and len(blocks) > 1
-                and all(b._fused_ok(x) for b in blocks)):
+        if (ops.DEFER_BLOCK_REDUCE and _BLOCK_CHAIN and grad and x0_grad and len(blocks) > 1
+                and all(b._fused_ok(probe) for b in blocks)
+                and (stem_flushes or all(ops._sink(p) is not None for b in blocks for p in b.parameters()))):
             chain = ops.new_block_chain()
+        if fuse_stem:
+            x = self._input(img, pos=self._pos, chain=chain if stem_flushes else None)
         for i, block in enumerate(blocks):
-            x = block.forward_plus_input(x, chain, flush=(i == 0))
+            x = block.forward_plus_input(x, chain, flush=(i == 0 and not stem_flushes))
+        if ops.gpt_out_head_supported(x, self._ln, self._out):
+            return self._out(x, pre_ln=self._ln, chain=chain if stem_flushes else None)
         return self._out(self._ln(x))
 
 

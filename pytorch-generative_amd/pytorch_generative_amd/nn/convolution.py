@@ -135,13 +135,22 @@ class Conv2d(nn.Conv2d):
                 and ops.conv_dual_ok(x, self.weight, self._conv_spec()))
 
     def forward(self, x, *, crop=None, in_act=None, res=None, out_act=None, out_pre_scaled=False,
-                in_post=None, n_skip=0, res2=None, gate=None, gate_res=None, res_slot=None, in_sum=None):
+                in_post=None, n_skip=0, res2=None, gate=None, gate_res=None, res_slot=None, in_sum=None, pre_ln=None,
+                chain=None):
         """n_skip > 0 (extension) returns (y, x_1, .., x_n): pass-through aliases of x for the skip
         connections that also read x, see ops.conv2d_taps.
+        pre_ln = an NCHWLayerNorm (extension; only where ops.gpt_out_head_supported(x, pre_ln, self)): returns self(pre_ln(x)) from
+        one kernel each way (ImageGPT's output head, ops.gpt_out_head); `chain` as there.
         gate = ops.GATE_TANH / GATE_IDENTITY (extension, round 6; only where gate_ok()): returns the GatedActivation of this
         convolution's output (conv + res, + gate_res behind the gate) — half the channels — from the same launch.
         in_sum = (r, slot) / res_slot = slot (extension, round 6; only where the consumer's dual_ok()): the two ends of the dual
         data gradient, see ops.GradSlot. Forward values do not change."""
+        if pre_ln is not None:
+            if (crop is not None or in_act is not None or res is not None or out_act is not None or n_skip or res2 is not None
+                    or gate is not None or res_slot is not None or in_sum is not None or ops.RowDecode.current is not None
+                    or not ops.gpt_out_head_supported(x, pre_ln, self)):
+                raise ValueError("Conv2d: pre_ln= needs a plain 1x1 convolution on a shape gpt_out_head_supported() accepts")
+            return ops.gpt_out_head(x, pre_ln, self, chain)
         if res_slot is not None or in_sum is not None:
             if (gate is not None or res2 is not None or n_skip or self._down2 or ops.RowDecode.current is not None
                     or not self.mfma_ok(x, crop)):
@@ -282,7 +291,14 @@ class CausalConv2d(Conv2d):
         m = self.mask[0, 0].detach().to("cpu")
         return [(u, v) for u in range(m.shape[0]) for v in range(m.shape[1]) if m[u, v] != 0]
 
-    def forward(self, x, *, crop=None, in_act=None, res=None, **kw):
+    def forward(self, x, *, crop=None, in_act=None, res=None, pos=None, chain=None, **kw):
+        """pos = a (1, 1, H, W) positional parameter (extension; only where ops.gpt_stem_supported(x, pos, self)): returns
+        self(x + pos) from one kernel each way, the in-place masking included (ImageGPT's stem, ops.gpt_stem); `chain` as there."""
+        if pos is not None:
+            if (crop is not None or in_act is not None or res is not None or kw or ops.RowDecode.current is not None
+                    or not ops.gpt_stem_supported(x, pos, self)):
+                raise ValueError("CausalConv2d: pos= needs the plain stem shape gpt_stem_supported() accepts")
+            return ops.gpt_stem(x, pos, self, chain)
         ops.mul_inplace_(self.weight.data, self.mask)
         return super().forward(x, crop=crop, in_act=in_act, res=res, **kw)
 

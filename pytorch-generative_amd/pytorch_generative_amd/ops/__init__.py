@@ -100,6 +100,17 @@ from pytorch_generative_amd.ops.gpt_block import (  # noqa: F401
     nchw_layernorm,
     nchw_layernorm_skip,
 )
+from pytorch_generative_amd.ops.gpt_ends import (  # noqa: F401
+    FUSE_ENDS,
+    model_reduce,
+    flush_model_reductions,
+    gpt_stem_supported,
+    _GPTStem,
+    gpt_stem,
+    gpt_out_head_supported,
+    _GPTOutHead,
+    gpt_out_head,
+)
 from pytorch_generative_amd.ops.attention import (  # noqa: F401
     _CausalAttention,
     _CausalAttentionQKV,

@@ -127,9 +127,10 @@ def assert_no_pending_block_reductions():
     gradients would silently be missing from the step."""
     for r in _open_chains:
         c = r()
-        if c is not None and c["jobs"]:
-            raise RuntimeError(f"{len(c['jobs'])} deferred GPT-block weight-gradient reductions were never flushed: the first "
-                               "block's backward did not run (set PG_BLOCK_REDUCE_MERGED=0 to reduce per block)")
+        if c is not None and (c["jobs"] or c.get("out") is not None):
+            raise RuntimeError(f"{len(c['jobs']) + (c.get('out') is not None)} deferred ImageGPT weight-gradient reductions were "
+                               "never flushed: the backward that flushes them (the stem's, else the first block's) did not run "
+                               "(set PG_BLOCK_REDUCE_MERGED=0 to reduce per block)")
 
 
 def flush_block_reductions(chain, n, c, L):
@@ -175,7 +176,11 @@ class _GPTBlockHead(torch.autograd.Function):
         x, lnw, lnb, wq, wkv = ctx.saved_tensors
         n, c, h, w = x.shape
         pending = ctx.pair.pop("tail", None) if ctx.pair is not None else None
+        chain = ctx.pair.get("chain") if ctx.pair is not None else None
+        flusher = chain is not None and bool(ctx.pair.get("flush"))
         if dqkv is None:
+            if flusher and chain["jobs"]:  # the other blocks' rows must not wait for a path this backward does not take
+                flush_block_reductions(chain, n, c, h * w)
             if pending is not None:
                 raise RuntimeError("gpt_block_head: a deferred tail reduction is pending but the head has no gradient")
             return gx, None, None, None, None, None, None, None, None, None
@@ -190,7 +195,6 @@ class _GPTBlockHead(torch.autograd.Function):
                      tgt[0].data_ptr(), tgt[1].data_ptr(), tgt[2].data_ptr(),
                      tgt[3].data_ptr(), tgt[4].data_ptr(), tgt[5].data_ptr(), n, c,
                      h * w, ctx.eps, ws.data_ptr(), ws_n)
-        chain = ctx.pair.get("chain") if ctx.pair is not None else None
         if pending is not None and chain is not None and all(r is None for r in ret):
             # round 6: a model-level chain of blocks (ImageGPT passes one list to all of its blocks): this block's head kernel
             # leaves its partial rows as well, and the LAST block to run backward (the model's first) adds the rows of every
@@ -202,9 +206,11 @@ class _GPTBlockHead(torch.autograd.Function):
             chain["jobs"].append((ws, t_ws, [g.data_ptr() for g in tgt] + [t[4].data_ptr(), t[5].data_ptr(), t[6].data_ptr(),
                                                                           t[7].data_ptr(), t[0].data_ptr(), t[1].data_ptr(),
                                                                           t[2].data_ptr(), t[3].data_ptr()], (tgt, t)))
-            if ctx.pair.get("flush"):
+            if flusher:
                 flush_block_reductions(chain, n, c, h * w)
             return (dx, *ret, None, None, None)
+        if flusher and chain["jobs"]:  # this block reduces its own rows (a parameter without a sink): still flush the others'
+            flush_block_reductions(chain, n, c, h * w)
         if pending is not None:  # this block's tail kernel left its partial rows: ONE reduce launch for both
             t_ws, t = pending    # t order: wp, bp, lnw, lnb, w1, b1, w2, b2
             _lib.check(
