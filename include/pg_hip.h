@@ -489,6 +489,18 @@ int pg_gpt_block_tail_bwd(const float* o, const float* x, const float* wp, const
                           float* dw2, float* db2, int N, int C, int Hd, int L, float eps,
                           float* workspace, size_t workspace_floats, void* stream);
 size_t pg_gpt_block_tail_bwd_workspace_floats(int N, int L);
+/* A block boundary of the forward pass in ONE launch: the tail of block i (image_gpt.py:21-52 and the model loop's
+ * `x = x + block(x)`, :104-109) and the head of block i+1 (its _ln1, _attn._q, _attn._kv) on the x_new tile while it is
+ * still in registers. Replaces pg_gpt_block_tail_fwd(..., x_new) followed by pg_gpt_block_head_fwd(x_new, next_*, next_qkv)
+ * and writes the same bits to both outputs (the same device functions; x_new is written but not read back). The first
+ * eleven pointers and N, C, Hd, L are pg_gpt_block_tail_fwd's; next_* are pg_gpt_block_head_fwd's parameters of the
+ * following block. eps is used by both LayerNorms. PG_ESHAPE under the conditions of the two launchers it replaces. */
+int pg_gpt_block_tail_head_fwd(const float* o, const float* x, const float* wp, const float* bp,
+                               const float* ln_w, const float* ln_b, const float* w1, const float* b1,
+                               const float* w2, const float* b2, float* x_new, const float* next_ln_w,
+                               const float* next_ln_b, const float* next_wq, const float* next_bq,
+                               const float* next_wkv, const float* next_bkv, float* next_qkv, int N, int C,
+                               int Hd, int L, float eps, void* stream);
 /* One reduce launch per block instead of two (at the reference's batch 64 the reductions were 6 % of the
  * step): _tail_bwd_partial runs the tail kernel and leaves its partial rows in `workspace` (keep it alive);
  * _head_bwd_with_tail of the SAME block then reduces both kernels' rows in one launch. Results identical to

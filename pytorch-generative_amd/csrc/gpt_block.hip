@@ -1,5 +1,6 @@
 // gpt_block.hip — everything of an ImageGPT transformer block that is not the attention core, as two
-// forward and two backward kernels working on 16-pixel tiles held in registers.
+// forward and two backward kernels working on 16-pixel tiles held in registers (plus a fifth that runs
+// a block's tail and the next block's head forward in one launch).
 //
 // Reference (models/autoregressive/image_gpt.py:21-52, :104-109), C = n_embedding_channels = 16:
 //   head:  qkv   = [W_q; W_kv] LN1(x) + [b_q; b_kv]                  (nn/attention.py:134-143)
@@ -147,22 +148,47 @@ __device__ __forceinline__ const float* qkv_row(const BlockArgs& a, int ch) {
 }
 
 // ---------------------------------------------------------------------------------- head, forward
+// The per-lane operands of the head chain: A[i = out channel 16m+j][k = g <-> in channel 4g+r], bias / LN1 affine in D layout
+struct HeadFrags {
+  float wf[3][4]; f32x4 bias[3], gam, bet;
+  __device__ __forceinline__ HeadFrags(const BlockArgs& a, int j, int g) {
+#pragma unroll
+    for (int m = 0; m < 3; ++m) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        wf[m][r] = qkv_row(a, 16 * m + j)[4 * g + r];
+        const int ch = 16 * m + 4 * g + r;
+        bias[m][r] = ch < C ? a.bq[ch] : a.bkv[ch - C];
+      }
+    }
+    gam = load_vec(a.g1, g);
+    bet = load_vec(a.be1, g);
+  }
+};
+// head chain of one tile: q/kv tile m (channels 16m .. 16m+15) = [W_q; W_kv] LN1(x) + [b_q; b_kv]. The ONE copy of this arithmetic:
+// head_fwd_kernel runs it on a loaded tile, tail_head_fwd_kernel on the x_new tile its tail chain left in registers.
+__device__ __forceinline__ void head_chain(const f32x4& xv, const HeadFrags& f, float eps, f32x4 (&out)[3]) {
+  const Ln s = ln_stats(xv, eps);
+  f32x4 y;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) y[r] = fmaf(s.xhat[r], f.gam[r], f.bet[r]);
+#pragma unroll
+  for (int m = 0; m < 3; ++m) {
+    out[m] = f.bias[m];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) out[m] = MFMA16(f.wf[m][r], y[r], out[m]);
+  }
+}
+__device__ __forceinline__ void store_qkv_tiles(float* __restrict__ qb, int L, int g, const f32x4 (&q)[3]) {
+#pragma unroll
+  for (int m = 0; m < 3; ++m) store_tile(qb + (size_t)(16 * m) * L, L, g, q[m]);
+}
+
 __global__ void __launch_bounds__(GB_THREADS) head_fwd_kernel(const BlockArgs a) {
   const int lane = threadIdx.x & 63, j = lane & 15, g = lane >> 4;
   const int wave = blockIdx.x * (GB_THREADS / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int nwaves = gridDim.x * (GB_THREADS / 64);
-  float wf[3][4];  // A[i = out channel 16m+j][k = g <-> in channel 4g+r]
-  f32x4 bias[3];
-#pragma unroll
-  for (int m = 0; m < 3; ++m) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      wf[m][r] = qkv_row(a, 16 * m + j)[4 * g + r];
-      const int ch = 16 * m + 4 * g + r;
-      bias[m][r] = ch < C ? a.bq[ch] : a.bkv[ch - C];
-    }
-  }
-  const f32x4 gam = load_vec(a.g1, g), bet = load_vec(a.be1, g);
+  const HeadFrags hf(a, j, g);
   if (wave >= a.total_tiles) return;  // a wave without a tile loads nothing
   TileWalk tw(a, wave, nwaves);
   f32x4 xv = load_tile(a.x + tw.base(C, a.L) + j, a.L, g);
@@ -173,18 +199,9 @@ __global__ void __launch_bounds__(GB_THREADS) head_fwd_kernel(const BlockArgs a)
     const bool more = nx.n < a.N;
     const f32x4 xn = load_tile(a.x + (more ? nx : tw).base(C, a.L) + j, a.L, g);
     prefetch_fence();
-    const Ln s = ln_stats(xv, a.eps);
-    f32x4 y;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) y[r] = fmaf(s.xhat[r], gam[r], bet[r]);
-    float* qb = a.qkv + tw.base(QKV, a.L) + j;
-#pragma unroll
-    for (int m = 0; m < 3; ++m) {
-      f32x4 out = bias[m];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) out = MFMA16(wf[m][r], y[r], out);
-      store_tile(qb + (size_t)(16 * m) * a.L, a.L, g, out);
-    }
+    f32x4 q[3];
+    head_chain(xv, hf, a.eps, q);
+    store_qkv_tiles(a.qkv + tw.base(QKV, a.L) + j, a.L, g, q);
     if (!more) break;
     xv = xn;
     tw = nx;
@@ -307,25 +324,61 @@ __global__ void __launch_bounds__(GB_THREADS) head_bwd_kernel(const BlockArgs a)
 }
 
 // ---------------------------------------------------------------------------------- tail, forward
+// The per-lane operands of the tail chain
+struct TailFrags {
+  float wpf[4];     // A[i = co j][k <-> ci 4g+r]
+  float w1f[4][4];  // A[i = hidden 16m+j][k <-> c 4g+r]
+  float w2f[4][4];  // A[i = co j][k <-> hidden 16m+4g+r]
+  f32x4 b1r[4], bpv, b2v, gam, bet;
+  __device__ __forceinline__ TailFrags(const BlockArgs& a, int j, int g) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) wpf[r] = a.wp[j * C + 4 * g + r];
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        w1f[m][r] = a.w1[(16 * m + j) * C + 4 * g + r];
+        w2f[m][r] = a.w2[j * HD + 16 * m + 4 * g + r];
+        b1r[m][r] = a.b1[16 * m + 4 * g + r];
+      }
+    }
+    bpv = load_vec(a.bp, g);
+    b2v = load_vec(a.b2, g);
+    gam = load_vec(a.g2, g);
+    bet = load_vec(a.be2, g);
+  }
+};
+// tail chain of one tile: x_new = x + x_mid + W_2 gelu(W_1 LN2(x_mid) + b_1) + b_2, x_mid = x + W_p o + b_p. The ONE copy of this
+// arithmetic, shared by tail_fwd_kernel and tail_head_fwd_kernel.
+__device__ __forceinline__ f32x4 tail_chain(const f32x4& xv, const f32x4& ov, const TailFrags& f, float eps) {
+  f32x4 xm = xv + f.bpv;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) xm = MFMA16(f.wpf[r], ov[r], xm);
+  const Ln s = ln_stats(xm, eps);
+  f32x4 y;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) y[r] = fmaf(s.xhat[r], f.gam[r], f.bet[r]);
+  f32x4 h[4];
+#pragma unroll
+  for (int m = 0; m < 4; ++m) {
+    h[m] = f.b1r[m];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) h[m] = MFMA16(f.w1f[m][r], y[r], h[m]);
+  }
+  f32x4 out = (xm + f.b2v) + xv;
+#pragma unroll
+  for (int m = 0; m < 4; ++m) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) out = MFMA16(f.w2f[m][r], gelu_f(h[m][r]), out);
+  }
+  return out;
+}
+
 __global__ void __launch_bounds__(GB_THREADS) tail_fwd_kernel(const BlockArgs a) {
   const int lane = threadIdx.x & 63, j = lane & 15, g = lane >> 4;
   const int wave = blockIdx.x * (GB_THREADS / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int nwaves = gridDim.x * (GB_THREADS / 64);
-  float wpf[4], w1f[4][4], w2f[4][4];
-  f32x4 b1r[4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) wpf[r] = a.wp[j * C + 4 * g + r];  // A[i = co j][k <-> ci 4g+r]
-#pragma unroll
-  for (int m = 0; m < 4; ++m) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      w1f[m][r] = a.w1[(16 * m + j) * C + 4 * g + r];      // A[i = hidden 16m+j][k <-> c 4g+r]
-      w2f[m][r] = a.w2[j * HD + 16 * m + 4 * g + r];       // A[i = co j][k <-> hidden 16m+4g+r]
-      b1r[m][r] = a.b1[16 * m + 4 * g + r];
-    }
-  }
-  const f32x4 bpv = load_vec(a.bp, g), b2v = load_vec(a.b2, g);
-  const f32x4 gam = load_vec(a.g2, g), bet = load_vec(a.be2, g);
+  const TailFrags tf(a, j, g);
   if (wave >= a.total_tiles) return;  // a wave without a tile loads nothing
   TileWalk tw(a, wave, nwaves);
   size_t off = tw.base(C, a.L) + j;
@@ -340,27 +393,48 @@ __global__ void __launch_bounds__(GB_THREADS) tail_fwd_kernel(const BlockArgs a)
     const f32x4 xn = load_tile(a.x + offn, a.L, g);
     const f32x4 on = load_tile(a.o + offn, a.L, g);
     prefetch_fence();
-    f32x4 xm = xv + bpv;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) xm = MFMA16(wpf[r], ov[r], xm);
-    const Ln s = ln_stats(xm, a.eps);
-    f32x4 y;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) y[r] = fmaf(s.xhat[r], gam[r], bet[r]);
-    f32x4 h[4];
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-      h[m] = b1r[m];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) h[m] = MFMA16(w1f[m][r], y[r], h[m]);
-    }
-    f32x4 out = (xm + b2v) + xv;
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) out = MFMA16(w2f[m][r], gelu_f(h[m][r]), out);
-    }
+    store_tile(a.xnew + off, a.L, g, tail_chain(xv, ov, tf, a.eps));
+    if (!more) break;
+    xv = xn;
+    ov = on;
+    off = offn;
+    tw = nx;
+  }
+}
+
+// ---------------------------------------------------------------------------------- tail(i) + head(i+1), forward
+// A block boundary of the forward pass in one launch: the tail chain of block i, then LN1 and the q/kv projection of block i+1 on
+// the x_new tile while it is still a register tile (D layout = the head's input layout). x_new is still written — the backward
+// pass reads it — but never read back: 64 B per pixel and one launch less than tail_fwd + head_fwd. The tail chain is bound by
+// issue (MFMA + VALU cycles add), the head by its 192 B per pixel of stores, which here drain under the next tile's chain.
+// tail_fwd's registers plus the head's 12 + 12 + 8 operand registers: 164 VGPRs, three waves per SIMD (launch bounds). A form with
+// those 32 and b_1's 16 operands as one [fragment][lane] copy in LDS (118 VGPRs, four waves) measured the same in the step at
+// batch 1024 and slower at batch 64 (profiles/gpt_boundary.json, "other_form").
+__global__ void __launch_bounds__(GB_THREADS, 3) tail_head_fwd_kernel(const BlockArgs a) {
+  const int lane = threadIdx.x & 63, j = lane & 15, g = lane >> 4;
+  const int wave = blockIdx.x * (GB_THREADS / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int nwaves = gridDim.x * (GB_THREADS / 64);
+  const TailFrags tf(a, j, g);
+  const HeadFrags hf(a, j, g);
+  if (wave >= a.total_tiles) return;  // a wave without a tile loads nothing
+  TileWalk tw(a, wave, nwaves);
+  size_t off = tw.base(C, a.L) + j;
+  f32x4 xv = load_tile(a.x + off, a.L, g);
+  f32x4 ov = load_tile(a.o + off, a.L, g);
+  wait_prologue_loads();
+  for (;;) {
+    // the last iteration re-reads its own tile instead of branching around the prefetch
+    const TileWalk nx = tw.next();
+    const bool more = nx.n < a.N;
+    const size_t offn = (more ? nx : tw).base(C, a.L) + j;
+    const f32x4 xn = load_tile(a.x + offn, a.L, g);
+    const f32x4 on = load_tile(a.o + offn, a.L, g);
+    prefetch_fence();
+    const f32x4 out = tail_chain(xv, ov, tf, a.eps);
     store_tile(a.xnew + off, a.L, g, out);
+    f32x4 q[3];
+    head_chain(out, hf, a.eps, q);
+    store_qkv_tiles(a.qkv + tw.base(QKV, a.L) + j, a.L, g, q);
     if (!more) break;
     xv = xn;
     ov = on;
@@ -722,22 +796,25 @@ __global__ void __launch_bounds__(256) seg_reduceM_kernel(const SegArgsM an) {
   }
 }
 
-// Workgroups per launch, at least `min_tiles` tiles per wave. which: 0 head fwd, 1 head bwd, 2 tail fwd, 3 tail bwd.
-// Resident waves per SIMD by register count (75 / 126 / 123 / 248 VGPRs): 6 / 4 / 4 / 2; tail bwd is also held at two
-// workgroups per CU by its 76 KiB of LDS. PG_BLOCK_GRID="a,b,c,d" overrides the caps (tuning).
+// Workgroups per launch, at least `min_tiles` tiles per wave. which: 0 head fwd, 1 head bwd, 2 tail fwd, 3 tail bwd,
+// 4 tail + head fwd. Resident waves per SIMD by register count (75 / 126 / 125 / 248 / 164 VGPRs): 6 / 4 / 4 / 2 / 3; tail bwd
+// is also held at two workgroups per CU by its 76 KiB of LDS. PG_BLOCK_GRID="a,b,c,d[,e]" overrides the caps (tuning).
 int grid_blocks(int which, int N, int L) {
   // immutable init-once tables (function-local static with an initialiser: thread-safe; the library
   // is entered from the main thread and from the autograd thread)
-  struct Cfg { int cap[4]; int mt[2]; };
+  struct Cfg { int cap[5]; int mt[2]; };
   static const Cfg cfg = []() {
-    Cfg c = {{2048, 1024, 2048, 512},  // the backward caps are one full round of resident waves; the re-sweep with the pipelined
+    Cfg c = {{2048, 1024, 2048, 512,  // the backward caps are one full round of resident waves; the re-sweep with the pipelined
                                       // loops moved nothing beyond spread (profiles/gpt_block_pipeline.json, "grid_sweep_us_per_launch")
+              1536},                  // tail + head fwd: two whole rounds like tail fwd's 2048, but of 3 waves per SIMD
+                                      // (256 CUs x 4 SIMDs x 3 waves / 4 waves per workgroup = 768 workgroups per round)
              {1, 2}};                 // tiles per wave below which the grid shrinks (forward, backward);
                                       // measured at batch 64: (4, 8) 1.82 ms/step, (2, 4) 1.59, (1, 2) 1.53, (1, 1) 1.56
     if (const char* e = PG_AB_ENV("PG_BLOCK_GRID")) {
-      int v[4];
-      if (sscanf(e, "%d,%d,%d,%d", &v[0], &v[1], &v[2], &v[3]) == 4 && v[0] > 0 && v[1] > 0 && v[2] > 0 && v[3] > 0)
-        for (int i = 0; i < 4; ++i) c.cap[i] = v[i];
+      int v[5];
+      const int got = sscanf(e, "%d,%d,%d,%d,%d", &v[0], &v[1], &v[2], &v[3], &v[4]);
+      if (got >= 4 && v[0] > 0 && v[1] > 0 && v[2] > 0 && v[3] > 0 && (got == 4 || v[4] > 0))
+        for (int i = 0; i < got; ++i) c.cap[i] = v[i];
     }
     if (const char* e = PG_AB_ENV("PG_BLOCK_MINTILES")) {
       int f = 0, b = 0;
@@ -992,6 +1069,30 @@ PG_EXPORT int pg_gpt_block_tail_fwd(const float* o, const float* x, const float*
   set_geometry(a, N, L, eps);
   hipLaunchKernelGGL(tail_fwd_kernel, dim3((unsigned)grid_blocks(2, N, L)), dim3(GB_THREADS), 0, (hipStream_t)stream, a);
   PG_LAUNCH_CHECK("pg_gpt_block_tail_fwd");
+  return 0;
+}
+
+// tail_fwd of block i and head_fwd of block i+1 in one launch (tail_head_fwd_kernel): writes x_new (N, 16, L) and the NEXT block's
+// qkv (N, 48, L), bit for bit what pg_gpt_block_tail_fwd followed by pg_gpt_block_head_fwd(x_new, ...) write. eps serves both
+// LayerNorms (the caller fuses only blocks whose ln2 / next ln1 share it).
+PG_EXPORT int pg_gpt_block_tail_head_fwd(const float* o, const float* x, const float* wp, const float* bp,
+                                         const float* ln_w, const float* ln_b, const float* w1, const float* b1,
+                                         const float* w2, const float* b2, float* x_new, const float* next_ln_w,
+                                         const float* next_ln_b, const float* next_wq, const float* next_bq,
+                                         const float* next_wkv, const float* next_bkv, float* next_qkv, int N, int Cc,
+                                         int Hd, int L, float eps, void* stream) {
+  PG_REQUIRE(o && x && wp && bp && ln_w && ln_b && w1 && b1 && w2 && b2 && x_new && next_ln_w && next_ln_b && next_wq &&
+                 next_bq && next_wkv && next_bkv && next_qkv, PG_EINVAL, "pg_gpt_block_tail_head_fwd: null pointer");
+  int rc = check_shape("pg_gpt_block_tail_head_fwd", N, Cc, L);
+  if (rc) return rc;
+  PG_REQUIRE(Hd == HD, PG_ESHAPE, "pg_gpt_block_tail_head_fwd: only hidden = 64 is instantiated (got %d)", Hd);
+  BlockArgs a = {};
+  a.o = o; a.x = x; a.wp = wp; a.bp = bp; a.g2 = ln_w; a.be2 = ln_b; a.w1 = w1; a.b1 = b1; a.w2 = w2;
+  a.b2 = b2; a.xnew = x_new;
+  a.g1 = next_ln_w; a.be1 = next_ln_b; a.wq = next_wq; a.bq = next_bq; a.wkv = next_wkv; a.bkv = next_bkv; a.qkv = next_qkv;
+  set_geometry(a, N, L, eps);
+  hipLaunchKernelGGL(tail_head_fwd_kernel, dim3((unsigned)grid_blocks(4, N, L)), dim3(GB_THREADS), 0, (hipStream_t)stream, a);
+  PG_LAUNCH_CHECK("pg_gpt_block_tail_head_fwd");
   return 0;
 }
 

@@ -81,6 +81,7 @@ SIGNATURES = {
                                   ctypes.POINTER(ctypes.c_void_p), c_f, c_i, c_i, c_i, c_i,
                                   ctypes.POINTER(ctypes.c_void_p), c_s]),
     "pg_gpt_block_tail_fwd": (c_i, [c_f] * 11 + [c_i, c_i, c_i, c_i, c_flt, c_s]),
+    "pg_gpt_block_tail_head_fwd": (c_i, [c_f] * 18 + [c_i, c_i, c_i, c_i, c_flt, c_s]),
     "pg_gpt_block_tail_bwd": (c_i, [c_f] * 20 + [c_i, c_i, c_i, c_i, c_flt, c_f, c_z, c_s]),
     "pg_gpt_block_tail_bwd_workspace_floats": (c_z, [c_i, c_i]),
     "pg_gpt_block_tail_bwd_partial": (c_i, [c_f] * 12 + [c_i, c_i, c_i, c_i, c_flt, c_f, c_z, c_s]),

@@ -42,21 +42,26 @@ class TransformerBlock(nn.Module):
         return ops.gpt_block_supported(x, self._ln1, self._attn._q, self._attn._kv, self._attn._proj,
                                        self._ln2, self._out[0], self._out[2])
 
-    def forward_plus_input(self, x, chain=None, flush=False):
+    def forward_plus_input(self, x, chain=None, flush=False, boundary=None, next_block=None):
         """x + self(x) — what the model loop computes (reference image_gpt.py:107) — on the fused
         head / attention / tail kernels (gpt_block.hip) when the block has the BASELINE shape.
         chain / flush (round 6): a queue shared by all blocks of the model, flushed by the block whose backward runs last —
-        the weight-gradient rows of all blocks are then reduced by ONE launch (ops.gpt_block_head)."""
+        the weight-gradient rows of all blocks are then reduced by ONE launch (ops.gpt_block_head).
+        boundary / next_block: a dict shared by the blocks of one forward and the block that runs next (fused shape as well) —
+        this block's tail launch then also computes that block's LN1 and q/kv projection (ops.gpt_block_tail)."""
         if not self._fused_ok(x):
             return ops.add(x, self.forward(x))
         attn = self._attn
         pair = {}  # lets the block's two backward kernels share one weight-gradient reduction launch
         if chain is not None:
             pair["chain"], pair["flush"] = chain, flush
+        if boundary is not None:
+            pair["boundary"] = boundary
+        nxt = None if next_block is None else (next_block._ln1, next_block._attn._q, next_block._attn._kv)
         qkv, xs = ops.gpt_block_head(x, self._ln1, attn._q, attn._kv, pair)
         o = ops.causal_attention_qkv(qkv, attn._n_heads, attn._embed_channels, attn._out_channels,
                                      attn._mask_center)
-        return ops.gpt_block_tail(o, xs, attn._proj, self._ln2, self._out[0], self._out[2], pair)
+        return ops.gpt_block_tail(o, xs, attn._proj, self._ln2, self._out[0], self._out[2], pair, nxt)
 
     def forward(self, x):
         # skip=True: the residual branch's gradient is added inside the LayerNorm backward kernel
@@ -220,8 +225,12 @@ class ImageGPT(base.AutoregressiveModel):
             chain = ops.new_block_chain()
         if fuse_stem:
             x = self._input(img, pos=self._pos, chain=chain if stem_flushes else None)
+        # block boundaries: tail(i) + head(i+1) in one launch where both blocks take the fused kernels; PG_FUSE_BOUNDARY=0 = two
+        fused = [b._fused_ok(probe) for b in blocks] if ops.gpt_block.FUSE_BOUNDARY else [False] * len(blocks)
+        boundary = {} if any(fused) else None
         for i, block in enumerate(blocks):
-            x = block.forward_plus_input(x, chain, flush=(i == 0 and not stem_flushes))
+            nxt = blocks[i + 1] if i + 1 < len(blocks) and fused[i] and fused[i + 1] else None
+            x = block.forward_plus_input(x, chain, flush=(i == 0 and not stem_flushes), boundary=boundary, next_block=nxt)
         if ops.gpt_out_head_supported(x, self._ln, self._out):
             return self._out(x, pre_ln=self._ln, chain=chain if stem_flushes else None)
         return self._out(self._ln(x))

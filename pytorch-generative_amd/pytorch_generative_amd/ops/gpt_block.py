@@ -88,6 +88,8 @@ def mlp_gelu(x, conv1, conv2, res=None):
 # --------------------------------------------------------------------------------------------
 FUSE_BLOCK = os.environ.get("PG_FUSE_BLOCK", "1") != "0"
 DEFER_BLOCK_REDUCE = os.environ.get("PG_BLOCK_REDUCE_MERGED", "1") != "0"  # A/B: 0 = two reduce launches per block
+# A/B: 0 = tail(i) and head(i+1) as two forward launches instead of pg_gpt_block_tail_head_fwd (read by ImageGPT.forward per call)
+FUSE_BOUNDARY = os.environ.get("PG_FUSE_BOUNDARY", "1") != "0"
 
 
 def _grad_targets(params):
@@ -148,6 +150,20 @@ def flush_block_reductions(chain, n, c, L):
     jobs.clear()
 
 
+def _take_boundary_qkv(pair, x, head, eps):
+    """The qkv that the previous block's tail already computed for exactly this input (pg_gpt_block_tail_head_fwd), or None.
+    The entry is keyed by the tail's x_new: it is taken only for the same memory at the same version, with the same six
+    parameter tensors and eps, and it is removed whether it matches or not."""
+    boundary = pair.get("boundary") if pair is not None else None
+    entry = boundary.pop("qkv", None) if boundary is not None else None
+    if entry is None:
+        return None
+    x_new, version, params, e, qkv = entry
+    same = (x.data_ptr() == x_new.data_ptr() and x.shape == x_new.shape and x.stride() == x_new.stride()
+            and x._version == version and e == eps and len(params) == len(head) and all(a is b for a, b in zip(params, head)))
+    return qkv if same else None
+
+
 class _GPTBlockHead(torch.autograd.Function):
     """(qkv, x) = ([W_q; W_kv] LN1(x) + b, x). The second output aliases x: whatever gradient reaches it
     (the residual routes of the block) is added to LN1's input gradient inside the backward kernel."""
@@ -159,13 +175,15 @@ class _GPTBlockHead(torch.autograd.Function):
         x_in = x
         x = _chk(x, "gpt_block_head.x")
         n, c, h, w = x.shape
-        qkv = torch.empty((n, 3 * c, h, w), device=x.device, dtype=torch.float32)
-        _lib.check(
-            lib.pg_gpt_block_head_fwd(x.data_ptr(), lnw.data_ptr(), lnb.data_ptr(), wq.data_ptr(),
-                                      bq.data_ptr(), wkv.data_ptr(), bkv.data_ptr(), qkv.data_ptr(),
-                                      n, c, h * w, eps, _stream()),
-            "pg_gpt_block_head_fwd",
-        )
+        qkv = _take_boundary_qkv(pair, x, (lnw, lnb, wq, bq, wkv, bkv), eps)
+        if qkv is None:
+            qkv = torch.empty((n, 3 * c, h, w), device=x.device, dtype=torch.float32)
+            _lib.check(
+                lib.pg_gpt_block_head_fwd(x.data_ptr(), lnw.data_ptr(), lnb.data_ptr(), wq.data_ptr(),
+                                          bq.data_ptr(), wkv.data_ptr(), bkv.data_ptr(), qkv.data_ptr(),
+                                          n, c, h * w, eps, _stream()),
+                "pg_gpt_block_head_fwd",
+            )
         ctx.save_for_backward(x, lnw, lnb, wq, wkv)
         ctx.eps, ctx.params = eps, params
         return qkv, x_in
@@ -232,17 +250,34 @@ class _GPTBlockTail(torch.autograd.Function):
     def forward(ctx, o, x, wp, bp, lnw, lnb, w1, b1, w2, b2, eps, params, pair=None):
         lib = _lib.load()
         ctx.pair = pair
+        # optional: the six parameter tensors of the NEXT block's head (gpt_block_tail), used as raw pointers only
+        next_head = pair.pop("next_head", None) if pair is not None else None
         o = _chk(o, "gpt_block_tail.o")
         x = _chk(x, "gpt_block_tail.x")
         n, c, h, w = x.shape
         x_new = torch.empty_like(x)
-        _lib.check(
-            lib.pg_gpt_block_tail_fwd(o.data_ptr(), x.data_ptr(), wp.data_ptr(), bp.data_ptr(),
-                                      lnw.data_ptr(), lnb.data_ptr(), w1.data_ptr(), b1.data_ptr(),
-                                      w2.data_ptr(), b2.data_ptr(), x_new.data_ptr(), n, c,
-                                      w1.shape[0], h * w, eps, _stream()),
-            "pg_gpt_block_tail_fwd",
-        )
+        if next_head is not None:
+            # the next block's head in the same launch: its qkv waits in pair["boundary"] for that block's _GPTBlockHead.forward,
+            # which returns it as its own output (autograd sees the same graph as with two launches); next_head's tensors are
+            # raw pointers here, their gradients come from the next head's backward as always
+            qkv = torch.empty((n, 3 * c, h, w), device=x.device, dtype=torch.float32)
+            _lib.check(
+                lib.pg_gpt_block_tail_head_fwd(o.data_ptr(), x.data_ptr(), wp.data_ptr(), bp.data_ptr(),
+                                               lnw.data_ptr(), lnb.data_ptr(), w1.data_ptr(), b1.data_ptr(),
+                                               w2.data_ptr(), b2.data_ptr(), x_new.data_ptr(),
+                                               *(t.data_ptr() for t in next_head), qkv.data_ptr(), n, c,
+                                               w1.shape[0], h * w, eps, _stream()),
+                "pg_gpt_block_tail_head_fwd",
+            )
+            pair["boundary"]["qkv"] = (x_new, x_new._version, tuple(next_head), eps, qkv)
+        else:
+            _lib.check(
+                lib.pg_gpt_block_tail_fwd(o.data_ptr(), x.data_ptr(), wp.data_ptr(), bp.data_ptr(),
+                                          lnw.data_ptr(), lnb.data_ptr(), w1.data_ptr(), b1.data_ptr(),
+                                          w2.data_ptr(), b2.data_ptr(), x_new.data_ptr(), n, c,
+                                          w1.shape[0], h * w, eps, _stream()),
+                "pg_gpt_block_tail_fwd",
+            )
         ctx.save_for_backward(o, x, wp, bp, lnw, lnb, w1, b1, w2)
         ctx.eps, ctx.params = eps, params
         return x_new
@@ -304,9 +339,17 @@ def gpt_block_head(x, ln1, q, kv, pair=None):
     return _GPTBlockHead.apply(x, *params, float(ln1.eps), params, pair)
 
 
-def gpt_block_tail(o, x, proj, ln2, fc1, fc2, pair=None):
+def gpt_block_tail(o, x, proj, ln2, fc1, fc2, pair=None, next_head=None):
+    """next_head = (ln1, q, kv) of the FOLLOWING block (which must pass gpt_block_supported too): its LN1 and q/kv projection run
+    in this block's tail launch, and the qkv waits in pair["boundary"] — a dict shared by the blocks of one forward — for the
+    gpt_block_head call of that block on the tensor returned here."""
     params = (proj.weight, proj.bias, ln2.weight, ln2.bias, fc1.weight, fc1.bias, fc2.weight, fc2.bias)
-    return _GPTBlockTail.apply(o, x, *params, float(ln2.eps), params, pair)
+    eps = float(ln2.eps)
+    if next_head is not None and pair is not None and pair.get("boundary") is not None:
+        ln1, q, kv = next_head
+        if float(ln1.eps) == eps:  # one eps serves both LayerNorms of the launch
+            pair["next_head"] = (ln1.weight, ln1.bias, q.weight, q.bias, kv.weight, kv.bias)
+    return _GPTBlockTail.apply(o, x, *params, eps, params, pair)
 
 
 # --------------------------------------------------------------------------------------------

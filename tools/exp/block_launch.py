@@ -1,4 +1,5 @@
-"""A few launches of the four GPT-block kernels (csrc/gpt_block.hip) at the bench's batch, through the C-ABI, for rocprofv3 counter
+"""A few launches of the GPT-block kernels (csrc/gpt_block.hip: head / tail forward and backward, and the fused tail + next head
+forward) at the bench's batch, through the C-ABI, for rocprofv3 counter
 passes (--pmc alone, never combined with a trace domain) and for a library A/B (PG_HIP_LIB=<other build>):
 
     python tools/exp/block_launch.py [launches] [batch]
@@ -26,6 +27,7 @@ torch.manual_seed(0)
 r = lambda *s: torch.randn(*s, device=dev)  # noqa: E731
 x, o, d, gx, dqkv = r(n, 16, L), r(n, 16, L), r(n, 16, L), r(n, 16, L), r(n, 48, L)
 qkv, xnew, d_o, gxo, dx = (torch.empty(n, c, L, device=dev) for c in (48, 16, 16, 16, 16))
+qkv2, xnew2 = torch.empty(n, 48, L, device=dev), torch.empty(n, 16, L, device=dev)  # the fused launch's own outputs
 g1, be1, wq, bq, wkv, bkv = r(16), r(16), r(16, 16) * .2, r(16), r(32, 16) * .2, r(32)
 wp, bp, g2, be2, w1, b1, w2, b2 = r(16, 16) * .2, r(16), r(16), r(16), r(64, 16) * .2, r(64), r(16, 64) * .1, r(16)
 G = {k: torch.zeros_like(v) for k, v in dict(g1=g1, be1=be1, wq=wq, bq=bq, wkv=wkv, bkv=bkv, wp=wp, bp=bp, g2=g2, be2=be2, w1=w1,
@@ -38,6 +40,10 @@ calls = {
     "head_fwd": lambda: lib.pg_gpt_block_head_fwd(p(x), p(g1), p(be1), p(wq), p(bq), p(wkv), p(bkv), p(qkv), n, 16, L, eps, st),
     "tail_fwd": lambda: lib.pg_gpt_block_tail_fwd(p(o), p(x), p(wp), p(bp), p(g2), p(be2), p(w1), p(b1), p(w2), p(b2), p(xnew),
                                                   n, 16, 64, L, eps, st),
+    # tail of a block + head of the next one (the head's parameters stand in for the next block's)
+    "tail_head_fwd": lambda: lib.pg_gpt_block_tail_head_fwd(p(o), p(x), p(wp), p(bp), p(g2), p(be2), p(w1), p(b1), p(w2), p(b2),
+                                                            p(xnew2), p(g1), p(be1), p(wq), p(bq), p(wkv), p(bkv), p(qkv2),
+                                                            n, 16, 64, L, eps, st),
     "tail_bwd": lambda: lib.pg_gpt_block_tail_bwd(p(o), p(x), p(wp), p(bp), p(g2), p(be2), p(w1), p(b1), p(w2), p(d), p(d_o), p(gxo),
                                                   p(G["wp"]), p(G["bp"]), p(G["g2"]), p(G["be2"]), p(G["w1"]), p(G["b1"]), p(G["w2"]),
                                                   p(G["b2"]), n, 16, 64, L, eps, p(tws), tn, st),
