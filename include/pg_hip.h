@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define PG_ABI_VERSION 2
+#define PG_ABI_VERSION 3
 
 #define PG_EINVAL (-1)  /* bad argument */
 #define PG_ESHAPE (-2)  /* shape outside what the kernels support (no silent fallback) */
@@ -501,31 +501,19 @@ int pg_gpt_block_tail_head_fwd(const float* o, const float* x, const float* wp, 
                                const float* next_ln_b, const float* next_wq, const float* next_bq,
                                const float* next_wkv, const float* next_bkv, float* next_qkv, int N, int C,
                                int Hd, int L, float eps, void* stream);
-/* One reduce launch per block instead of two (at the reference's batch 64 the reductions were 6 % of the
- * step): _tail_bwd_partial runs the tail kernel and leaves its partial rows in `workspace` (keep it alive);
- * _head_bwd_with_tail of the SAME block then reduces both kernels' rows in one launch. Results identical to
- * pg_gpt_block_tail_bwd + pg_gpt_block_head_bwd (same summation order). */
+/* The two backward kernels WITHOUT their reductions: each leaves its rows of partial weight-gradient sums in `workspace`
+ * (pg_gpt_block_*_bwd_workspace_floats floats; keep it alive) and touches no gradient. pg_gpt_model_reduce, declared with
+ * ImageGPT's ends below, adds the rows of up to 8 blocks to their gradients in one launch. The gradients are bit for bit those of
+ * pg_gpt_block_tail_bwd + pg_gpt_block_head_bwd, however the blocks are grouped into launches: the same kernel adds every
+ * column's rows in the same order. */
 int pg_gpt_block_tail_bwd_partial(const float* o, const float* x, const float* wp, const float* bp,
                                   const float* ln_w, const float* ln_b, const float* w1, const float* b1,
                                   const float* w2, const float* dx_new, float* d_o, float* gx, int N, int Cc,
                                   int Hd, int L, float eps, float* workspace, size_t workspace_floats,
                                   void* stream);
-int pg_gpt_block_head_bwd_with_tail(const float* x, const float* ln_w, const float* ln_b, const float* wq,
-                                    const float* wkv, const float* dqkv, const float* gx, float* dx,
-                                    float* dln_w, float* dln_b, float* dwq, float* dbq, float* dwkv,
-                                    float* dbkv, int N, int Cc, int L, float eps, float* workspace,
-                                    size_t workspace_floats, const float* tail_workspace, float* t_dw1,
-                                    float* t_db1, float* t_dw2, float* t_db2, float* t_dwp, float* t_dbp,
-                                    float* t_dln_w, float* t_dln_b, void* stream);
-/* Round 6: the same head backward WITHOUT its reduction (partial rows stay in `workspace`), and ONE launch that adds the partial
- * rows of up to 8 blocks' head and tail kernels into their gradients at the end of the backward pass (at the reference's batch 64
- * the eight per-block reduce launches were 3.9 % of a step's kernel time). grads: n_blocks x 14 device pointers (HOST array), per
- * block dln1_w, dln1_b, dwq, dbq, dwkv, dbkv, then the tail's dw1, db1, dw2, db2, dwp, dbp, dln2_w, dln2_b. */
 int pg_gpt_block_head_bwd_partial(const float* x, const float* ln_w, const float* ln_b, const float* wq, const float* wkv,
                                   const float* dqkv, const float* gx, float* dx, int N, int C, int L, float eps,
                                   float* workspace, size_t workspace_floats, void* stream);
-int pg_gpt_blocks_reduce(int n_blocks, const float* const* head_ws, const float* const* tail_ws, float* const* grads,
-                         int N, int C, int L, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * Incremental autoregressive sampling (models/base.py:97-120 runs H*W full forwards; the causal
@@ -698,8 +686,12 @@ int pg_gpt_out_head_bwd_rows(int N, int L, int grid_cap);
 int pg_gpt_out_head_bwd(const float* x, const float* ln_w, const float* ln_b, const float* conv_w, const float* dlogits,
                         float* dx, int N, int C, int Cout, int L, float eps, int grid_cap, float* workspace,
                         size_t workspace_floats, void* stream);
-/* pg_gpt_blocks_reduce (n_blocks 0..8, same arguments) and both ends in ONE launch. out_ws / stem_ws may be null (that end is
- * left out). out_grads: d ln.weight, d ln.bias, d conv.weight, d conv.bias; stem_grads: d weight, d bias, d pos. */
+/* ONE launch that adds partial rows to gradients: those of n_blocks (0..8) transformer blocks, as left by
+ * pg_gpt_block_head_bwd_partial (head_ws[b]) and pg_gpt_block_tail_bwd_partial (tail_ws[b]) for the same N, C, L, and those of
+ * either end. head_ws, tail_ws, grads, out_grads and stem_grads are HOST arrays of device pointers. grads: n_blocks x 14, per block
+ * dln1_w, dln1_b, dwq, dbq, dwkv, dbkv, then the tail's dw1, db1, dw2, db2, dwp, dbp, dln2_w, dln2_b. out_ws / stem_ws may be
+ * null (that end is left out; with n_blocks = 0 at least one must be given). out_grads: d ln.weight, d ln.bias, d conv.weight,
+ * d conv.bias; stem_grads: d weight, d bias, d pos. Everything is added to what the destinations hold. */
 int pg_gpt_model_reduce(int n_blocks, const float* const* head_ws, const float* const* tail_ws, float* const* grads, int N,
                         int C, int L, const float* out_ws, int out_rows, int Cout, float* const* out_grads,
                         const float* stem_ws, int stem_rows, int stem_slices, int H, int W, float* const* stem_grads,

@@ -1,6 +1,8 @@
 // gpt_block.hip — everything of an ImageGPT transformer block that is not the attention core, as two
-// forward and two backward kernels working on 16-pixel tiles held in registers (plus a fifth that runs
-// a block's tail and the next block's head forward in one launch).
+// forward and two backward kernels working on 16-pixel tiles held in registers, a fifth that runs
+// a block's tail and the next block's head forward in one launch, and the model's one segmented-reduce
+// kernel, which adds the rows of partial weight-gradient sums that the backward kernels here and in
+// gpt_ends.hip leave.
 //
 // Reference (models/autoregressive/image_gpt.py:21-52, :104-109), C = n_embedding_channels = 16:
 //   head:  qkv   = [W_q; W_kv] LN1(x) + [b_q; b_kv]                  (nn/attention.py:134-143)
@@ -18,7 +20,9 @@
 // Weight gradients contract over pixels: both operands go through per-wave LDS transposes (the loaded ones,
 // d qkv / d x_new / o, are written from the registers that already hold them instead of being read from
 // global memory a second time in transposed order); partial sums live in registers for all the
-// tiles of a wave, are reduced per workgroup in LDS and summed by a small second kernel (deterministic).
+// tiles of a wave, are reduced per workgroup in LDS to one row per workgroup, and seg_reduce_kernel adds the rows
+// (deterministic: a fixed order, the same whether a kernel's rows are reduced at once, alone, or later in a launch
+// shared with other blocks and the model's ends).
 // Backward recomputes x_mid, both LayerNorms and the hidden activations instead of storing them.
 // The tile loops are software-pipelined: a wave issues the global loads of its next tile before the
 // MFMA/VALU chain of the tile in hand and touches them after its stores (see prefetch_fence below).
@@ -644,113 +648,21 @@ __global__ void __launch_bounds__(GB_THREADS) tail_bwd_kernel(const BlockArgs a)
     prow[i] = (lds[i] + lds[T_PART + i]) + (lds[2 * T_PART + i] + lds[3 * T_PART + i]);
 }
 
-// ---- second stage: out_k[i] += sum_rows part[row][seg_k + i] for up to 8 gradient tensors
+// ---- second stage: the segmented reduce, the one kernel that turns rows of partial sums into gradients
+// A job is a [rows x stride] matrix of partial sums, one row per workgroup of the kernel that left it, and up to 8 destination
+// tensors that tile its columns: dst_k[i] += sum_rows part[row][begin_k + i]. Jobs are independent; a launch runs any mix of them.
 struct SegArgs {
   const float* part; int rows, stride, nseg;
   int end[8]; float* dst[8];
 };
-__global__ void __launch_bounds__(256) seg_reduce_kernel(const SegArgs a) {
-  __shared__ float red[32][9];
-  const int sl = threadIdx.x & 7, rg = threadIdx.x >> 3;
-  const int s = blockIdx.x * 8 + sl;
-  float a0 = 0.f, a1 = 0.f;
-  if (s < a.stride) {
-    const float* p = a.part + s;
-    int r = rg;
-    for (; r + 32 < a.rows; r += 64) {
-      a0 += p[(size_t)r * a.stride];
-      a1 += p[(size_t)(r + 32) * a.stride];
-    }
-    if (r < a.rows) a0 += p[(size_t)r * a.stride];
-  }
-  red[rg][sl] = a0 + a1;
-  __syncthreads();
-  if (rg != 0 || s >= a.stride) return;
-  float acc = 0.f;
-#pragma unroll
-  for (int r = 0; r < 32; ++r) acc += red[r][sl];
-  int begin = 0;
-  for (int k = 0; k < a.nseg; ++k) {
-    if (s < a.end[k]) { a.dst[k][s - begin] += acc; return; }
-    begin = a.end[k];
-  }
-}
-
-// Two segmented reductions in ONE launch (round 3): the tail and head kernels of a block each leave rows of
-// partial weight-gradient sums; at the reference's batch 64 the 16 reduce launches of a step were 6 % of it.
-struct SegArgs2 { SegArgs j[2]; int blocks0; };
-__global__ void __launch_bounds__(256) seg_reduce2_kernel(const SegArgs2 a2) {
-  __shared__ float red[32][9];
-  const bool second = (int)blockIdx.x >= a2.blocks0;
-  const SegArgs& a = a2.j[second ? 1 : 0];
-  const int blk = second ? blockIdx.x - a2.blocks0 : blockIdx.x;
-  const int sl = threadIdx.x & 7, rg = threadIdx.x >> 3;
-  const int s = blk * 8 + sl;
-  float a0 = 0.f, a1 = 0.f;
-  if (s < a.stride) {
-    const float* p = a.part + s;
-    int r = rg;
-    for (; r + 32 < a.rows; r += 64) {
-      a0 += p[(size_t)r * a.stride];
-      a1 += p[(size_t)(r + 32) * a.stride];
-    }
-    if (r < a.rows) a0 += p[(size_t)r * a.stride];
-  }
-  red[rg][sl] = a0 + a1;
-  __syncthreads();
-  if (rg != 0 || s >= a.stride) return;
-  float acc = 0.f;
-#pragma unroll
-  for (int r = 0; r < 32; ++r) acc += red[r][sl];
-  int begin = 0;
-  for (int k = 0; k < a.nseg; ++k) {
-    if (s < a.end[k]) { a.dst[k][s - begin] += acc; return; }
-    begin = a.end[k];
-  }
-}
-
-// Round 6: the reductions of up to 8 blocks (16 jobs) in ONE launch at the end of the backward pass — at the reference's batch 64 a
-// replayed step is ~83 launches of which ~45 run at the ~4.5 us floor of a graph kernel node; the eight per-block reduce launches
-// were 3.9 % of its kernel time (profiles/r05_image_gpt_b64_kernel_stats.csv).
-constexpr int SEG_MAX_JOBS = 16;
-struct SegArgsN { SegArgs j[SEG_MAX_JOBS]; int first[SEG_MAX_JOBS + 1]; int n; };
-__global__ void __launch_bounds__(256) seg_reduceN_kernel(const SegArgsN an) {
-  __shared__ float red[32][9];
-  int job = 0;
-  while (job + 1 < an.n && (int)blockIdx.x >= an.first[job + 1]) ++job;
-  const SegArgs& a = an.j[job];
-  const int blk = blockIdx.x - an.first[job];
-  const int sl = threadIdx.x & 7, rg = threadIdx.x >> 3;
-  const int s = blk * 8 + sl;
-  float a0 = 0.f, a1 = 0.f;
-  if (s < a.stride) {
-    const float* p = a.part + s;
-    int r = rg;
-    for (; r + 32 < a.rows; r += 64) {
-      a0 += p[(size_t)r * a.stride];
-      a1 += p[(size_t)(r + 32) * a.stride];
-    }
-    if (r < a.rows) a0 += p[(size_t)r * a.stride];
-  }
-  red[rg][sl] = a0 + a1;
-  __syncthreads();
-  if (rg != 0 || s >= a.stride) return;
-  float acc = 0.f;
-#pragma unroll
-  for (int r = 0; r < 32; ++r) acc += red[r][sl];
-  int begin = 0;
-  for (int k = 0; k < a.nseg; ++k) {
-    if (s < a.end[k]) { a.dst[k][s - begin] += acc; return; }
-    begin = a.end[k];
-  }
-}
-
-// The whole model's reductions in ONE launch: the rows of up to 8 blocks (16 jobs) and of the two ends (gpt_ends.hip): the output
-// head's rows, the stem's d weight / d bias rows, and the stem's d pos — the one job that is not a plain column sum: column q
-// gathers the position-wise sums G[tap][q - off(tap)] of the four active taps (gpt_ends.h, region B).
-constexpr int SEGM_MAX_JOBS = SEG_MAX_JOBS + 3;
-struct SegArgsM { SegArgs j[SEGM_MAX_JOBS]; int first[SEGM_MAX_JOBS + 1]; int n, pos_job, H, W; };
-__global__ void __launch_bounds__(256) seg_reduceM_kernel(const SegArgsM an) {
+// Up to 8 blocks (a head and a tail job each) and the model's two ends (gpt_ends.hip): the output head's rows, the stem's
+// d weight / d bias rows, and the stem's d pos — the one job that is not a plain column sum: column q gathers the position-wise
+// sums G[tap][q - off(tap)] of the four active taps (gpt_ends.h, region B). Job k owns workgroups first[k] .. first[k + 1] - 1,
+// eight columns each.
+constexpr int SEG_MAX_BLOCKS = 8;
+constexpr int SEG_MAX_JOBS = 2 * SEG_MAX_BLOCKS + 3;
+struct SegJobs { SegArgs j[SEG_MAX_JOBS]; int first[SEG_MAX_JOBS + 1]; int n, pos_job, H, W; };
+__global__ void __launch_bounds__(256) seg_reduce_kernel(const SegJobs an) {
   __shared__ float red[32][9];
   int job = 0;
   while (job + 1 < an.n && (int)blockIdx.x >= an.first[job + 1]) ++job;
@@ -799,6 +711,7 @@ __global__ void __launch_bounds__(256) seg_reduceM_kernel(const SegArgsM an) {
 // Workgroups per launch, at least `min_tiles` tiles per wave. which: 0 head fwd, 1 head bwd, 2 tail fwd, 3 tail bwd,
 // 4 tail + head fwd. Resident waves per SIMD by register count (75 / 126 / 125 / 248 / 164 VGPRs): 6 / 4 / 4 / 2 / 3; tail bwd
 // is also held at two workgroups per CU by its 76 KiB of LDS. PG_BLOCK_GRID="a,b,c,d[,e]" overrides the caps (tuning).
+// A backward kernel's workgroup count is also its number of partial rows (the *_bwd_workspace_floats and the reduce jobs use it).
 int grid_blocks(int which, int N, int L) {
   // immutable init-once tables (function-local static with an initialiser: thread-safe; the library
   // is entered from the main thread and from the autograd thread)
@@ -830,7 +743,6 @@ int grid_blocks(int which, int N, int L) {
   if (b > cap[which]) b = cap[which];
   return b < 1 ? 1 : (int)b;
 }
-int bwd_blocks(int N, int L) { return grid_blocks(3, N, L); }
 
 int check_shape(const char* who, int N, int Cc, int L) {
   PG_REQUIRE(N > 0 && L > 0, PG_EINVAL, "%s: non-positive dimension", who);
@@ -899,13 +811,27 @@ SegArgs head_seg_args(const float* workspace, int rows, float* dln_w, float* dln
   return r;
 }
 
-// defer != 0: the partial rows stay in `workspace` (pg_gpt_blocks_reduce adds them later); the gradient pointers are then unused
+// The one way to seg_reduce_kernel: jobs[0 .. n) in ONE launch, job k on (its columns + 7) / 8 workgroups behind those of
+// job k - 1. pos_job: the index of the stem's d pos job (over an H x W image), -1 without one.
+int seg_reduce(const SegArgs* jobs, int n, const char* who, hipStream_t st, int pos_job = -1, int H = 0, int W = 0) {
+  SegJobs an = {};
+  for (int k = 0; k < n; ++k) {
+    an.j[k] = jobs[k];
+    an.first[k + 1] = an.first[k] + (jobs[k].end[jobs[k].nseg - 1] + 7) / 8;
+  }
+  an.n = n; an.pos_job = pos_job; an.H = H; an.W = W;
+  hipLaunchKernelGGL(seg_reduce_kernel, dim3((unsigned)an.first[n]), dim3(256), 0, st, an);
+  PG_LAUNCH_CHECK(who);
+  return 0;
+}
+
+// reduce_now == false: the partial rows stay in `workspace` for pg_gpt_model_reduce; the six gradient pointers are then unused
 int head_bwd_impl(const float* x, const float* ln_w, const float* ln_b, const float* wq, const float* wkv,
                   const float* dqkv, const float* gx, float* dx, float* dln_w, float* dln_b, float* dwq,
                   float* dbq, float* dwkv, float* dbkv, int N, int Cc, int L, float eps, float* workspace,
-                  size_t workspace_floats, const SegArgs* tail, void* stream, int defer = 0) {
+                  size_t workspace_floats, bool reduce_now, void* stream) {
   PG_REQUIRE(x && ln_w && ln_b && wq && wkv && dqkv && gx && dx && workspace &&
-                 (defer || (dln_w && dln_b && dwq && dbq && dwkv && dbkv)), PG_EINVAL, "pg_gpt_block_head_bwd: null pointer");
+                 (!reduce_now || (dln_w && dln_b && dwq && dbq && dwkv && dbkv)), PG_EINVAL, "pg_gpt_block_head_bwd: null pointer");
   int rc = check_shape("pg_gpt_block_head_bwd", N, Cc, L);
   if (rc) return rc;
   PG_REQUIRE(workspace_floats >= pg_gpt_block_head_bwd_workspace_floats(N, L), PG_EINVAL,
@@ -920,17 +846,9 @@ int head_bwd_impl(const float* x, const float* ln_w, const float* ln_b, const fl
   const size_t tr = (size_t)4 * (C + QKV) * TS, rd = (size_t)4 * H_PART;
   hipLaunchKernelGGL(head_bwd_kernel, dim3((unsigned)blocks), dim3(GB_THREADS), (tr > rd ? tr : rd) * sizeof(float), st, a);
   PG_LAUNCH_CHECK("pg_gpt_block_head_bwd");
-  if (defer) return 0;
+  if (!reduce_now) return 0;
   const SegArgs r = head_seg_args(workspace, blocks, dln_w, dln_b, dwq, dbq, dwkv, dbkv);
-  if (tail) {  // one launch for this block's two reductions
-    SegArgs2 r2;
-    r2.j[0] = r; r2.j[1] = *tail; r2.blocks0 = (H_PART + 7) / 8;
-    hipLaunchKernelGGL(seg_reduce2_kernel, dim3((unsigned)(r2.blocks0 + (T_PART + 7) / 8)), dim3(256), 0, st, r2);
-  } else {
-    hipLaunchKernelGGL(seg_reduce_kernel, dim3((unsigned)((H_PART + 7) / 8)), dim3(256), 0, st, r);
-  }
-  PG_LAUNCH_CHECK("pg_gpt_block_head_bwd(reduce)");
-  return 0;
+  return seg_reduce(&r, 1, "pg_gpt_block_head_bwd(reduce)", st);
 }
 }  // namespace
 
@@ -940,84 +858,41 @@ PG_EXPORT int pg_gpt_block_head_bwd(const float* x, const float* ln_w, const flo
                                     float* dbkv, int N, int Cc, int L, float eps, float* workspace,
                                     size_t workspace_floats, void* stream) {
   return head_bwd_impl(x, ln_w, ln_b, wq, wkv, dqkv, gx, dx, dln_w, dln_b, dwq, dbq, dwkv, dbkv, N, Cc, L, eps,
-                       workspace, workspace_floats, nullptr, stream);
+                       workspace, workspace_floats, true, stream);
 }
 
-// head backward + the reduction a preceding pg_gpt_block_tail_bwd_partial of the SAME block left undone
-PG_EXPORT int pg_gpt_block_head_bwd_with_tail(const float* x, const float* ln_w, const float* ln_b, const float* wq,
-                                              const float* wkv, const float* dqkv, const float* gx, float* dx,
-                                              float* dln_w, float* dln_b, float* dwq, float* dbq, float* dwkv,
-                                              float* dbkv, int N, int Cc, int L, float eps, float* workspace,
-                                              size_t workspace_floats, const float* tail_workspace, float* t_dw1,
-                                              float* t_db1, float* t_dw2, float* t_db2, float* t_dwp, float* t_dbp,
-                                              float* t_dln_w, float* t_dln_b, void* stream) {
-  PG_REQUIRE(tail_workspace && t_dw1 && t_db1 && t_dw2 && t_db2 && t_dwp && t_dbp && t_dln_w && t_dln_b, PG_EINVAL,
-             "pg_gpt_block_head_bwd_with_tail: null pointer");
-  if (int rc = check_shape("pg_gpt_block_head_bwd_with_tail", N, Cc, L)) return rc;
-  const SegArgs tail = tail_seg_args(tail_workspace, bwd_blocks(N, L), t_dw1, t_db1, t_dw2, t_db2, t_dwp, t_dbp,
-                                     t_dln_w, t_dln_b);
-  return head_bwd_impl(x, ln_w, ln_b, wq, wkv, dqkv, gx, dx, dln_w, dln_b, dwq, dbq, dwkv, dbkv, N, Cc, L, eps,
-                       workspace, workspace_floats, &tail, stream);
-}
-
-// head backward WITHOUT its reduction: the partial rows stay in `workspace` for pg_gpt_blocks_reduce
+// the head kernel only: its rows of partial weight-gradient sums stay in `workspace` (which must stay alive) until
+// pg_gpt_model_reduce adds them
 PG_EXPORT int pg_gpt_block_head_bwd_partial(const float* x, const float* ln_w, const float* ln_b, const float* wq,
                                             const float* wkv, const float* dqkv, const float* gx, float* dx, int N, int Cc,
                                             int L, float eps, float* workspace, size_t workspace_floats, void* stream) {
   return head_bwd_impl(x, ln_w, ln_b, wq, wkv, dqkv, gx, dx, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, N, Cc, L,
-                       eps, workspace, workspace_floats, nullptr, stream, 1);
+                       eps, workspace, workspace_floats, false, stream);
 }
 
-// ONE launch for the weight-gradient reductions of n_blocks (<= 8) blocks whose head (pg_gpt_block_head_bwd_partial) and tail
-// (pg_gpt_block_tail_bwd_partial) kernels left their partial rows. grads: n_blocks x 14 destinations, per block in the order
-// dln1_w, dln1_b, dwq, dbq, dwkv, dbkv (head) | t_dw1, t_db1, t_dw2, t_db2, t_dwp, t_dbp, t_dln_w, t_dln_b (tail); added to.
-PG_EXPORT int pg_gpt_blocks_reduce(int n_blocks, const float* const* head_ws, const float* const* tail_ws, float* const* grads,
-                                   int N, int Cc, int L, void* stream) {
-  PG_REQUIRE(head_ws && tail_ws && grads, PG_EINVAL, "pg_gpt_blocks_reduce: null pointer");
-  PG_REQUIRE(n_blocks >= 1 && 2 * n_blocks <= SEG_MAX_JOBS, PG_ESHAPE, "pg_gpt_blocks_reduce: 1..8 blocks per launch, got %d", n_blocks);
-  if (int rc = check_shape("pg_gpt_blocks_reduce", N, Cc, L)) return rc;
-  SegArgsN an = {};
-  int nb = 0;
-  for (int b = 0; b < n_blocks; ++b) {
-    float* const* g = grads + 14 * b;
-    PG_REQUIRE(head_ws[b] && tail_ws[b], PG_EINVAL, "pg_gpt_blocks_reduce: null workspace of block %d", b);
-    for (int k = 0; k < 14; ++k) PG_REQUIRE(g[k], PG_EINVAL, "pg_gpt_blocks_reduce: null gradient %d of block %d", k, b);
-    an.j[2 * b] = head_seg_args(head_ws[b], grid_blocks(1, N, L), g[0], g[1], g[2], g[3], g[4], g[5]);
-    an.first[2 * b] = nb; nb += (H_PART + 7) / 8;
-    an.j[2 * b + 1] = tail_seg_args(tail_ws[b], bwd_blocks(N, L), g[6], g[7], g[8], g[9], g[10], g[11], g[12], g[13]);
-    an.first[2 * b + 1] = nb; nb += (T_PART + 7) / 8;
-  }
-  an.n = 2 * n_blocks;
-  an.first[an.n] = nb;
-  hipLaunchKernelGGL(seg_reduceN_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, an);
-  PG_LAUNCH_CHECK("pg_gpt_blocks_reduce");
-  return 0;
-}
-
-// pg_gpt_blocks_reduce plus the model's two ends: ONE launch adds the partial rows of n_blocks (0..8) blocks, of the output head
-// (out_ws: out_rows rows left by pg_gpt_out_head_bwd; out_grads = d ln.weight, d ln.bias, d conv.weight, d conv.bias) and of
-// the stem (stem_ws as left by pg_gpt_stem_bwd with stem_rows / stem_slices of pg_gpt_stem_bwd_plan; stem_grads = d weight
-// (16, 1, 3, 3), d bias, d pos (H x W)). A null out_ws / stem_ws leaves that end out. Everything is added to.
+// ONE launch adds the partial rows of n_blocks (0..8) blocks whose head (pg_gpt_block_head_bwd_partial) and tail
+// (pg_gpt_block_tail_bwd_partial) kernels left them, of the output head (out_ws: out_rows rows left by pg_gpt_out_head_bwd;
+// out_grads = d ln.weight, d ln.bias, d conv.weight, d conv.bias) and of the stem (stem_ws as left by pg_gpt_stem_bwd with
+// stem_rows / stem_slices of pg_gpt_stem_bwd_plan; stem_grads = d weight (16, 1, 3, 3), d bias, d pos (H x W)). grads: n_blocks x 14
+// destinations, per block in the order dln1_w, dln1_b, dwq, dbq, dwkv, dbkv (head) | t_dw1, t_db1, t_dw2, t_db2, t_dwp, t_dbp,
+// t_dln_w, t_dln_b (tail). A null out_ws / stem_ws leaves that end out. Everything is added to.
 PG_EXPORT int pg_gpt_model_reduce(int n_blocks, const float* const* head_ws, const float* const* tail_ws, float* const* grads,
                                   int N, int Cc, int L, const float* out_ws, int out_rows, int Cout, float* const* out_grads,
                                   const float* stem_ws, int stem_rows, int stem_slices, int H, int W,
                                   float* const* stem_grads, void* stream) {
-  PG_REQUIRE(n_blocks >= 0 && 2 * n_blocks <= SEG_MAX_JOBS, PG_ESHAPE, "pg_gpt_model_reduce: 0..8 blocks per launch, got %d", n_blocks);
+  PG_REQUIRE(n_blocks >= 0 && n_blocks <= SEG_MAX_BLOCKS, PG_ESHAPE, "pg_gpt_model_reduce: 0..8 blocks per launch, got %d", n_blocks);
   PG_REQUIRE(n_blocks == 0 || (head_ws && tail_ws && grads), PG_EINVAL, "pg_gpt_model_reduce: null pointer");
   PG_REQUIRE(n_blocks > 0 || out_ws || stem_ws, PG_EINVAL, "pg_gpt_model_reduce: nothing to reduce");
   if (n_blocks > 0)
     if (int rc = check_shape("pg_gpt_model_reduce", N, Cc, L)) return rc;
-  SegArgsM an = {};
-  an.pos_job = -1;
-  int nb = 0, nj = 0;
+  SegArgs jobs[SEG_MAX_JOBS];
+  int nj = 0, pos_job = -1;
   for (int b = 0; b < n_blocks; ++b) {
     float* const* g = grads + 14 * b;
     PG_REQUIRE(head_ws[b] && tail_ws[b], PG_EINVAL, "pg_gpt_model_reduce: null workspace of block %d", b);
     for (int k = 0; k < 14; ++k) PG_REQUIRE(g[k], PG_EINVAL, "pg_gpt_model_reduce: null gradient %d of block %d", k, b);
-    an.j[nj] = head_seg_args(head_ws[b], grid_blocks(1, N, L), g[0], g[1], g[2], g[3], g[4], g[5]);
-    an.first[nj++] = nb; nb += (H_PART + 7) / 8;
-    an.j[nj] = tail_seg_args(tail_ws[b], bwd_blocks(N, L), g[6], g[7], g[8], g[9], g[10], g[11], g[12], g[13]);
-    an.first[nj++] = nb; nb += (T_PART + 7) / 8;
+    jobs[nj++] = head_seg_args(head_ws[b], grid_blocks(1, N, L), g[0], g[1], g[2], g[3], g[4], g[5]);
+    jobs[nj++] = tail_seg_args(tail_ws[b], grid_blocks(3, N, L), g[6], g[7], g[8], g[9], g[10], g[11], g[12], g[13]);
   }
   if (out_ws) {
     PG_REQUIRE(out_rows >= 1 && Cout >= 1 && Cout <= pg_ends::MAX_COUT && out_grads && out_grads[0] && out_grads[1] &&
@@ -1028,8 +903,7 @@ PG_EXPORT int pg_gpt_model_reduce(int n_blocks, const float* const* head_ws, con
     r.end[1] = pg_ends::O_W; r.dst[1] = out_grads[1];
     r.end[2] = pg_ends::O_W + Cout * pg_ends::C; r.dst[2] = out_grads[2];
     r.end[3] = r.stride; r.dst[3] = out_grads[3];
-    an.j[nj] = r;
-    an.first[nj++] = nb; nb += (r.stride + 7) / 8;
+    jobs[nj++] = r;
   }
   if (stem_ws) {
     PG_REQUIRE(stem_rows >= 1 && stem_slices >= 1 && H >= 1 && W >= 1 && stem_grads && stem_grads[0] && stem_grads[1] &&
@@ -1038,20 +912,14 @@ PG_EXPORT int pg_gpt_model_reduce(int n_blocks, const float* const* head_ws, con
     r.part = stem_ws; r.rows = stem_rows; r.stride = pg_ends::S_PART; r.nseg = 2;
     r.end[0] = pg_ends::S_B; r.dst[0] = stem_grads[0];
     r.end[1] = pg_ends::S_PART; r.dst[1] = stem_grads[1];
-    an.j[nj] = r;
-    an.first[nj++] = nb; nb += (pg_ends::S_PART + 7) / 8;
-    SegArgs q = {};
+    jobs[nj++] = r;
+    SegArgs q = {};  // d pos: H x W columns gathered from ACTIVE x H x W position-wise sums per slice
     q.part = stem_ws + (size_t)stem_rows * pg_ends::S_PART; q.rows = stem_slices; q.stride = pg_ends::ACTIVE * H * W; q.nseg = 1;
     q.end[0] = H * W; q.dst[0] = stem_grads[2];
-    an.pos_job = nj; an.H = H; an.W = W;
-    an.j[nj] = q;
-    an.first[nj++] = nb; nb += (H * W + 7) / 8;
+    pos_job = nj;
+    jobs[nj++] = q;
   }
-  an.n = nj;
-  an.first[nj] = nb;
-  hipLaunchKernelGGL(seg_reduceM_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, an);
-  PG_LAUNCH_CHECK("pg_gpt_model_reduce");
-  return 0;
+  return seg_reduce(jobs, nj, "pg_gpt_model_reduce", (hipStream_t)stream, pos_job, H, W);
 }
 
 PG_EXPORT int pg_gpt_block_tail_fwd(const float* o, const float* x, const float* wp, const float* bp,
@@ -1103,8 +971,8 @@ int tail_bwd_impl(const float* o, const float* x, const float* wp, const float* 
                                     float* dwp, float* dbp, float* dln_w, float* dln_b, float* dw1,
                                     float* db1, float* dw2, float* db2, int N, int Cc, int Hd, int L,
                                     float eps, float* workspace, size_t workspace_floats, bool reduce_now, void* stream) {
-  PG_REQUIRE(o && x && wp && bp && ln_w && ln_b && w1 && b1 && w2 && dx_new && d_o && gx && dwp && dbp &&
-                 dln_w && dln_b && dw1 && db1 && dw2 && db2 && workspace, PG_EINVAL,
+  PG_REQUIRE(o && x && wp && bp && ln_w && ln_b && w1 && b1 && w2 && dx_new && d_o && gx && workspace &&
+                 (!reduce_now || (dwp && dbp && dln_w && dln_b && dw1 && db1 && dw2 && db2)), PG_EINVAL,
              "pg_gpt_block_tail_bwd: null pointer");
   int rc = check_shape("pg_gpt_block_tail_bwd", N, Cc, L);
   if (rc) return rc;
@@ -1116,7 +984,7 @@ int tail_bwd_impl(const float* o, const float* x, const float* wp, const float* 
   a.o = o; a.x = x; a.wp = wp; a.bp = bp; a.g2 = ln_w; a.be2 = ln_b; a.w1 = w1; a.b1 = b1; a.w2 = w2;
   a.dxnew = dx_new; a.d_o = d_o; a.gx_out = gx; a.part = workspace;
   set_geometry(a, N, L, eps);
-  const int blocks = bwd_blocks(N, L);
+  const int blocks = grid_blocks(3, N, L);
   hipStream_t st = (hipStream_t)stream;
   const size_t tr = (size_t)4 * TB_WAVE_ROWS * TS + 64 * 64, rd = (size_t)4 * T_PART;
   const size_t shmem = (tr > rd ? tr : rd) * sizeof(float);  // 76 KiB: above the 64 KB default, two workgroups per CU (160 KB)
@@ -1125,11 +993,9 @@ int tail_bwd_impl(const float* o, const float* x, const float* wp, const float* 
   (void)attr;  // thread-safe one-time opt-in
   hipLaunchKernelGGL(tail_bwd_kernel, dim3((unsigned)blocks), dim3(GB_THREADS), shmem, st, a);
   PG_LAUNCH_CHECK("pg_gpt_block_tail_bwd");
-  if (!reduce_now) return 0;  // the partial rows stay in `workspace` for pg_gpt_block_head_bwd_with_tail
+  if (!reduce_now) return 0;
   const SegArgs r = tail_seg_args(workspace, blocks, dw1, db1, dw2, db2, dwp, dbp, dln_w, dln_b);
-  hipLaunchKernelGGL(seg_reduce_kernel, dim3((unsigned)((T_PART + 7) / 8)), dim3(256), 0, st, r);
-  PG_LAUNCH_CHECK("pg_gpt_block_tail_bwd(reduce)");
-  return 0;
+  return seg_reduce(&r, 1, "pg_gpt_block_tail_bwd(reduce)", st);
 }
 }  // namespace
 
@@ -1144,13 +1010,12 @@ PG_EXPORT int pg_gpt_block_tail_bwd(const float* o, const float* x, const float*
 }
 
 // the tail kernel only: its rows of partial weight-gradient sums stay in `workspace` (which must stay alive) until
-// pg_gpt_block_head_bwd_with_tail of the same block reduces them together with its own
+// pg_gpt_model_reduce adds them
 PG_EXPORT int pg_gpt_block_tail_bwd_partial(const float* o, const float* x, const float* wp, const float* bp,
                                             const float* ln_w, const float* ln_b, const float* w1, const float* b1,
                                             const float* w2, const float* dx_new, float* d_o, float* gx, int N,
                                             int Cc, int Hd, int L, float eps, float* workspace,
                                             size_t workspace_floats, void* stream) {
-  float* dummy = workspace;  // the gradient destinations are not touched without the reduction
-  return tail_bwd_impl(o, x, wp, bp, ln_w, ln_b, w1, b1, w2, dx_new, d_o, gx, dummy, dummy, dummy, dummy, dummy, dummy,
-                       dummy, dummy, N, Cc, Hd, L, eps, workspace, workspace_floats, false, stream);
+  return tail_bwd_impl(o, x, wp, bp, ln_w, ln_b, w1, b1, w2, dx_new, d_o, gx, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                       nullptr, nullptr, N, Cc, Hd, L, eps, workspace, workspace_floats, false, stream);
 }

@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # HIP library, still loaded or the import fails; the default is the production library
 LIB_PATH = os.environ.get("PG_HIP_LIB") or os.path.join(_HERE, "lib", "libpg_hip.so")
 
-ABI_VERSION = 2
+ABI_VERSION = 3
 
 c_f = ctypes.c_void_p  # device float* (passed as integer address)
 c_i = ctypes.c_int
@@ -67,8 +67,6 @@ SIGNATURES = {
     "pg_gpt_block_head_bwd": (c_i, [c_f] * 14 + [c_i, c_i, c_i, c_flt, c_f, c_z, c_s]),
     "pg_gpt_block_head_bwd_workspace_floats": (c_z, [c_i, c_i]),
     "pg_gpt_block_head_bwd_partial": (c_i, [c_f] * 8 + [c_i, c_i, c_i, c_flt, c_f, c_z, c_s]),
-    "pg_gpt_blocks_reduce": (c_i, [c_i, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p),
-                                   ctypes.POINTER(ctypes.c_void_p), c_i, c_i, c_i, c_s]),
     "pg_gpt_stem_fwd": (c_i, [c_f] * 5 + [c_i, c_i, c_i, c_i, c_s]),
     "pg_gpt_stem_bwd_plan": (c_i, [c_i, c_i, c_i, c_i, c_ip, c_ip]),
     "pg_gpt_stem_bwd_workspace_floats": (c_z, [c_i, c_i, c_i, c_i]),
@@ -85,7 +83,6 @@ SIGNATURES = {
     "pg_gpt_block_tail_bwd": (c_i, [c_f] * 20 + [c_i, c_i, c_i, c_i, c_flt, c_f, c_z, c_s]),
     "pg_gpt_block_tail_bwd_workspace_floats": (c_z, [c_i, c_i]),
     "pg_gpt_block_tail_bwd_partial": (c_i, [c_f] * 12 + [c_i, c_i, c_i, c_i, c_flt, c_f, c_z, c_s]),
-    "pg_gpt_block_head_bwd_with_tail": (c_i, [c_f] * 14 + [c_i, c_i, c_i, c_flt, c_f, c_z] + [c_f] * 9 + [c_s]),
     "pg_sample_embed": (c_i, [c_f] * 5 + [c_i] * 10 + [c_f, c_s]),
     "pg_attn_decode": (c_i, [c_f] * 4 + [c_i] * 8 + [c_f, c_s]),
     "pg_mlp_gelu_fwd": (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_s]),

@@ -7,8 +7,6 @@ NCHW LayerNorm, 1x1 convs (residual adds fused into the projection / MLP-out ker
 GELU, and the fused causal attention core.
 """
 
-import os
-
 import torch
 from torch import nn
 
@@ -16,9 +14,6 @@ from pytorch_generative_amd import _lib
 from pytorch_generative_amd import nn as pg_nn
 from pytorch_generative_amd import ops
 from pytorch_generative_amd.models import base
-
-# A/B (measurement only): 0 = one weight-gradient reduction launch per block instead of one per model (round 6)
-_BLOCK_CHAIN = os.environ.get("PG_BLOCK_CHAIN", "1") != "0"
 
 
 class TransformerBlock(nn.Module):
@@ -45,7 +40,7 @@ class TransformerBlock(nn.Module):
     def forward_plus_input(self, x, chain=None, flush=False, boundary=None, next_block=None):
         """x + self(x) — what the model loop computes (reference image_gpt.py:107) — on the fused
         head / attention / tail kernels (gpt_block.hip) when the block has the BASELINE shape.
-        chain / flush (round 6): a queue shared by all blocks of the model, flushed by the block whose backward runs last —
+        chain / flush: a queue shared by all blocks of the model, flushed by the block whose backward runs last —
         the weight-gradient rows of all blocks are then reduced by ONE launch (ops.gpt_block_head).
         boundary / next_block: a dict shared by the blocks of one forward and the block that runs next (fused shape as well) —
         this block's tail launch then also computes that block's LN1 and q/kv projection (ops.gpt_block_tail)."""
@@ -219,8 +214,7 @@ class ImageGPT(base.AutoregressiveModel):
         # FIRST block flushes (its backward runs last among the blocks); it queues only on its all-sinks path, so the chain is
         # then declined unless every block parameter has a sink.
         chain = None
-        if (ops.DEFER_BLOCK_REDUCE and _BLOCK_CHAIN and grad and x0_grad and len(blocks) > 1
-                and all(b._fused_ok(probe) for b in blocks)
+        if (grad and x0_grad and len(blocks) > 1 and all(b._fused_ok(probe) for b in blocks)
                 and (stem_flushes or all(ops._sink(p) is not None for b in blocks for p in b.parameters()))):
             chain = ops.new_block_chain()
         if fuse_stem:

@@ -86,11 +86,10 @@ from pytorch_generative_amd.ops.gpt_block import (  # noqa: F401
     _MlpGelu,
     mlp_gelu,
     FUSE_BLOCK,
-    DEFER_BLOCK_REDUCE,
     _grad_targets,
     new_block_chain,
     assert_no_pending_block_reductions,
-    flush_block_reductions,
+    reduce_rows,
     _GPTBlockHead,
     _GPTBlockTail,
     gpt_block_supported,
@@ -102,8 +101,6 @@ from pytorch_generative_amd.ops.gpt_block import (  # noqa: F401
 )
 from pytorch_generative_amd.ops.gpt_ends import (  # noqa: F401
     FUSE_ENDS,
-    model_reduce,
-    flush_model_reductions,
     gpt_stem_supported,
     _GPTStem,
     gpt_stem,

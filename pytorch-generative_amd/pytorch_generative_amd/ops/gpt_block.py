@@ -3,6 +3,7 @@
 Part of the operator layer (pytorch_generative_amd.ops): HIP kernels behind torch.autograd.Function, called through the C-ABI
 with tensor.data_ptr() and the current stream. No CPU / ATen fallback: a missing library, a CPU tensor or an unsupported shape raises."""
 
+import ctypes
 import os
 
 import torch
@@ -87,7 +88,6 @@ def mlp_gelu(x, conv1, conv2, res=None):
 # ImageGPT transformer block minus the attention core: fused head / tail (gpt_block.hip)
 # --------------------------------------------------------------------------------------------
 FUSE_BLOCK = os.environ.get("PG_FUSE_BLOCK", "1") != "0"
-DEFER_BLOCK_REDUCE = os.environ.get("PG_BLOCK_REDUCE_MERGED", "1") != "0"  # A/B: 0 = two reduce launches per block
 # A/B: 0 = tail(i) and head(i+1) as two forward launches instead of pg_gpt_block_tail_head_fwd (read by ImageGPT.forward per call)
 FUSE_BOUNDARY = os.environ.get("PG_FUSE_BOUNDARY", "1") != "0"
 
@@ -131,22 +131,32 @@ def assert_no_pending_block_reductions():
         c = r()
         if c is not None and (c["jobs"] or c.get("out") is not None):
             raise RuntimeError(f"{len(c['jobs']) + (c.get('out') is not None)} deferred ImageGPT weight-gradient reductions were "
-                               "never flushed: the backward that flushes them (the stem's, else the first block's) did not run "
-                               "(set PG_BLOCK_REDUCE_MERGED=0 to reduce per block)")
+                               "never flushed: the backward that flushes them (the stem's, else the first block's) did not run")
 
 
-def flush_block_reductions(chain, n, c, L):
-    """Adds the partial weight-gradient rows of every block queued in `chain` (8 blocks per launch) and empties the queue."""
-    import ctypes
+def _ptrs(tensors):
+    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
 
+
+def reduce_rows(jobs, n, c, L, out=None, stem=None):
+    """Adds partial weight-gradient rows to their destinations (pg_gpt_model_reduce): those of the blocks in `jobs` (as
+    _GPTBlockHead.backward queues them), 8 blocks per launch, and those of the model's ends, which ride with the last launch
+    (the only one when there are no blocks): out = (workspace, rows, Cout, 4 destinations), stem = (workspace, rows, slices, H, W,
+    3 destinations). Empties `jobs`."""
+    if not jobs and out is None and stem is None:
+        return
     lib = _lib.load()
-    jobs = chain["jobs"]
-    for i in range(0, len(jobs), 8):
-        grp = jobs[i:i + 8]
-        hw = (ctypes.c_void_p * len(grp))(*[j[0].data_ptr() for j in grp])
-        tw = (ctypes.c_void_p * len(grp))(*[j[1].data_ptr() for j in grp])
-        gr = (ctypes.c_void_p * (14 * len(grp)))(*[ptr for j in grp for ptr in j[2]])
-        _lib.check(lib.pg_gpt_blocks_reduce(len(grp), hw, tw, gr, n, c, L, _stream()), "pg_gpt_blocks_reduce")
+    no_out, no_stem = (0, 0, 0, None), (0, 0, 0, 0, 0, None)
+    out_args = no_out if out is None else (out[0].data_ptr(), out[1], out[2], _ptrs(out[3]))
+    stem_args = no_stem if stem is None else (stem[0].data_ptr(), *stem[1:5], _ptrs(stem[5]))
+    groups = [jobs[i:i + 8] for i in range(0, len(jobs), 8)] or [[]]
+    for grp in groups:
+        last = grp is groups[-1]
+        hw = _ptrs([j[0] for j in grp]) if grp else None
+        tw = _ptrs([j[1] for j in grp]) if grp else None
+        gr = (ctypes.c_void_p * (14 * len(grp)))(*[ptr for j in grp for ptr in j[2]]) if grp else None
+        _lib.check(lib.pg_gpt_model_reduce(len(grp), hw, tw, gr, n, c, L, *(out_args if last else no_out),
+                                           *(stem_args if last else no_stem), _stream()), "pg_gpt_model_reduce")
     jobs.clear()
 
 
@@ -198,7 +208,7 @@ class _GPTBlockHead(torch.autograd.Function):
         flusher = chain is not None and bool(ctx.pair.get("flush"))
         if dqkv is None:
             if flusher and chain["jobs"]:  # the other blocks' rows must not wait for a path this backward does not take
-                flush_block_reductions(chain, n, c, h * w)
+                reduce_rows(chain["jobs"], n, c, h * w)
             if pending is not None:
                 raise RuntimeError("gpt_block_head: a deferred tail reduction is pending but the head has no gradient")
             return gx, None, None, None, None, None, None, None, None, None
@@ -209,36 +219,28 @@ class _GPTBlockHead(torch.autograd.Function):
         ws_n = lib.pg_gpt_block_head_bwd_workspace_floats(n, h * w)
         ws = torch.empty(ws_n, device=x.device, dtype=torch.float32)
         head_args = (x.data_ptr(), lnw.data_ptr(), lnb.data_ptr(), wq.data_ptr(),
-                     wkv.data_ptr(), dqkv.data_ptr(), gx.data_ptr(), dx.data_ptr(),
-                     tgt[0].data_ptr(), tgt[1].data_ptr(), tgt[2].data_ptr(),
-                     tgt[3].data_ptr(), tgt[4].data_ptr(), tgt[5].data_ptr(), n, c,
-                     h * w, ctx.eps, ws.data_ptr(), ws_n)
-        if pending is not None and chain is not None and all(r is None for r in ret):
-            # round 6: a model-level chain of blocks (ImageGPT passes one list to all of its blocks): this block's head kernel
-            # leaves its partial rows as well, and the LAST block to run backward (the model's first) adds the rows of every
-            # block with ONE launch (pg_gpt_blocks_reduce) instead of one reduce launch per block
-            t_ws, t = pending
-            _lib.check(lib.pg_gpt_block_head_bwd_partial(*head_args[:8], *head_args[14:], _stream()),
-                       "pg_gpt_block_head_bwd_partial")
-            # 14 destinations in the C-ABI's order: head lnw, lnb, wq, bq, wkv, bkv | tail w1, b1, w2, b2, wp, bp, lnw, lnb
-            chain["jobs"].append((ws, t_ws, [g.data_ptr() for g in tgt] + [t[4].data_ptr(), t[5].data_ptr(), t[6].data_ptr(),
-                                                                          t[7].data_ptr(), t[0].data_ptr(), t[1].data_ptr(),
-                                                                          t[2].data_ptr(), t[3].data_ptr()], (tgt, t)))
-            if flusher:
-                flush_block_reductions(chain, n, c, h * w)
+                     wkv.data_ptr(), dqkv.data_ptr(), gx.data_ptr(), dx.data_ptr())
+        geometry = (n, c, h * w, ctx.eps, ws.data_ptr(), ws_n, _stream())
+        queue = pending is not None and chain is not None and all(r is None for r in ret)
+        if flusher and chain["jobs"] and not queue:  # this block reduces its own rows (a parameter without a sink): still flush the others'
+            reduce_rows(chain["jobs"], n, c, h * w)
+        if pending is None:
+            _lib.check(lib.pg_gpt_block_head_bwd(*head_args, *(g.data_ptr() for g in tgt), *geometry), "pg_gpt_block_head_bwd")
             return (dx, *ret, None, None, None)
-        if flusher and chain["jobs"]:  # this block reduces its own rows (a parameter without a sink): still flush the others'
-            flush_block_reductions(chain, n, c, h * w)
-        if pending is not None:  # this block's tail kernel left its partial rows: ONE reduce launch for both
-            t_ws, t = pending    # t order: wp, bp, lnw, lnb, w1, b1, w2, b2
-            _lib.check(
-                lib.pg_gpt_block_head_bwd_with_tail(*head_args, t_ws.data_ptr(), t[4].data_ptr(), t[5].data_ptr(),
-                                                    t[6].data_ptr(), t[7].data_ptr(), t[0].data_ptr(),
-                                                    t[1].data_ptr(), t[2].data_ptr(), t[3].data_ptr(), _stream()),
-                "pg_gpt_block_head_bwd_with_tail",
-            )
+        # this block's tail kernel left its partial rows: the head kernel leaves its own as well, and both are one job. On a
+        # model-level chain of blocks (ImageGPT passes one to all of its blocks) whose every head parameter has a sink the job
+        # waits for the LAST backward of the model, which adds the rows of every block with one launch per 8 blocks; otherwise
+        # it is reduced at once, one launch for the block
+        t_ws, t = pending  # t order: wp, bp, lnw, lnb, w1, b1, w2, b2
+        _lib.check(lib.pg_gpt_block_head_bwd_partial(*head_args, *geometry), "pg_gpt_block_head_bwd_partial")
+        # 14 destinations in the C-ABI's order: head lnw, lnb, wq, bq, wkv, bkv | tail w1, b1, w2, b2, wp, bp, lnw, lnb
+        job = (ws, t_ws, [g.data_ptr() for g in tgt + t[4:] + t[:4]], (tgt, t))
+        if not queue:
+            reduce_rows([job], n, c, h * w)
         else:
-            _lib.check(lib.pg_gpt_block_head_bwd(*head_args, _stream()), "pg_gpt_block_head_bwd")
+            chain["jobs"].append(job)
+            if flusher:
+                reduce_rows(chain["jobs"], n, c, h * w)
         return (dx, *ret, None, None, None)
 
 
@@ -292,9 +294,9 @@ class _GPTBlockTail(torch.autograd.Function):
         tgt, ret = _grad_targets(ctx.params)  # order: wp, bp, lnw, lnb, w1, b1, w2, b2
         ws_n = lib.pg_gpt_block_tail_bwd_workspace_floats(n, h * w)
         ws = torch.empty(ws_n, device=x.device, dtype=torch.float32)
-        if ctx.pair is not None and DEFER_BLOCK_REDUCE and all(r is None for r in ret):
+        if ctx.pair is not None and all(r is None for r in ret):
             # every gradient goes into a sink (FlatAdam): leave the partial rows for the head's backward of the
-            # same block, which reduces both kernels' rows in one launch
+            # same block, which reduces both kernels' rows in one launch or queues them for the model's
             _lib.check(
                 lib.pg_gpt_block_tail_bwd_partial(o.data_ptr(), x.data_ptr(), wp.data_ptr(), bp.data_ptr(),
                                                   lnw.data_ptr(), lnb.data_ptr(), w1.data_ptr(), b1.data_ptr(),
@@ -333,7 +335,7 @@ def gpt_block_supported(x, ln1, q, kv, proj, ln2, fc1, fc2):
 
 def gpt_block_head(x, ln1, q, kv, pair=None):
     """pair: a dict shared with gpt_block_tail of the SAME block (one per forward): lets the two backward
-    kernels share one weight-gradient reduction launch. pair["chain"] = {"jobs": []} shared by ALL blocks of a model and
+    kernels share one weight-gradient reduction launch. pair["chain"] = ops.new_block_chain() shared by ALL blocks of a model and
     pair["flush"] = True on the block whose backward runs last (the model's first block): one reduction launch per 8 blocks."""
     params = (ln1.weight, ln1.bias, q.weight, q.bias, kv.weight, kv.bias)
     return _GPTBlockHead.apply(x, *params, float(ln1.eps), params, pair)

@@ -11,50 +11,15 @@ import torch
 
 from pytorch_generative_amd import _lib
 from pytorch_generative_amd.ops._common import RowDecode, _chk, _stream
-from pytorch_generative_amd.ops.gpt_block import _grad_targets
+from pytorch_generative_amd.ops.gpt_block import _grad_targets, reduce_rows
 
 FUSE_ENDS = os.environ.get("PG_FUSE_ENDS", "1") != "0"  # A/B: 0 = the generic operators (add, mask, conv_taps, LayerNorm, 1x1)
 MAX_OUT_CHANNELS = 4  # csrc/gpt_ends.h MAX_COUT
 
 
-def _ptrs(tensors):
-    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
-
-
-def model_reduce(jobs, n, c, L, out=None, stem=None):
-    """ONE launch (pg_gpt_model_reduce) that adds the partial weight-gradient rows of up to 8 queued blocks (`jobs`, as
-    gpt_block_head queues them) and of the model's ends: out = (workspace, rows, Cout, 4 destinations),
-    stem = (workspace, rows, slices, H, W, 3 destinations)."""
-    lib = _lib.load()
-    assert len(jobs) <= 8
-    hw = _ptrs([j[0] for j in jobs]) if jobs else None
-    tw = _ptrs([j[1] for j in jobs]) if jobs else None
-    gr = (ctypes.c_void_p * (14 * len(jobs)))(*[ptr for j in jobs for ptr in j[2]]) if jobs else None
-    o_ws, o_rows, o_cout, o_tgt = out if out is not None else (None, 0, 0, None)
-    s_ws, s_rows, s_slices, h, w, s_tgt = stem if stem is not None else (None, 0, 0, 0, 0, None)
-    _lib.check(
-        lib.pg_gpt_model_reduce(len(jobs), hw, tw, gr, n, c, L,
-                                0 if o_ws is None else o_ws.data_ptr(), o_rows, o_cout, None if o_tgt is None else _ptrs(o_tgt),
-                                0 if s_ws is None else s_ws.data_ptr(), s_rows, s_slices, h, w,
-                                None if s_tgt is None else _ptrs(s_tgt), _stream()),
-        "pg_gpt_model_reduce",
-    )
-
-
-def flush_model_reductions(chain, n, c, L, stem=None):
-    """Empties `chain`: the queued blocks, the output head's rows if its backward parked them, and the caller's stem rows —
-    one launch for up to 8 blocks and both ends (more blocks: 8 per additional launch)."""
-    from pytorch_generative_amd.ops.gpt_block import flush_block_reductions
-
-    jobs = chain["jobs"]
-    out = chain.pop("out", None)
-    last = jobs[max(0, len(jobs) - 8):] if jobs else []
-    if len(jobs) > 8:
-        del jobs[len(jobs) - 8:]
-        flush_block_reductions(chain, n, c, L)
-    if last or out is not None or stem is not None:
-        model_reduce(last, n, c, L, out=out, stem=stem)
-    jobs.clear()
+def _flush(chain, n, c, L, stem=None):
+    """Empties `chain`: the queued blocks, the output head's rows if its backward parked them, and the caller's stem rows."""
+    reduce_rows(chain["jobs"], n, c, L, out=chain.pop("out", None), stem=stem)
 
 
 # --------------------------------------------------------------------------------------------
@@ -110,12 +75,12 @@ class _GPTStem(torch.autograd.Function):
             stem = (ws, rows.value, slices.value, h, w, [tgt[1], tgt[2], tgt[0]])
         except BaseException:
             if chain is not None:  # whatever was queued still reaches its destinations
-                flush_model_reductions(chain, n, 16, h * w)
+                _flush(chain, n, 16, h * w)
             raise
         if chain is not None:
-            flush_model_reductions(chain, n, 16, h * w, stem=stem)
+            _flush(chain, n, 16, h * w, stem=stem)
         else:
-            model_reduce([], n, 16, h * w, stem=stem)
+            reduce_rows([], n, 16, h * w, stem=stem)
         return None, ret[0], ret[1], ret[2], None, None, None
 
 
@@ -174,7 +139,7 @@ class _GPTOutHead(torch.autograd.Function):
         if ctx.chain is not None and all(r is None for r in ret):
             ctx.chain["out"] = out  # the stem's backward adds these rows in the step's one reduce launch
         else:
-            model_reduce([], n, c, L, out=out)
+            reduce_rows([], n, c, L, out=out)
         return dx, ret[0], ret[1], ret[2], ret[3], None, None, None, None
 
 

@@ -687,7 +687,7 @@ def test_ops_package_reexports_every_operator_name():
                  "add", "add_broadcast_batch", "relu", "elu", "gelu", "merge_qkv_weight", "new_block_chain",
                  "_use_mfma", "_pack_frag", "_adjacent_view", "_Act", "_ACT_IDS", "_sink", "_chk", "_dense_per_image",
                  "ACT_NONE", "ACT_RELU", "ACT_ELU", "ACT_GELU", "ACT_ELU_OUT", "GATE_TANH", "GATE_IDENTITY",
-                 "CONV_FMT_B3", "FUSE_SKIP", "FUSE_PAIR", "FUSE_BLOCK", "DEFER_BLOCK_REDUCE"):
+                 "CONV_FMT_B3", "FUSE_SKIP", "FUSE_PAIR", "FUSE_BLOCK"):
         assert hasattr(ops, name), name
     assert ops.conv2d_taps.__module__ == "pytorch_generative_amd.ops.conv"
     assert ops.causal_attention.__module__ == "pytorch_generative_amd.ops.attention"

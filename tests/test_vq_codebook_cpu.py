@@ -61,7 +61,7 @@ def test_cpu_tensor_raises(use_ema):
 def test_entry_points_reject_bad_arguments(lib):
     from pytorch_generative_amd import _lib
 
-    assert lib.pg_abi_version() == _lib.ABI_VERSION == 2
+    assert lib.pg_abi_version() == _lib.ABI_VERSION == 3
     big = 1 << 40
     bad = [(0, 8, 4, 4), (2, 0, 4, 4), (2, 8, 0, 4), (2, 8, 4, 0), (-1, 8, 4, 4), (2, 8, 4, -3),
            (2, (1 << 20) + 1, 4, 4), (2, 8, 4, 65535 * 64 + 1), (1 << 16, 8, 1 << 15, 4), (1, 1 << 16, 1, 1 << 15)]
