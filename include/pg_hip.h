@@ -697,6 +697,33 @@ int pg_gpt_model_reduce(int n_blocks, const float* const* head_ws, const float* 
                         const float* stem_ws, int stem_rows, int stem_slices, int H, int W, float* const* stem_grads,
                         void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Categorical (K-way softmax) pixel likelihood, categorical.hip: the likelihood PixelCNN, GatedPixelCNN, PixelSNAIL and
+ * ImageGPT were published with. logits (N, K C, H, W) dense, read as (N, K, C, HW): class-major, the layout
+ * F.cross_entropy takes as logits.view(N, K, C, H, W). x: images (N, C, HW) at the levels j / (K - 1); the class of a
+ * sub-pixel is t = clamp((int)rintf(x (K - 1)), 0, K - 1).
+ *   fwd:    lse (2, N, C, HW): plane 0 is lse[n, c, p] = logsumexp_k z as max + log(sum exp(z - max)), plane 1 the fp32
+ *           rounding residual of that last addition (the backward needs the normaliser to better than one ulp of a large
+ *           lse); loss[0] += (1 / N) sum (lse - z_t) (nats; zeroed by the caller; fp32 atomics in arrival order, as
+ *           pg_bce_logits_fwd); per_sample (N) or NULL: sum over the image's sub-pixels of lse - z_t, in a fixed order.
+ *   bwd:    dlogits = g[0] / N * (exp(z - lse) - [k == t]) from the forward's two planes; no reduction: bit-reproducible.
+ *   sample: one position's draw. logits (N, K C) with element strides (sn, sk): the logit of (n, k, c) is at
+ *           n * sn + (k * C + c) * sk; uniforms (N, C) in [0, 1); out (N, C). With e_k = exp((z_k - max_k z) *
+ *           inv_temperature): the first class whose inclusive running sum exceeds u * sum_k e_k strictly, the last class
+ *           if rounding leaves none; out = class / (K - 1).
+ *   plan:   host only, no device needed: the lanes that share one sub-pixel's classes (K / 64 rounded down to a power
+ *           of two, 1..8; N, C and HW do not change it) and the sub-pixels per lane (4 when HW % 4 == 0, else 1) of the
+ *           fwd / bwd launches with 16-byte aligned operands (others take vec = 1).
+ * K in 2..4096, N, C, HW >= 1, N * C * HW < 2^31, N * C * HW * K < 2^40 (PG_ESHAPE otherwise); PG_EINVAL for a null
+ * operand (per_sample excepted), a non-positive stride or inverse temperature. No device call before these checks. */
+int pg_categorical_plan(int N, int C, int K, int HW, int* lanes_per_pixel, int* vec);
+int pg_categorical_nll_fwd(const float* logits, const float* x, float* lse, float* per_sample, float* loss, int N, int C,
+                           int K, int HW, void* stream);
+int pg_categorical_nll_bwd(const float* logits, const float* x, const float* lse, const float* g, float* dlogits, int N,
+                           int C, int K, int HW, void* stream);
+int pg_categorical_sample(const float* logits, long sn, long sk, const float* uniforms, float* out, int N, int C, int K,
+                          float inv_temperature, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,7 +9,7 @@ from pytorch_generative_amd.nn.convolution import (
     GatedConv,
     NCHWLayerNorm,
 )
-from pytorch_generative_amd.nn.utils import VectorQuantizer
+from pytorch_generative_amd.nn.utils import CategoricalSampler, VectorQuantizer
 
 __all__ = [
     "CausalAttention",
@@ -22,4 +22,5 @@ __all__ = [
     "GatedConv",
     "NCHWLayerNorm",
     "VectorQuantizer",
+    "CategoricalSampler",
 ]

@@ -149,3 +149,33 @@ class VectorQuantizer(nn.Module):
                                                   ops._sink(self._embedding))
         self.last_indices = idx
         return st, loss
+
+
+class CategoricalSampler:
+    """Draws sub-pixel intensities from K-way softmax logits: the `sample_fn` of an AutoregressiveModel whose output has
+    `n_classes * in_channels` channels, class-major (the layout of ops.categorical_nll_sum_mean). Every sampler of the
+    package (full forward per pixel, row-cached, ImageGPT's incremental one) calls `sample_fn(logits).view(n, c)` on one
+    position's (N, n_classes * C) logits; this returns the (N, C) levels class / (n_classes - 1) in [0, 1], drawn by
+    inverse CDF in one kernel launch (ops.categorical_sample) from uniforms of `generator` (None: the device's default).
+    temperature divides the logits: below 1 sharpens the distribution.
+
+    `sample(return_logits=True)` of the models stores logits in a canvas-shaped tensor, that is, it assumes
+    out_channels == in_channels: it cannot be combined with a categorical head."""
+
+    def __init__(self, n_classes, temperature=1.0, generator=None):
+        n_classes = int(n_classes)
+        if not 2 <= n_classes <= ops.CATEGORICAL_MAX_CLASSES:
+            raise ValueError(f"CategoricalSampler: n_classes = {n_classes} outside 2..{ops.CATEGORICAL_MAX_CLASSES}")
+        if not float(temperature) > 0.0:
+            raise ValueError(f"CategoricalSampler: temperature {temperature} must be positive")
+        self.n_classes, self.temperature, self.generator = n_classes, float(temperature), generator
+
+    def draw(self, logits, uniforms):
+        """The draw as a pure function of (N, n_classes * C) logits and (N, C) uniforms in [0, 1)."""
+        return ops.categorical_sample(logits, uniforms, self.n_classes, self.temperature)
+
+    def __call__(self, logits):
+        if logits.dim() != 2 or logits.shape[1] % self.n_classes:
+            raise ValueError(f"CategoricalSampler: expected (N, {self.n_classes} * C) logits, got {tuple(logits.shape)}")
+        shape = (logits.shape[0], logits.shape[1] // self.n_classes)
+        return self.draw(logits, torch.rand(shape, device=logits.device, generator=self.generator))

@@ -147,6 +147,11 @@ from pytorch_generative_amd.ops.losses import (  # noqa: F401
     DMOL_SAMPLE_MAX_K,
     dmol_sample,
     bce_with_logits_sum_mean,
+    _CategoricalNLLSumMean,
+    CATEGORICAL_MAX_CLASSES,
+    categorical_nll_sum_mean,
+    categorical_nll_per_sample,
+    categorical_sample,
     _ElboMean,
     elbo_terms,
 )

@@ -123,6 +123,111 @@ def bce_with_logits_sum_mean(logits, targets):
     return _BCEWithLogitsSumMean.apply(logits, targets)
 
 
+CATEGORICAL_MAX_CLASSES = 4096  # csrc/categorical.hip
+
+
+def _categorical_dims(logits, images, n_classes, what):
+    k = int(n_classes)
+    if not 2 <= k <= CATEGORICAL_MAX_CLASSES:
+        raise ValueError(f"{what}: n_classes = {k} outside 2..{CATEGORICAL_MAX_CLASSES}")
+    if logits.dim() != 4 or images.dim() != 4:
+        raise ValueError(f"{what}: expected (N, n_classes * C, H, W) logits and (N, C, H, W) images")
+    n, c, h, w = images.shape
+    if tuple(logits.shape) != (n, k * c, h, w):
+        raise ValueError(f"{what}: logits {tuple(logits.shape)} != {(n, k * c, h, w)} for images {tuple(images.shape)} "
+                         f"and {k} classes")
+    return n, c, k, h * w
+
+
+class _CategoricalNLLSumMean(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, images, n_classes):
+        lib = _lib.load()
+        logits = _chk(logits, "categorical.logits")
+        images = _chk(images, "categorical.images")
+        n, c, k, hw = _categorical_dims(logits, images, n_classes, "categorical_nll")
+        loss = zeros((1,), logits.device)
+        lse = torch.empty((2,) + tuple(images.shape), device=images.device, dtype=torch.float32)  # lse | its rounding residual
+        _lib.check(lib.pg_categorical_nll_fwd(logits.data_ptr(), images.data_ptr(), lse.data_ptr(), None, loss.data_ptr(),
+                                              n, c, k, hw, _stream()), "pg_categorical_nll_fwd")
+        ctx.save_for_backward(logits, images, lse)
+        ctx.dims = (n, c, k, hw)
+        return loss.view(())
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = _lib.load()
+        logits, images, lse = ctx.saved_tensors
+        g = _chk(g.reshape(1), "categorical.grad")
+        n, c, k, hw = ctx.dims
+        dlogits = torch.empty_like(logits)
+        _lib.check(lib.pg_categorical_nll_bwd(logits.data_ptr(), images.data_ptr(), lse.data_ptr(), g.data_ptr(),
+                                              dlogits.data_ptr(), n, c, k, hw, _stream()), "pg_categorical_nll_bwd")
+        return dlogits, None, None
+
+
+def categorical_nll_sum_mean(logits, images, n_classes):
+    """K-way softmax negative log-likelihood, nats, summed over sub-pixels and averaged over the batch:
+    F.cross_entropy(logits.view(N, K, C, H, W), classes, reduction='none').sum((1, 2, 3)).mean().
+    logits (N, n_classes * C, H, W), class-major; images (N, C, H, W) at the levels j / (n_classes - 1), from which the
+    class is rint(x * (n_classes - 1)) clamped to the range. The gradient goes to the logits only."""
+    return _CategoricalNLLSumMean.apply(logits, images, int(n_classes))
+
+
+@torch.no_grad()
+def categorical_nll_per_sample(logits, images, n_classes):
+    """The same likelihood per image: (N,) nats, no gradient (evaluation, bits/dim)."""
+    lib = _lib.load()
+    logits = _chk(logits, "categorical.logits")
+    images = _chk(images, "categorical.images")
+    n, c, k, hw = _categorical_dims(logits, images, n_classes, "categorical_nll_per_sample")
+    loss = zeros((1,), logits.device)
+    lse = torch.empty((2,) + tuple(images.shape), device=images.device, dtype=torch.float32)  # lse | its rounding residual
+    per_sample = torch.empty(n, device=logits.device, dtype=torch.float32)
+    _lib.check(lib.pg_categorical_nll_fwd(logits.data_ptr(), images.data_ptr(), lse.data_ptr(), per_sample.data_ptr(),
+                                          loss.data_ptr(), n, c, k, hw, _stream()), "pg_categorical_nll_fwd")
+    return per_sample
+
+
+@torch.no_grad()
+def categorical_sample(logits, uniforms, n_classes, temperature=1.0):
+    """One position's draw from the K-way softmax by inverse CDF, in one launch (pg_categorical_sample).
+
+    logits (N, n_classes * C), class-major, any positive strides (a column of a row step's output goes in without a
+    copy); uniforms (N, C) in [0, 1). Returns (N, C) levels class / (n_classes - 1): the first class whose running sum of
+    exp((z - max) / temperature) exceeds u times the total. Sampling only: no gradient is defined."""
+    lib = _lib.load()
+    k = int(n_classes)
+    if not 2 <= k <= CATEGORICAL_MAX_CLASSES:
+        raise ValueError(f"categorical_sample: n_classes = {k} outside 2..{CATEGORICAL_MAX_CLASSES}")
+    if not float(temperature) > 0.0:
+        raise ValueError(f"categorical_sample: temperature {temperature} must be positive")
+    for t, name in ((logits, "logits"), (uniforms, "uniforms")):
+        if not t.is_cuda:
+            raise RuntimeError(f"categorical_sample.{name}: expected a tensor on the MI355X (cuda) device, got {t.device}; "
+                               "the HIP operator path has no CPU fallback")
+        if t.dtype != torch.float32:
+            raise TypeError(f"categorical_sample.{name}: expected float32, got {t.dtype}")
+        if t.device.index != torch.cuda.current_device():
+            raise RuntimeError(f"categorical_sample.{name}: tensor lives on {t.device} but the current device is "
+                               f"cuda:{torch.cuda.current_device()}")
+    if logits.dim() != 2 or logits.shape[1] % k or uniforms.dim() != 2:
+        raise ValueError(f"categorical_sample: expected (N, {k} * C) logits and (N, C) uniforms, got "
+                         f"{tuple(logits.shape)} and {tuple(uniforms.shape)}")
+    n, c = logits.shape[0], logits.shape[1] // k
+    if tuple(uniforms.shape) != (n, c) or n < 1 or c < 1:
+        raise ValueError(f"categorical_sample: uniforms {tuple(uniforms.shape)} != {(n, c)}")
+    sn, sk = logits.stride()
+    if sn <= 0 or sk <= 0:  # an expanded or size-one dimension: the kernel wants real strides
+        logits = logits.contiguous()
+        sn, sk = logits.stride()
+    uniforms = uniforms.contiguous()
+    out = torch.empty((n, c), device=logits.device, dtype=torch.float32)
+    _lib.check(lib.pg_categorical_sample(logits.data_ptr(), sn, sk, uniforms.data_ptr(), out.data_ptr(), n, c, k,
+                                         1.0 / float(temperature), _stream()), "pg_categorical_sample")
+    return out
+
+
 class _ElboMean(torch.autograd.Function):
     """loss = mean_n(recon_n) + mean_n(kl_n) with recon_n the per-sample BCE-with-logits sum."""
 

@@ -20,6 +20,16 @@ def bce_loss(x, _, preds):
     return ops.bce_with_logits_sum_mean(preds, x)
 
 
+def categorical_loss(n_classes):
+    """loss_fn of a model with a K-way softmax head (out_channels = n_classes * in_channels, class-major): sum-over-sub-pixels,
+    mean-over-batch negative log-likelihood of images at the levels j / (n_classes - 1) (`grey_mnist` for 256)."""
+
+    def loss_fn(x, _, preds):
+        return ops.categorical_nll_sum_mean(preds, x, n_classes)
+
+    return loss_fn
+
+
 def elbo_loss(x, _, preds):
     """{"recon_loss", "kl_div", "loss"} of the VAE recipes (vae.py:149-159)."""
     logits, kl_div = preds
@@ -53,6 +63,11 @@ def run(build_model, *, loaders, loss_fn, lr, lr_decay=1.0, n_epochs, batch_size
 
 def binarized_mnist(batch_size):
     return datasets.get_mnist_loaders(batch_size, dynamically_binarize=True)
+
+
+def grey_mnist(batch_size):
+    """MNIST at its 256 grey levels / 255, for `categorical_loss(256)`."""
+    return datasets.get_mnist_loaders(batch_size)
 
 
 def binarized_mnist_32(batch_size):
