@@ -724,6 +724,42 @@ int pg_categorical_nll_bwd(const float* logits, const float* x, const float* lse
 int pg_categorical_sample(const float* logits, long sn, long sk, const float* uniforms, float* out, int N, int C, int K,
                           float inv_temperature, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * The last 1x1 convolution fused into the categorical likelihood, linear_categorical.hip:
+ *   loss = categorical_nll(conv1x1(transform(h))) with nothing of the logits' size N K C HW written in either pass.
+ * h (N, Cin, HW) dense; w (K C, Cin) the convolution's weight, class-major (output channel k C + c), 16-byte aligned;
+ * b (K C) or NULL; x as above. transform (PG_LC_*) is applied to h on load: none, relu, or LayerNorm over the Cin
+ * channels with (ln_w, ln_b, eps) (biased variance, eps inside the root; both 16-byte aligned, NULL otherwise).
+ *   plan:   host only. A workgroup (one wave) owns ceil(tiles / rows) consecutive tiles of `pixels_per_tile` consecutive
+ *           pixels of the sequence n HW + hw; `rows` workgroups = partial rows; `lds_bytes` the largest LDS a launch takes;
+ *           workspace_floats = rows * (K C Cin + K C + 2 Cin). rows * row length stays within a quarter of N K C HW
+ *           floats unless a single row exceeds that (rows = 1 then).
+ *   fwd:    lse (2, N, C, HW) as pg_categorical_nll_fwd — (3, N, C, HW) when per_sample is given: plane 2 then receives the
+ *           sub-pixel's lse - z_t, which per_sample (N) sums in a fixed order; loss[0] += (1 / N) sum (lse - z_t), one fp32
+ *           atomic per workgroup.
+ *   bwd:    recomputes the logits bit for bit, d = g[0] / N (exp((z - lse) - residual) - [k == t]); writes
+ *           dh (N, Cin, HW) (through the transform's derivative) and one partial row per workgroup into `workspace`:
+ *           [ dW (K C x Cin) | db (K C) | d ln_w (Cin) | d ln_b (Cin) ] (parts that do not apply stay zero).
+ *           Where |lse| of a sub-pixel is 16 or more (8 for Cin > 64) the classes within 18 of it are evaluated once more in
+ *           float64, in both passes: lse + residual is the normaliser of the exact logits to 4e-6, whatever their size.
+ *   reduce: ADDS the rows, in row order, into dW and (where not NULL) db, dln_w, dln_b. No float atomics on a gradient.
+ * Cin a multiple of 4 in 4..256, K in 2..4096, the size limits of pg_categorical_*, N HW < 2^31 - 16 and
+ * K C (Cin + 1) + 2 Cin < 2^31 (PG_ESHAPE otherwise); PG_EINVAL for a null or misaligned operand or a short workspace.
+ * No device call before these checks. */
+#define PG_LC_NONE 0
+#define PG_LC_RELU 1
+#define PG_LC_LN 2
+int pg_linear_categorical_plan(int N, int C, int K, int Cin, int HW, int transform, int* pixels_per_tile, int* rows,
+                               int* lds_bytes, size_t* workspace_floats);
+int pg_linear_categorical_nll_fwd(const float* h, const float* w, const float* b, const float* ln_w, const float* ln_b,
+                                  float eps, const float* x, float* lse, float* per_sample, float* loss, int N, int C, int K,
+                                  int Cin, int HW, int transform, void* stream);
+int pg_linear_categorical_nll_bwd(const float* h, const float* w, const float* b, const float* ln_w, const float* ln_b,
+                                  float eps, const float* x, const float* lse, const float* g, float* dh, int N, int C, int K,
+                                  int Cin, int HW, int transform, float* workspace, size_t workspace_floats, void* stream);
+int pg_linear_categorical_reduce(const float* workspace, int rows, int KC, int Cin, int transform, float* dW, float* db,
+                                 float* dln_w, float* dln_b, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -42,6 +42,7 @@
 #include <math.h>
 #include <stdlib.h>
 
+#include "categorical.h"  // cat_class, cat_merge
 #include "common.h"
 
 namespace {
@@ -70,19 +71,6 @@ struct CatVec<4> {
     *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
   }
 };
-
-__device__ __forceinline__ int cat_class(float x, int K) {
-  // fmaxf / fminf drop a NaN: the index is in range whatever the image holds
-  return (int)fminf(fmaxf(rintf(x * (float)(K - 1)), 0.f), (float)(K - 1));
-}
-
-// (m, s) stands for m + log s; (-inf, 0) is the empty sum. All-(-inf) inputs keep it empty (no exp(-inf + inf)).
-__device__ __forceinline__ void cat_merge(float& m, float& s, float m2, float s2) {
-  const float mn = fmaxf(m, m2);
-  const float ref = mn > -INFINITY ? mn : 0.f;
-  s = s * __expf(m - ref) + s2 * __expf(m2 - ref);
-  m = mn;
-}
 
 // where a lane's unit lies; lanes past the last unit are parked on it (they take part in the shuffles, store nothing)
 struct CatPos {

@@ -177,6 +177,10 @@ SIGNATURES = {
     "pg_categorical_nll_fwd": (c_i, [c_f] * 5 + [c_i] * 4 + [c_s]),
     "pg_categorical_nll_bwd": (c_i, [c_f] * 5 + [c_i] * 4 + [c_s]),
     "pg_categorical_sample": (c_i, [c_f, c_l, c_l, c_f, c_f, c_i, c_i, c_i, c_flt, c_s]),
+    "pg_linear_categorical_plan": (c_i, [c_i] * 6 + [c_ip, c_ip, c_ip, ctypes.POINTER(ctypes.c_size_t)]),
+    "pg_linear_categorical_nll_fwd": (c_i, [c_f] * 5 + [c_flt] + [c_f] * 4 + [c_i] * 6 + [c_s]),
+    "pg_linear_categorical_nll_bwd": (c_i, [c_f] * 5 + [c_flt] + [c_f] * 4 + [c_i] * 6 + [c_f, c_z, c_s]),
+    "pg_linear_categorical_reduce": (c_i, [c_f, c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_f, c_s]),
     "pg_col_subsample2": (c_i, [c_f, c_f, c_l, c_i, c_s]),
     "pg_col_zero_insert2": (c_i, [c_f, c_f, c_l, c_i, c_s]),
     "pg_copy_rows": (c_i, [c_f, c_f, c_l, c_l, c_l, c_l, c_i, c_s]),

@@ -124,7 +124,7 @@ class GatedPixelCNN(base.AutoregressiveModel):
         vstack, hstack, skip_connections = self._input(x, x)
         for gated_layer in self._gated_layers:
             vstack, hstack, skip_connections = gated_layer(vstack, hstack, skip_acc=skip_connections)
-        return self._head[3](self._head[1](skip_connections, in_act="relu"), in_act="relu")
+        return self._logits(self._head[1](skip_connections, in_act="relu"), self._head[3], in_act="relu")
 
 
 def reproduce(n_epochs=457, batch_size=128, log_dir="/tmp/run", n_gpus=1, device_id=0,

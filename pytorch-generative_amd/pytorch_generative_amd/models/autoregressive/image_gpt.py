@@ -106,6 +106,7 @@ class ImageGPT(base.AutoregressiveModel):
         probe = torch.empty(1, self._input.weight.shape[0], 1, ld, device="meta")
         return all(blk._fused_ok(probe) for blk in self._transformer) and self._input.bias is not None
 
+    @base.dense_head
     @torch.no_grad()
     def sample(self, n_samples=None, conditioned_on=None, *, incremental=True, return_logits=False):
         """Same contract as the reference's AutoregressiveModel.sample (models/base.py:97-120: raster
@@ -225,9 +226,8 @@ class ImageGPT(base.AutoregressiveModel):
         for i, block in enumerate(blocks):
             nxt = blocks[i + 1] if i + 1 < len(blocks) and fused[i] and fused[i + 1] else None
             x = block.forward_plus_input(x, chain, flush=(i == 0 and not stem_flushes), boundary=boundary, next_block=nxt)
-        if ops.gpt_out_head_supported(x, self._ln, self._out):
-            return self._out(x, pre_ln=self._ln, chain=chain if stem_flushes else None)
-        return self._out(self._ln(x))
+        # defer_head: the head runs inside the loss (ops.DeferredLogits) and reduces its own rows: it does not join the chain
+        return self._logits(x, self._out, pre_ln=self._ln, chain=chain if stem_flushes else None)
 
 
 def reproduce(n_epochs=457, batch_size=64, log_dir="/tmp/run", n_gpus=1, device_id=0,

@@ -80,7 +80,7 @@ class PixelCNN(base.AutoregressiveModel):
         x = self._input(x)
         for layer in self._causal_layers:
             x = layer(x, double=True)
-        return self._head[3](self._head[1](x, in_act="relu"), in_act="relu")
+        return self._logits(self._head[1](x, in_act="relu"), self._head[3], in_act="relu")
 
 
 def reproduce(n_epochs=457, batch_size=256, log_dir="/tmp/run", n_gpus=1, device_id=0,

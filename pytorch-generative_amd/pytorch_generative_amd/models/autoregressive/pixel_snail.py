@@ -161,7 +161,7 @@ class PixelSNAIL(base.AutoregressiveModel):
         x = self._input(x)
         for block in self._pixel_snail_blocks:
             x = block(x, input_img, add_input=True)
-        return self._output[1](self._output[0](x))
+        return self._logits(self._output[0](x), self._output[1])
 
 
 def reproduce(n_epochs=457, batch_size=128, log_dir="/tmp/run", n_gpus=1, device_id=0,

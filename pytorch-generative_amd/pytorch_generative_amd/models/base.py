@@ -27,6 +27,21 @@ def auto_reshape(fn):
     return wrapped_fn
 
 
+def dense_head(fn):
+    """Decorator of sample(): it always sees dense logits, so `defer_head` is off for the duration of the call."""
+
+    @functools.wraps(fn)
+    def wrapped_fn(self, *args, **kwargs):
+        saved = self.defer_head
+        self.defer_head = False
+        try:
+            return fn(self, *args, **kwargs)
+        finally:
+            self.defer_head = saved
+
+    return wrapped_fn
+
+
 def _bernoulli_from_logits(logits):
     return distributions.Bernoulli(logits=logits).sample()
 
@@ -76,6 +91,24 @@ class AutoregressiveModel(GenerativeModel):
     _row_graph = False            # the row step is identical for every row (no attention): hipGraph it
     _row_decode_min_batch = 1     # below this batch the per-pixel full forward is used (launch-bound row steps)
 
+    # True (extension; an attribute, not a constructor argument: signatures and state_dict stay the reference's): the models
+    # with a K-way softmax head return ops.DeferredLogits from forward() instead of running their last 1x1 convolution, and
+    # ops.categorical_nll_* run it inside the loss kernels (ops.linear_categorical): the (N, K C, H, W) logits are never written.
+    defer_head = False
+
+    def _logits(self, features, conv, *, in_act=None, pre_ln=None, **dense_kw):
+        """The model's last 1x1 convolution: deferred when `defer_head` is set and no RowDecode is open, else as always."""
+        from pytorch_generative_amd import ops
+
+        if self.defer_head and ops.RowDecode.current is None:
+            return ops.DeferredLogits(features, conv, in_act=in_act, pre_ln=pre_ln)
+        if pre_ln is not None:
+            if ops.gpt_out_head_supported(features, pre_ln, conv):
+                return conv(features, pre_ln=pre_ln, **dense_kw)
+            return conv(pre_ln(features))
+        return conv(features, in_act=in_act)
+
+    @dense_head
     @torch.no_grad()
     def sample(self, n_samples=None, conditioned_on=None, *, incremental=True, return_logits=False):
         """Generates samples; entries of `conditioned_on` that are >= 0 are kept as given

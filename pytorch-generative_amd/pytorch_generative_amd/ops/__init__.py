@@ -140,6 +140,11 @@ from pytorch_generative_amd.ops.density import (  # noqa: F401
     kde_parzen,
     mixture_log_prob,
 )
+from pytorch_generative_amd.ops.linear_categorical import (  # noqa: F401
+    DeferredLogits,
+    _LinearCategoricalNLL,
+    linear_categorical_supported,
+)
 from pytorch_generative_amd.ops.losses import (  # noqa: F401
     _BCEWithLogitsSumMean,
     _DmolLossSumMean,

@@ -6,6 +6,7 @@ with tensor.data_ptr() and the current stream. No CPU / ATen fallback: a missing
 import torch
 
 from pytorch_generative_amd import _lib
+from pytorch_generative_amd.ops import linear_categorical
 from pytorch_generative_amd.ops._common import _chk, _stream, zeros
 
 
@@ -170,13 +171,25 @@ def categorical_nll_sum_mean(logits, images, n_classes):
     """K-way softmax negative log-likelihood, nats, summed over sub-pixels and averaged over the batch:
     F.cross_entropy(logits.view(N, K, C, H, W), classes, reduction='none').sum((1, 2, 3)).mean().
     logits (N, n_classes * C, H, W), class-major; images (N, C, H, W) at the levels j / (n_classes - 1), from which the
-    class is rint(x * (n_classes - 1)) clamped to the range. The gradient goes to the logits only."""
+    class is rint(x * (n_classes - 1)) clamped to the range. The gradient goes to the logits only.
+    logits may be an ops.DeferredLogits (a model with defer_head = True): the head's 1x1 convolution then runs inside the loss
+    kernels (ops.linear_categorical) where they cover it, and as .dense() in front of this function's kernels where not."""
+    if isinstance(logits, linear_categorical.DeferredLogits):
+        dims = linear_categorical.fused_route(logits, images, n_classes)
+        if dims is not None:
+            return linear_categorical.linear_categorical_nll_sum_mean(logits, images, dims)
+        logits = logits.dense()
     return _CategoricalNLLSumMean.apply(logits, images, int(n_classes))
 
 
 @torch.no_grad()
 def categorical_nll_per_sample(logits, images, n_classes):
-    """The same likelihood per image: (N,) nats, no gradient (evaluation, bits/dim)."""
+    """The same likelihood per image: (N,) nats, no gradient (evaluation, bits/dim). logits may be an ops.DeferredLogits."""
+    if isinstance(logits, linear_categorical.DeferredLogits):
+        dims = linear_categorical.fused_route(logits, images, n_classes, "categorical_nll_per_sample")
+        if dims is not None:
+            return linear_categorical.linear_categorical_nll_per_sample(logits, images, dims)
+        logits = logits.dense()
     lib = _lib.load()
     logits = _chk(logits, "categorical.logits")
     images = _chk(images, "categorical.images")

@@ -46,14 +46,17 @@ def _device(n_gpus, device_id):
 
 
 def run(build_model, *, loaders, loss_fn, lr, lr_decay=1.0, n_epochs, batch_size, log_dir, n_gpus,
-        device_id, debug_loader):
-    """Builds everything a recipe names and trains for `n_epochs`; returns the Trainer."""
+        device_id, debug_loader, defer_head=False):
+    """Builds everything a recipe names and trains for `n_epochs`; returns the Trainer. defer_head=True sets the attribute
+    of that name on the model (autoregressive models with a categorical head: the head runs inside the loss kernels)."""
     device = _device(n_gpus, device_id)
     if debug_loader is not None:
         train_loader = test_loader = debug_loader
     else:
         train_loader, test_loader = loaders(batch_size)
     model = build_model().to(device)
+    if defer_head:
+        model.defer_head = True
     optimizer = optim.FlatAdam(model.parameters(), lr=lr, lr_decay=lr_decay)
     t = trainer.Trainer(model=model, loss_fn=loss_fn, optimizer=optimizer, train_loader=train_loader,
                         eval_loader=test_loader, log_dir=log_dir, n_gpus=n_gpus, device_id=device_id)
