@@ -760,6 +760,49 @@ int pg_linear_categorical_nll_bwd(const float* h, const float* w, const float* b
 int pg_linear_categorical_reduce(const float* workspace, int rows, int KC, int Cin, int transform, float* dW, float* db,
                                  float* dln_w, float* dln_b, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Convolution over an image of code indices, code_conv.hip: F.conv2d(one_hot(codes), w) as a table lookup, for
+ * autoregressive priors over VQ-VAE codes. levels (N, 1, Hin, Win) dense: a code image at the levels j / (K - 1) (the
+ * layout pg_categorical_nll_* take as x; the code is clamp((int)rintf(level (K - 1)), 0, K - 1)); a NEGATIVE level is an
+ * undrawn position and stands for the all-zero one-hot vector. w (Cout, K, KH, KW).
+ *   fwd:    out[n, :, y, x] = b + sum_t w[:, code(n, y + u_t - pad_h, x + v_t - pad_w), u_t, v_t] over the tap list
+ *           (u, v) (host arrays; inside the kernel, strictly ascending in u KW + v), zero outside the image;
+ *           out (N, Cout, OH, OW) is any window anchored at the top-left corner (a row band is the same call with another
+ *           pad_h). The taps are packed once per call into a (taps, K, Cout) table in `ws`
+ *           (pg_code_conv_fwd_workspace_floats floats). Bias first, then the taps in ascending order: bit-reproducible.
+ *           b may be NULL. The caller has masked w already.
+ *   wgrad:  dw[co, k, u, v] (+)= sum of dy[n, co, y, x] over the positions with code(n, y + u - pad_h, x + v - pad_w) = k,
+ *           for ALL KH KW taps (the reference's weight gradient is unmasked), db[co] (+)= sum dy[:, co]; either may be
+ *           NULL. Store-and-sum: an inverted index (per code the ascending list of its positions: a stable counting sort
+ *           on integer counters), one wave sums a chunk of at most 512 list entries for a group of channels, a code's
+ *           chunks are added in chunk order. No float atomics, no host synchronisation, capturable; bit-reproducible.
+ *           Codes that never occur receive exact zeros. accumulate != 0 adds the finished sum to dw / db (a flat-gradient
+ *           sink) with one fp32 addition per element. ws: pg_code_conv_wgrad_workspace_floats floats (every word that is
+ *           read is written first).
+ *   plan:   host only. max_chunks = the chunks of the longest possible list, ceil(N Hin Win / 512); items = the work
+ *           items reserved for the sum, K + N Hin Win / 512 (an upper bound of sum_k ceil(list_k / 512)).
+ * pg_sample_embed_codes: the code counterpart of pg_sample_embed. out[co * ld + n] = b[co] + pos_term[co, r, c] + the
+ *   stem at raster position (r, c) of every sample (pos_dev != NULL: the position is read from the device), padding
+ *   KH / 2, KW / 2, every tap read (w is masked). canvas (N, 1, H, W) levels, pos_term (Cout, H, W) or NULL.
+ * pg_vq_lookup: out (N, D, L) = embedding[code(levels (N, L))] transposed: the VQ-VAE decoder's input from a code image
+ *   (a negative level reads code 0).
+ * K in 2..4096, at most PG_MAX_TAPS taps, positions and weights below 2^31 (PG_ESHAPE otherwise); PG_EINVAL for a null
+ * operand, a bad tap list, a pixel outside the image or a short workspace. No device call before these checks; the queries return 0 for shapes
+ * the launch refuses. */
+size_t pg_code_conv_fwd_workspace_floats(int Cout, int K, int n_taps);
+int pg_code_conv_fwd(const float* levels, const float* w, const float* b, float* out, int N, int K, int Hin, int Win,
+                     int Cout, int KH, int KW, int OH, int OW, int n_taps, const int* u, const int* v, int pad_h, int pad_w,
+                     float* ws, size_t ws_floats, void* stream);
+int pg_code_conv_wgrad_plan(int N, int K, int Hin, int Win, int* max_chunks, int* items);
+size_t pg_code_conv_wgrad_workspace_floats(int N, int K, int Hin, int Win, int Cout, int KH, int KW);
+int pg_code_conv_wgrad(const float* levels, const float* dy, float* dw, float* db, int accumulate, int N, int K, int Hin,
+                       int Win, int Cout, int KH, int KW, int OH, int OW, int pad_h, int pad_w, float* ws, size_t ws_floats,
+                       void* stream);
+int pg_sample_embed_codes(const float* canvas, const float* w, const float* b, const float* pos_term, float* out, int N,
+                          int K, int H, int W, int Cout, int KH, int KW, int r, int c, int ld, const int* pos_dev,
+                          void* stream);
+int pg_vq_lookup(const float* levels, const float* embedding, float* out, int N, int D, int L, int K, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -121,6 +121,7 @@ class GatedPixelCNN(base.AutoregressiveModel):
         )
 
     def forward(self, x):
+        self._no_input_codes()  # two stem convolutions inside a fused layer
         vstack, hstack, skip_connections = self._input(x, x)
         for gated_layer in self._gated_layers:
             vstack, hstack, skip_connections = gated_layer(vstack, hstack, skip_acc=skip_connections)

@@ -100,6 +100,19 @@ class ImageGPT(base.AutoregressiveModel):
             in_channels=n_embedding_channels, out_channels=out_channels, kernel_size=1
         )
 
+    # ---- code-index input (AutoregressiveModel.input_codes) ------------------------------------
+    def _position_term(self):
+        """W * _pos without the bias, (1, C, H, W): the data-independent half of _input(onehot + _pos) (the convolution is
+        linear), on the dense kernels at batch 1; its gradient reaches _pos and the weight through them. The caller has
+        masked the weight."""
+        conv = self._input
+        return ops.conv2d_taps(self._pos, conv.weight, None, conv._conv_spec(), weight_param=conv.weight)
+
+    def _stem_codes(self, levels):
+        """_input(one_hot(codes) + _pos) for a code image (N, 1, H, W): lookup with the bias + the position term."""
+        x = self._input.forward_codes(levels, self.input_codes)  # masks the weight in place first
+        return ops.add_broadcast_batch(x, self._position_term())
+
     # ---- incremental sampling (SURVEY §8 f2) -------------------------------------------------
     def _incremental_ok(self, n):
         ld = (n + 15) // 16 * 16
@@ -142,13 +155,25 @@ class ImageGPT(base.AutoregressiveModel):
         x = torch.zeros(1, emb, 1, ld, device=dev)
         pos_dev = torch.zeros(1, dtype=torch.int32, device=dev)  # raster position, advanced on the device
 
+        n_codes = self.input_codes
+        if n_codes is not None:
+            if c != 1 or int(n_codes) != conv.in_channels or (h, w) != tuple(self._pos.shape[2:]):
+                raise ValueError(f"sample: input_codes = {n_codes} needs a (N, 1, {self._pos.shape[2]}, {self._pos.shape[3]}) "
+                                 f"canvas and {n_codes} stem input channels")
+            pos_term = self._position_term().contiguous()  # once per call
+
         def position_logits():
             """logits (n, c) of the position in pos_dev; appends its keys / values to the caches"""
             st = torch.cuda.current_stream().cuda_stream
-            _lib.check(lib.pg_sample_embed(canvas.data_ptr(), self._pos.data_ptr(),
-                                           conv.weight.data_ptr(), conv.bias.data_ptr(), x.data_ptr(),
-                                           n, c, h, w, emb, kh, kw, 0, 0, ld, pos_dev.data_ptr(), st),
-                       "pg_sample_embed")
+            if n_codes is not None:
+                _lib.check(lib.pg_sample_embed_codes(canvas.data_ptr(), conv.weight.data_ptr(), conv.bias.data_ptr(),
+                                                     pos_term.data_ptr(), x.data_ptr(), n, int(n_codes), h, w, emb, kh, kw,
+                                                     0, 0, ld, pos_dev.data_ptr(), st), "pg_sample_embed_codes")
+            else:
+                _lib.check(lib.pg_sample_embed(canvas.data_ptr(), self._pos.data_ptr(),
+                                               conv.weight.data_ptr(), conv.bias.data_ptr(), x.data_ptr(),
+                                               n, c, h, w, emb, kh, kw, 0, 0, ld, pos_dev.data_ptr(), st),
+                           "pg_sample_embed")
             cur = x
             for blk, (kc, vc) in zip(blocks, caches):
                 a = blk._attn
@@ -201,12 +226,16 @@ class ImageGPT(base.AutoregressiveModel):
     def forward(self, x):
         img, blocks, grad = x, list(self._transformer), torch.is_grad_enabled()
         # the two ends on their own kernels (gpt_ends.hip) where the model has the BASELINE shape; PG_FUSE_ENDS=0 = generic operators
-        fuse_stem = ops.gpt_stem_supported(img, self._pos, self._input)
+        codes = self.input_codes is not None  # the stem as a table lookup: the fused stem is not taken
+        fuse_stem = not codes and ops.gpt_stem_supported(img, self._pos, self._input)
         # The stem's backward runs last: a trainable fused stem flushes the chain on its only path, whichever blocks queued rows
         stem_flushes = fuse_stem and grad and any(p.requires_grad for p in (self._pos, self._input.weight, self._input.bias))
         if fuse_stem:
             x0_grad = stem_flushes
             probe = torch.empty(1, self._input.weight.shape[0], img.shape[2], img.shape[3], device="meta")
+        elif codes:
+            x = probe = self._stem_codes(img)
+            x0_grad = x.requires_grad
         else:
             x = probe = self._input(ops.add_broadcast_batch(img, self._pos))
             x0_grad = x.requires_grad

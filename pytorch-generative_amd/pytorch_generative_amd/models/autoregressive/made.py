@@ -144,6 +144,7 @@ class MADE(base.AutoregressiveModel):
         return specs
 
     def _forward(self, x, index):
+        self._no_input_codes()  # forward() and sample() both pass here
         return ops.masked_mlp(x, self._layer_specs(index, x.device))
 
     def _apply(self, fn, *args, **kwargs):

@@ -77,7 +77,8 @@ class PixelCNN(base.AutoregressiveModel):
         )
 
     def forward(self, x):
-        x = self._input(x)
+        # input_codes = K: x is a code image (N, 1, H, W) and the stem a table lookup (row-cached sampling: a band of levels)
+        x = self._input(x) if self.input_codes is None else self._input.forward_codes(x, self.input_codes)
         for layer in self._causal_layers:
             x = layer(x, double=True)
         return self._logits(self._head[1](x, in_act="relu"), self._head[3], in_act="relu")

@@ -112,6 +112,7 @@ class PixelCNNpp(base.AutoregressiveModel):
     def _net(self, x):
         """The network body on images in [-1, 1]. forward() and sample() both call THIS, so that a subclass whose
         forward() rescales its input (reproduce()'s wrapper for [0, 1] loaders) does not rescale the sampler's canvas."""
+        self._no_input_codes()
         n, _, h, w = x.shape
         if h % 4 or w % 4:
             raise ValueError("PixelCNNpp: H and W must be multiples of 4 (two stride-2 levels)")
@@ -256,6 +257,7 @@ class PixelCNNpp(base.AutoregressiveModel):
         the (N, 10 K, H, W) mixture parameters the draws were made from.
         A `sample_fn` given to the constructor replaces the mixture draw on the incremental path:
         sample_fn(params (N, 10 K)) -> (N, 3), called eagerly once per pixel."""
+        self._no_input_codes()  # (the row-cached sampler runs _row_net, not _net)
         if return_params and not incremental:
             raise ValueError("return_params requires incremental=True")
         if conditioned_on is not None:

@@ -157,6 +157,7 @@ class PixelSNAIL(base.AutoregressiveModel):
         )
 
     def forward(self, x):
+        self._no_input_codes()  # the input image feeds every block
         input_img = x
         x = self._input(x)
         for block in self._pixel_snail_blocks:

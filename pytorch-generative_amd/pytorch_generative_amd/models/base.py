@@ -82,7 +82,8 @@ class AutoregressiveModel(GenerativeModel):
         ), 'Must provided one, and only one, of "n_samples" or "conditioned_on"'
         if conditioned_on is not None:
             return conditioned_on.clone()
-        shape = (n_samples, int(self._c), int(self._h), int(self._w))
+        # a code image has one channel, whatever channel count a checkpoint trained on one-hot input recorded
+        shape = (n_samples, 1 if self.input_codes is not None else int(self._c), int(self._h), int(self._w))
         return torch.full(shape, -1.0, device=self.device)
 
     # Models whose every layer is row-causal set this: sample() then evaluates one image ROW per step
@@ -95,6 +96,16 @@ class AutoregressiveModel(GenerativeModel):
     # with a K-way softmax head return ops.DeferredLogits from forward() instead of running their last 1x1 convolution, and
     # ops.categorical_nll_* run it inside the loss kernels (ops.linear_categorical): the (N, K C, H, W) logits are never written.
     defer_head = False
+
+    # K (extension; an attribute like defer_head): forward() takes a code image (N, 1, H, W) at the levels j / (K - 1) — the
+    # target layout of ops.categorical_nll_* and what nn.CategoricalSampler returns — in place of the (N, K, H, W) one-hot
+    # tensor, and the stem runs as a table lookup (Conv2d.forward_codes). Parameters, state_dict and results are those of the
+    # model on one_hot(codes); a negative level is an undrawn position. ImageGPT and PixelCNN take it; the others raise.
+    input_codes = None
+
+    def _no_input_codes(self):
+        if self.input_codes is not None:
+            raise ValueError(f"{type(self).__name__} does not support input_codes (ImageGPT and PixelCNN do)")
 
     def _logits(self, features, conv, *, in_act=None, pre_ln=None, **dense_kw):
         """The model's last 1x1 convolution: deferred when `defer_head` is set and no RowDecode is open, else as always."""
@@ -158,6 +169,9 @@ class AutoregressiveModel(GenerativeModel):
                             band = getattr(m, "_row_band", None)
                             if band is not None:
                                 band.zero_()
+                            band = getattr(m, "_row_code_band", None)
+                            if band is not None:  # a band of levels: -1 = no code (Conv2d.forward_codes)
+                                band.fill_(-1.0)
                     except Exception as e:  # noqa: BLE001 — capture is an optimisation only
                         import os
                         if os.environ.get("PG_DEBUG"):
@@ -165,6 +179,7 @@ class AutoregressiveModel(GenerativeModel):
                         step_graph = commit_graph = None
                         torch.cuda.synchronize()
                         reset()
+                self._row_step_captured = step_graph is not None  # for inspection: the capture falls back silently
                 for row in range(h):
                     ctx.row, ctx.commit = row, False
                     for col in range(w):

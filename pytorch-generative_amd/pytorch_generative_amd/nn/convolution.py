@@ -67,6 +67,7 @@ class Conv2d(nn.Conv2d):
     # ---- row-cached incremental sampling (ops.RowDecode) ------------------------------------------
     def _row_reset(self):
         self._row_band = None
+        self._row_code_band = None
         self._row_spec_cached = None
 
     def _row_forward(self, ctx, x, crop, in_act, res, out_act):
@@ -100,6 +101,50 @@ class Conv2d(nn.Conv2d):
             if res is not None:
                 y = ops.add(y, res)
         if ctx.commit and k > 0:  # the row is final: it becomes the newest cached row
+            band[:, :, :k, :].copy_(band[:, :, 1:, :].clone())
+        return y
+
+    # ---- code-index input (ops.code_conv2d) ---------------------------------------------------------
+    def _check_n_codes(self, n_codes):
+        if int(n_codes) != self.in_channels:
+            raise ValueError(f"forward_codes: n_codes = {n_codes} must equal in_channels = {self.in_channels}")
+        if self._down2:
+            raise ValueError("forward_codes: strided convolutions take no code input")
+
+    def forward_codes(self, levels, n_codes, *, crop=None):
+        """self(one_hot(codes)) (extension) for a code image `levels` (N, 1, H, W) at the levels j / (n_codes - 1), without the
+        (N, n_codes, H, W) one-hot tensor: a table lookup, ops.code_conv2d. A negative level (an undrawn canvas position) is
+        the all-zero vector. Under ops.RowDecode `levels` is one image row and the band holds one channel of levels."""
+        self._check_n_codes(n_codes)
+        ctx = ops.RowDecode.current
+        if ctx is not None:
+            return self._row_forward_codes(ctx, levels, n_codes, crop)
+        return ops.code_conv2d(levels, self.weight, self.bias, self._conv_spec(), n_codes, out_hw=crop,
+                               weight_param=self.weight, bias_param=self.bias)
+
+    def _row_forward_codes(self, ctx, levels, n_codes, crop):
+        """_row_forward for a row of levels: the band is (N, 1, k + 1, W), cleared to -1 (no code: rows above the image
+        contribute nothing, as zero padding does); same commit rule, no host synchronisation."""
+        spec = self._conv_spec()
+        reach = [spec.pad_h - u for u, _ in spec.fwd_taps]
+        if min(reach) < 0:
+            raise ValueError("row decode: a tap below the output row (the layer is not row-causal)")
+        k = max(reach)
+        n, c, one, w = levels.shape
+        if one != 1 or c != 1:
+            raise ValueError("row decode expects one row of a level image (N, 1, 1, W)")
+        if getattr(self, "_row_spec_cached", None) is None:
+            self._row_spec_cached = ops.ConvSpec(spec.kh, spec.kw, spec.pad_h - k, spec.pad_w, active=spec.fwd_taps)
+        if k == 0:
+            band = levels
+        else:
+            if getattr(self, "_row_code_band", None) is None or self._row_code_band.shape != (n, 1, k + 1, w):
+                self._row_code_band = torch.full((n, 1, k + 1, w), -1.0, device=levels.device, dtype=levels.dtype)
+            band = self._row_code_band
+            band[:, :, k:, :].copy_(levels)
+        ow = crop[1] if crop is not None else spec.full_out(1, w)[1]
+        y = ops.code_conv2d(band, self.weight, self.bias, self._row_spec_cached, n_codes, out_hw=(1, ow))
+        if ctx.commit and k > 0:
             band[:, :, :k, :].copy_(band[:, :, 1:, :].clone())
         return y
 
@@ -301,6 +346,11 @@ class CausalConv2d(Conv2d):
             return ops.gpt_stem(x, pos, self, chain)
         ops.mul_inplace_(self.weight.data, self.mask)
         return super().forward(x, crop=crop, in_act=in_act, res=res, **kw)
+
+    def forward_codes(self, levels, n_codes, *, crop=None):
+        self._check_n_codes(n_codes)
+        ops.mul_inplace_(self.weight.data, self.mask)  # in place on every forward, as the reference's (nn/convolution.py:42)
+        return super().forward_codes(levels, n_codes, crop=crop)
 
 
 class GatedActivation(nn.Module):

@@ -80,6 +80,13 @@ from pytorch_generative_amd.ops.conv import (  # noqa: F401
     FUSE_DUAL,
     FUSE_GATE,
 )
+from pytorch_generative_amd.ops.code_conv import (  # noqa: F401
+    CODE_MAX_CODES,
+    code_conv2d,
+    code_conv_wgrad_plan,
+    vq_lookup,
+    codes_to_levels,
+)
 from pytorch_generative_amd.ops.gpt_block import (  # noqa: F401
     FUSE_MLP,
     mlp_gelu_supported,

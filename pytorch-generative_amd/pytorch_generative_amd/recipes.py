@@ -93,3 +93,32 @@ def vq_loss(vq_weight):
                 "loss": recon_loss + vq_weight * quantization_loss}
 
     return loss_fn
+
+
+class _CodeLoader:
+    """A loader whose (x, y) batches become (vqvae.encode_codes(x), y): the training data of a prior over the codes."""
+
+    def __init__(self, vqvae, loader):
+        self._vqvae, self._loader = vqvae, loader
+
+    def __len__(self):
+        return len(self._loader)
+
+    def __iter__(self):
+        vqvae = self._vqvae
+        device = vqvae.device
+        for x, y in self._loader:
+            was_training = vqvae.training
+            vqvae.eval()  # frozen
+            try:
+                codes = vqvae.encode_codes(x.to(device))
+            finally:
+                vqvae.train(was_training)
+            yield codes, y
+
+
+def code_loaders(vqvae, loaders):
+    """Wraps a tuple of loaders (train, eval): each batch (x, y) becomes (vqvae.encode_codes(x), y), encoded by the frozen
+    VQ-VAE in eval mode on its device — code images (N, 1, h, w) at the levels j / (n_embeddings - 1), the input of a model
+    with `input_codes` and the target of `categorical_loss`."""
+    return tuple(_CodeLoader(vqvae, loader) for loader in loaders)
