@@ -139,6 +139,23 @@ int pg_conv2d_mfma_dual(const float* in, const float* wfrag, float* out, float* 
  * pg_conv2d_mfma_gate reads (one wave then owns both operands of its gate channels); `out` is still written in natural order. */
 #define PG_CONV_FMT_B3_GATE 3
 int pg_conv_mfma_supported(int Cin, int Cout, int T, int OH, int OW, int IW, int hr, int hc);
+/* Host only (no device call): which bf16x3 kernel instantiation a PG_CONV_FMT_B3 launch of this problem takes and how it is laid out —
+ * the answer of the one route function the launch itself, pg_conv_dual_ok and pg_conv_gate_fusable read (csrc/conv_b3.hip: b3_route).
+ * flags: PG_B3R_* (which optional operands the launch has); gate: 0 or 1 + PG_GATE_*. Fills out[0 .. PG_B3_ROUTE_INTS): kernel id (0 staged,
+ * 1 1x1, 2 pipelined, 3 overlapped), GELU instantiation, MT, NT, CG, MS, GT, waves, staging slots per thread, two tiles per workgroup,
+ * grid x, grid y, block size, LDS bytes, then TR, tile_h, tile_w, plane16, tiles_per_img, CIB, cgs, groups, ksteps, wslab4, xslots,
+ * dump16, w_off16, ep_off, b_off, res_scale, "same residual twice" folded, min_dr, min_dc, g_tapoff[20], g_cg[20]. Returns 0, or the
+ * status the launch would return (PG_ESHAPE) with the same message; PG_EINVAL for a null pointer, a short array or a bad dimension. */
+#define PG_B3R_RES 1            /* res given */
+#define PG_B3R_RES2 2           /* res2 given */
+#define PG_B3R_RES2_SAME 4      /* ... and it is the same tensor as res */
+#define PG_B3R_RES_STRIDED 8    /* res is a channel slice of a wider tensor */
+#define PG_B3R_DACT_SRC 16      /* a derivative source is given */
+#define PG_B3R_DUAL 32          /* pg_conv2d_mfma_dual's second output */
+#define PG_B3R_IN_MISALIGNED 64 /* `in` is not 8-byte aligned */
+#define PG_B3_ROUTE_INTS 73
+int pg_conv_b3_route(int N, int Cin, int IH, int IW, int Cout, int OH, int OW, int T, const int* tap_dr, const int* tap_dc,
+                     int in_act, int dact, int out_act, int gate, int flags, int* out, int out_len);
 /* floats pg_pack_conv_weight_frag writes for K_channels contracted into M_channels over T taps */
 size_t pg_conv_frag_floats(int K_channels, int M_channels, int T, int fmt);
 /* wfrag[chunk][g*T + t][m][lane] = Wsel[64 chunk + 16 m + (lane & 15)][4 g + (lane >> 4)][t], with

@@ -552,17 +552,14 @@ int check_dims(const char* who, int N, int heads, int L, int dk, int dv, int str
 // d_k = d_v = 4 (ImageGPT) runs on the matrix cores (attention_mfma.hip); PG_ATTN_MFMA=0 forces the
 // VALU row-owner kernels above (A/B measurements, tests of both paths).
 static bool use_mfma_attention() {
-  static const bool on = []() {
-    const char* e = PG_AB_ENV("PG_ATTN_MFMA");
-    return !(e && e[0] == '0');
-  }();
+  static const bool on = PG_AB_ON("PG_ATTN_MFMA");
   return on;
 }
 
 // launch `which` on whichever kernel family covers the shape
 static int launch_any(int which, AttnArgs& a, hipStream_t st) {
   // ab library: PG_ATTN_MFMA_MASK = bit mask of the kernels allowed on the matrix-core family (1 forward, 2 dQ, 4 dK/dV)
-  static const int mask = []() { const char* e = PG_AB_ENV("PG_ATTN_MFMA_MASK"); return e ? atoi(e) : 7; }();
+  static const int mask = PG_AB_INT("PG_ATTN_MFMA_MASK", 7);
   const int bit = which == K_FWD ? 1 : (which == K_DQ ? 2 : 4);
   if (use_mfma_attention() && (mask & bit) && pg_attn_mfma_launch(which, a, st) == 1) return 0;
   return launch_attn(which, a, st);

@@ -1021,7 +1021,7 @@ int pg_attn_k4_launch(int which, const PgAttnArgs& a, hipStream_t st);  // atten
 // pg_attn_fused_bwd(0) selects the two-kernel backward, whose results are bit-reproducible
 #include <atomic>
 static std::atomic<int>& fused_bwd_flag() {
-  static std::atomic<int> flag([]() { const char* e = PG_AB_ENV("PG_ATTN_FUSED_BWD"); return (e && e[0] == '0') ? 0 : 1; }());
+  static std::atomic<int> flag(PG_AB_ON("PG_ATTN_FUSED_BWD") ? 1 : 0);
   return flag;
 }
 static bool pg_attn_fused_bwd_enabled() { return fused_bwd_flag().load(std::memory_order_relaxed) != 0; }
@@ -1206,7 +1206,7 @@ int pg_attn_mfma_launch(int which, const PgAttnArgs& a0, hipStream_t st) {
     if (!pg_attn_fused_bwd_enabled()) return 0;
     if (a0.dk_dim != 4 || a0.dv_dim != 4) {
       // d_k = 4, d_v = 16 / 32 (PixelSNAIL): attn_bwd_k4_kernel (round 4); PG_ATTN_FUSED_BWD_K4=0 for A/B
-      static const bool k4_fused = []() { const char* e = PG_AB_ENV("PG_ATTN_FUSED_BWD_K4"); return !(e && e[0] == '0'); }();
+      static const bool k4_fused = PG_AB_ON("PG_ATTN_FUSED_BWD_K4");
       return k4_fused ? pg_attn_k4_launch(which, a0, st) : 0;
     }
   }
@@ -1219,16 +1219,13 @@ int pg_attn_mfma_launch(int which, const PgAttnArgs& a0, hipStream_t st) {
   // dK/dV: 10 planes; plus the ones chunk
   // dK/dV score tile on the bf16x3 MFMA (default; PG_ATTN_DKV_BF16=0 selects the all-fp32 variant:
   // measured 0.534-0.545 ms vs 0.515-0.521 ms per launch at batch 1024)
-  static const bool dkv_bf16 = []() { const char* e = PG_AB_ENV("PG_ATTN_DKV_BF16"); return !(e && e[0] == '0'); }();
+  static const bool dkv_bf16 = PG_AB_ON("PG_ATTN_DKV_BF16");
   const size_t planes = which == PG_ATTN_BWD ? 21
                         : which == PG_ATTN_DKV ? (dkv_bf16 ? 18 : 10) : (which == PG_ATTN_DQ ? 20 : 12);
   int wcfg[3];
   attn_waves(wcfg);
-  static const int bwd_waves = []() {
-    const char* e = PG_AB_ENV("PG_ATTN_BWD_WAVES");
-    const int v = e ? atoi(e) : 8;
-    return v >= 1 && v <= 8 ? v : 8;
-  }();
+  static const int bwd_waves_env = PG_AB_INT("PG_ATTN_BWD_WAVES", 8);
+  const int bwd_waves = bwd_waves_env >= 1 && bwd_waves_env <= 8 ? bwd_waves_env : 8;
   int W = which == PG_ATTN_BWD ? bwd_waves : wcfg[which];
   // fused backward: + 1 KB of transposition scratch per wave
   const size_t shmem = planes * (size_t)a.lp * sizeof(float) + (which == PG_ATTN_BWD ? 8 * 1024 : 16);

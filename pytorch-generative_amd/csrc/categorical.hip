@@ -262,7 +262,7 @@ __global__ void __launch_bounds__(CAT_THREADS) cat_sample_kernel(const float* __
 int cat_plan(int K, int HW, int vec_ok, int& S, int& vec) {
   vec = (vec_ok && HW % 4 == 0) ? 4 : 1;
   // A/B (PG_VARIANT=ab builds only): classes a lane keeps at least
-  static const int per_lane = []() { const char* e = PG_AB_ENV("PG_CAT_CLASSES_PER_LANE"); return e ? atoi(e) : 0; }();
+  static const int per_lane = PG_AB_INT("PG_CAT_CLASSES_PER_LANE", 0);
   const int keep = per_lane >= 4 ? per_lane : CAT_CLASSES_PER_LANE;
   const int cap = per_lane >= 4 ? 64 : CAT_MAX_SPLIT;  // a sweep goes all the way
   S = 1;

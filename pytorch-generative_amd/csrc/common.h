@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 
 #include "../../include/pg_hip.h"
 
@@ -229,3 +230,19 @@ __device__ __forceinline__ void pg_stage_rows_vec4(float* __restrict__ lds, int 
 #else
 #define PG_AB_ENV(name) ((const char*)nullptr)
 #endif
+// The three shapes a switch takes (each call site keeps its value in a function-local static): on unless the variable starts with '0';
+// off unless it starts with `on`; an integer with a default. (A switch that carries a list — PG_CONV_B3_CAPS, PG_ATTN_WAVES,
+// PG_BLOCK_GRID — is parsed from PG_AB_ENV where it is read.)
+#define PG_AB_ON(name) ([]() { const char* e_ = PG_AB_ENV(name); return !(e_ && e_[0] == '0'); }())
+#define PG_AB_OFF(name, on) ([]() { const char* e_ = PG_AB_ENV(name); return e_ && e_[0] == (on); }())
+#define PG_AB_INT(name, dflt) ([]() { const char* e_ = PG_AB_ENV(name); return e_ ? atoi(e_) : (dflt); }())
+
+// Extent of a tap list (host): smallest row / column offset and the spans max - min, i.e. the halo a tile needs.
+static inline void pg_tap_extent(int T, const int* dr, const int* dc, int& min_dr, int& hr, int& min_dc, int& hc) {
+  int a0 = dr[0], a1 = dr[0], b0 = dc[0], b1 = dc[0];
+  for (int t = 1; t < T; ++t) {
+    a0 = dr[t] < a0 ? dr[t] : a0; a1 = dr[t] > a1 ? dr[t] : a1;
+    b0 = dc[t] < b0 ? dc[t] : b0; b1 = dc[t] > b1 ? dc[t] : b1;
+  }
+  min_dr = a0; hr = a1 - a0; min_dc = b0; hc = b1 - b0;
+}

@@ -22,6 +22,7 @@
 // Workgroups are persistent like conv_mfma's: (tile, channel chunk) steps with the next step's
 // loads in flight under the MFMA loop.
 #include "conv_b3_kernels.h"
+#include "conv_b3.h"
 
 // conv_b3_gelu.hip: the same launch on the instantiations that carry the GELU paths
 void pg_b3_dispatch_gelu(const B3Args& a, const B3Launch& l, hipStream_t st);
@@ -93,7 +94,6 @@ inline int b3_chunks(int M) { return (M + B3_CO_CHUNK - 1) / B3_CO_CHUNK; }
 struct B3Plan {
   int ok, CIB, cgs, groups, ksteps, MT;
   size_t w_bytes;
-  int w9;  // the plan needs the 9-weight-slot instantiation (conv_b3_kernel<.., W9 = true>)
   int px_cap;     // staged tile pixels (with halo) this plan's LDS budget assumes: 0 = the default for T (B3_PX_CAP), or the smaller
                   // tile (336) that lets a larger channel chunk fit (round 5)
   int pipelined;  // set ONLY by the PG_CONV_B3P branch of b3_plan: conv_b3p_kernel takes the launch (the generic planner can
@@ -107,21 +107,21 @@ constexpr int B3_PX_CAP = 352;  // tile pixels (with halo) the LDS plan assumes 
 // chunk, K steps of 4 groups. ok = 0: the fp32-MFMA kernel takes the problem.
 B3Plan b3_plan(int Kc, int M, int T) {
   B3Plan best = {};
-  static const bool on = []() { const char* e = PG_AB_ENV("PG_CONV_B3"); return !(e && e[0] == '0'); }();
+  static const bool on = PG_AB_ON("PG_CONV_B3");
   if (!on || Kc % 8 != 0 || Kc < 16 || M < 16 || T < 1) return best;
   const int MT = b3_mt(M);
   const int px = T == 1 ? 256 : B3_PX_CAP;
   // 4 taps with >= 64 output channels: one 8-channel group x 4 taps = exactly one K step of 32 per chunk — the format
   // of the pipelined kernel (conv_b3p_kernel: double-buffered 14.6 KB x tile + 12 KB weight slab). PG_CONV_B3P=0 keeps
   // the 16-channel chunks of conv_b3_kernel (A/B).
-  static const bool p_on = []() { const char* e = PG_AB_ENV("PG_CONV_B3P"); return !(e && e[0] == '0'); }();
+  static const bool p_on = PG_AB_ON("PG_CONV_B3P");
   // (one output chunk only: with 128+ output channels the wide conv_b3_kernel, whose two chunks share ONE staged x tile,
   // measured faster — 247 against 282 us on the 2x2 64 -> 128 at N = 512 — while 64 -> 64 runs 119 -> 108 us here)
   // Round 5: also several output chunks when their number is odd-sized for the wide kernel (M % 128 != 0, e.g. PixelCNN++'s 160 / 320
   // filters): conv_b3_kernel then runs one chunk per workgroup as well, so both stage x once per chunk. PG_CONV_B3P_MULTI=0 for A/B.
-  static const bool pm_on = []() { const char* e = PG_AB_ENV("PG_CONV_B3P_MULTI"); return !(e && e[0] == '0'); }();
+  static const bool pm_on = PG_AB_ON("PG_CONV_B3P_MULTI");
   if (p_on && on && T == 4 && MT == 4 && (M <= B3_CO_CHUNK || (pm_on && M % (2 * B3_CO_CHUNK) != 0)) && Kc % 8 == 0 && Kc >= 16) {
-    B3Plan pp = {1, 8, 1, 4, 1, 4, (size_t)MT * 3 * 1024, 0, 0, 1};
+    B3Plan pp = {1, 8, 1, 4, 1, 4, (size_t)MT * 3 * 1024, 0, 1};
     return pp;
   }
   double best_cost = 1e30;
@@ -155,30 +155,18 @@ B3Plan b3_plan(int Kc, int M, int T) {
     const size_t scratch = (size_t)4 * 16 * 68 * 4;  // per-wave epilogue scratch of one chunk's four waves
     if (xb + wb_s + scratch + 1024 > 80 * 1024) continue;
     if ((long)cgs * pxp > (long)B3_XS * B3_THREADS) continue;
-    // (round 4 and before: the slab went through 6 float4 registers per thread, so ksteps * MT * 192 <= 6 * 256 bounded the plan. The
-    // slab is moved by LDS-DMA now — no such bound; PG_CONV_B3_WSLOTS=1 in the ab library restores it for A/B)
-    static const bool wslots = []() { const char* e = PG_AB_ENV("PG_CONV_B3_WSLOTS"); return e && e[0] == '1'; }();
-    if (wslots && (long)ksteps * MT * 192 > (long)B3_WS * B3_THREADS) continue;
+    // (no bound from the weight slab: since round 5 it is moved by LDS-DMA, not through per-thread registers)
     const double cost = (double)ksteps / CIB + 0.002 / CIB + (pass ? 1e-4 : 0.0);  // MFMA work per channel, then fewer steps, then the full tile
     if (cost < best_cost) {
       best_cost = cost;
-      best = {1, CIB, cgs, groups, ksteps, MT, wb_s, 0, pass ? pxp : 0, 0};
+      best = {1, CIB, cgs, groups, ksteps, MT, wb_s, pass ? pxp : 0, 0};
     }
-  }
-  static const bool w9_on = []() { const char* e = PG_AB_ENV("PG_CONV_B3_W9"); return !(e && e[0] == '0'); }();
-  if (!best.ok && w9_on && MT == 4 && Kc % 8 == 0) {
-    // nothing fits 6 weight slots per thread: one 8-channel group per chunk with 9 slots (3x3, >= 64 output channels)
-    const int cgs = 1, groups = T, ksteps = (groups + 3) / 4;
-    const size_t xb = (size_t)cgs * 3 * px * 16, wb = (size_t)ksteps * MT * 3 * 1024;
-    if (ksteps <= 5 && groups <= B3_MAXG && xb + wb + (size_t)4 * 16 * 68 * 4 + 1024 <= 80 * 1024 &&
-        (long)cgs * px <= 2L * B3_THREADS && (long)ksteps * MT * 192 <= 9L * B3_THREADS)
-      best = {1, 8, cgs, groups, ksteps, MT, wb, 1, 0, 0};
   }
   return best;
 }
 
 // rows per tile: as many as fit 256 output pixels and a staged tile (with halo) of at most `cap` pixels; cap = 0: the
-// format-level assumption (B3_PX_CAP). pg_b3_conv passes the cap its launch's real LDS budget allows (round 4): the
+// format-level assumption (B3_PX_CAP). The route passes the cap its launch's real LDS budget allows (round 4): the
 // plan is made for 352 pixels whatever the image, but a plan with one channel group leaves room for more — on 64-wide
 // rows a 3x3 then takes 4 output rows per tile (6 staged: 396 pixels) instead of 3 (5 staged), and the tile is a full
 // 256 pixels instead of 192.
@@ -192,13 +180,282 @@ int b3_rows(int T, int OH, int OW, int hr, int hc, int cap = 0) {
   return (OH + nt_rows - 1) / nt_rows;
 }
 
-void tap_extent(int T, const int* dr, const int* dc, int& min_dr, int& hr, int& min_dc, int& hc) {
-  int a0 = dr[0], a1 = dr[0], b0 = dc[0], b1 = dc[0];
-  for (int t = 1; t < T; ++t) {
-    a0 = dr[t] < a0 ? dr[t] : a0; a1 = dr[t] > a1 ? dr[t] : a1;
-    b0 = dc[t] < b0 ? dc[t] : b0; b1 = dc[t] > b1 ? dc[t] : b1;
+// Rows per tile the format-level plan gives the shape, 0 = the format does not take it: the first thing b3_route checks and (with its
+// A/B pixel floor) all that pg_b3_applicable asks.
+int b3_plan_rows(const B3Plan& pl, int T, int OH, int OW, int hr, int hc) {
+  if (!pl.ok || OH * OW < 16 || OW > 256) return 0;
+  const int TR = b3_rows(T, OH, OW, hr, hc, pl.px_cap);
+  return TR >= 1 ? TR : 0;
+}
+
+// The 1x1 kernel's format condition: one tap, one K step, the weight slab of an output chunk <= 24 KB (up to 64 input channels).
+size_t b3_pw_wbytes(const B3Plan& pl, int Cin) { return (size_t)(Cin / pl.CIB) * pl.MT * 3 * 1024; }
+bool b3_pw_format(const B3Plan& pl, int Cin, int T) { return pl.ok && T == 1 && pl.ksteps == 1 && b3_pw_wbytes(pl, Cin) <= 24 * 1024; }
+
+// ---- the route: ONE function decides which kernel takes a problem and how it is laid out -----------------------------------------
+// b3_route(problem) -> route is pure host arithmetic: the launch (pg_b3_conv), the fusion queries (pg_b3_dual_ok, pg_b3_gate_fusable)
+// and the host-only export pg_conv_b3_route all read the same answer.
+struct B3Problem {
+  int N, Cin, IH, IW, Cout, OH, OW, T;
+  const int* tap_dr;
+  const int* tap_dc;
+  int in_act, dact, out_act;
+  int gate;           // 0, or 1 + PG_GATE_*
+  bool res, res2;     // residual operands given
+  bool res2_same;     // res2 is the same tensor as res, same batch stride (PixelCNN's x + (x + net(x)), the two equal skip gradients)
+  bool res_strided;   // res is a channel slice of a wider tensor (batch stride != Cout OH OW)
+  bool dact_src;      // a derivative source is given
+  bool dual;          // the "dual" data gradient (a second output)
+  bool in_aligned8;   // `in` is 8-byte aligned
+};
+
+struct B3Route {
+  B3Launch launch;
+  // B3Args' geometry and LDS offsets (same names)
+  int TR, tile_h, tile_w, plane16, tiles_per_img, CIB, cgs, groups, ksteps, wslab4, xslots, dump16, w_off16, ep_off, b_off;
+  float res_scale;
+  bool res2_folded;  // both residual operands are one tensor: the kernel gets res only, added res_scale = 2 times
+  int min_dr, min_dc;
+  int g_tapoff[B3_MAXG], g_cg[B3_MAXG];
+  char msg[192];     // why the route refuses (the launch's error text)
+};
+
+#define B3_ROUTE_REQUIRE(cond, code, ...)              \
+  do {                                                 \
+    if (!(cond)) {                                     \
+      snprintf(r.msg, sizeof(r.msg), __VA_ARGS__);     \
+      return (code);                                   \
+    }                                                  \
+  } while (0)
+
+// per K group g = (tap t, channel group cg of the chunk): where its B fragments live in the staged tile
+void b3_group_table(const B3Problem& p, const B3Plan& pl, B3Route& r) {
+  for (int g = 0; g < pl.groups; ++g) {
+    const int t = g / pl.cgs;
+    r.g_tapoff[g] = (p.tap_dr[t] - r.min_dr) * r.tile_w + (p.tap_dc[t] - r.min_dc);
+    r.g_cg[g] = g - t * pl.cgs;
   }
-  min_dr = a0; hr = a1 - a0; min_dc = b0; hc = b1 - b0;
+}
+
+void b3_set_tile(const B3Problem& p, int TR, int hr, int hc, B3Route& r) {
+  r.TR = TR; r.tile_h = TR + hr; r.tile_w = p.OW + hc;
+  r.plane16 = ((r.tile_h * r.tile_w + 15) / 16) * 16;
+  r.tiles_per_img = (p.OH + TR - 1) / TR;
+}
+
+// persistent workgroups: `resident` of them in total, a multiple of the row tiles per image, at most one per unit of work
+dim3 b3_grid(long resident, int chunks_y, int tiles_per_img, long units) {
+  long want = resident / chunks_y;
+  if (want < tiles_per_img) want = tiles_per_img;
+  long gx = (want / tiles_per_img) * tiles_per_img;
+  if (gx > units) gx = units;
+  return dim3((unsigned)gx, (unsigned)chunks_y);
+}
+
+// ---- the 1x1 kernel (conv_b3_pw_kernel): no LDS x tile. LDS = weight slab | 4 x epilogue scratch | bias
+// Measured forward, old -> new kernel (tools/exp/pw_ab.py): 64 -> 64 at N = 512, 32x32: 76.8 -> 65.4 us (4.1 TB/s of
+// algorithmic traffic), with ELU on both sides 83.0 -> 74.8; 64 -> 32 at N = 1024, 28x28: 84.1 -> 64.7; 32 -> 64:
+// 99.4 -> 88.7. 128 input channels are compute-heavy enough for the staged kernel: 182 -> 197 us, left there.
+bool b3_route_pw(const B3Problem& p, const B3Plan& pl, bool ms, B3Route& r) {
+  static const bool pw_on = PG_AB_ON("PG_CONV_B3_PW");
+  // both residual operands the SAME tensor: one stream, added twice
+  const bool ms_pw = p.res2_same ? (p.dact_src || p.res_strided) : ms;  // (dual: res + dact_src => ms)
+  if (!(pw_on && !p.gate && (!ms_pw || pl.MT == 4) && b3_pw_format(pl, p.Cin, p.T) && p.tap_dr[0] == 0 && p.tap_dc[0] == 0 &&
+        p.IH == p.OH && p.IW == p.OW && (p.OH * p.OW) % 2 == 0 && p.in_aligned8))
+    return false;
+  r.ep_off = (int)(b3_pw_wbytes(pl, p.Cin) / 4);
+  r.b_off = r.ep_off + PW_WAVES * 16 * PW_EPS;
+  const size_t shmem = ((size_t)r.b_off + B3_CO_CHUNK + 4) * sizeof(float);
+  const int chunks_y = b3_chunks(p.Cout);
+  const long items = (long)p.N * ((p.OH * p.OW + 31) / 32);
+  // resident workgroups per CU: what the registers allow (waves per SIMD = 4 / 3 / 2 for 1 / 2 / 3-4 output
+  // tiles of 16 channels), LDS permitting
+  // (round 6: four output tiles WITHOUT the multi-stream epilogue hold their A fragments in halves: 167 registers, three too)
+  const int by_regs = pl.MT == 1 ? 4 : ((pl.MT == 2 || (pl.MT == 4 && !ms_pw && !r.launch.gelu)) ? 3 : 2);
+  const int by_lds = (int)((160 * 1024) / shmem);
+  const int per_cu = by_lds < by_regs ? by_lds : by_regs;
+  long gx = (long)256 * per_cu / chunks_y;
+  if (gx > (items + PW_WAVES - 1) / PW_WAVES) gx = (items + PW_WAVES - 1) / PW_WAVES;
+  if (gx < 1) gx = 1;
+  if (p.res2_same) { r.res2_folded = true; r.res_scale = 2.f; }
+  r.launch.kernel = B3K_PW;
+  r.launch.MT = pl.MT;
+  r.launch.ms = ms_pw ? 1 : 0;
+  r.launch.grid = dim3((unsigned)gx, (unsigned)chunks_y);
+  r.launch.shmem = shmem;
+  return true;
+}
+
+// conv_b3_kernel, T > 1: the staged tile may be larger than the format-level 352 pixels if THIS launch's LDS has the room
+// (one 64-channel chunk per workgroup assumed here; the wide kernel's LDS holds two weight slabs: it keeps the plan's tile)
+int b3_bigtile_rows(const B3Problem& p, const B3Plan& pl, int hr, int hc, int TR) {
+  static const bool big_on = PG_AB_ON("PG_CONV_B3_BIGTILE");
+  if (!(p.T > 1 && !pl.pipelined)) return TR;
+  const long fixed = (long)pl.w_bytes + 4L * 16 * 68 * 4 + (B3_CO_CHUNK + B3_MAXG + 4) * 4 + 16 * 16 + 512;
+  long cap = (80L * 1024 - fixed) / ((long)pl.cgs * 48);        // 16-byte entries per (group, piece) plane
+  const long slot_cap = (long)B3_XS * B3_THREADS / pl.cgs;  // staging slots per thread
+  if (cap > slot_cap) cap = slot_cap;
+  cap = (cap / 16) * 16;
+  const bool wide = pl.MT == 4 && p.Cout % (2 * B3_CO_CHUNK) == 0;
+  if (big_on && !wide && cap > (pl.px_cap ? pl.px_cap : B3_PX_CAP)) {
+    const int TR2 = b3_rows(p.T, p.OH, p.OW, hr, hc, (int)cap);
+    if (TR2 > TR) TR = TR2;
+  }
+  return TR;
+}
+
+// ---- the pipelined kernel (conv_b3p_kernel): LDS = x[2][3 pieces][plane16] | dump entry | w[2][768] | per-wave epilogue scratch | bias, taps
+int b3_route_pipelined(const B3Problem& p, B3Route& r) {
+  for (int t = 0; t < 4; ++t) r.g_tapoff[t] = (p.tap_dr[t] - r.min_dr) * r.tile_w + (p.tap_dc[t] - r.min_dc);
+  r.xslots = r.tile_h * r.tile_w;
+  const size_t x16 = (size_t)2 * 3 * r.plane16;
+  r.dump16 = (int)x16;
+  r.w_off16 = (int)(((x16 + 1 + 15) / 16) * 16);
+  // waves per workgroup: 8 (a wave owns 32 pixels, 128 registers, four waves per SIMD) unless PG_CONV_B3P_WAVES=4
+  static const int waves = PG_AB_INT("PG_CONV_B3P_WAVES", 8) == 4 ? 4 : 8;
+  const int px = r.TR * p.OW;
+  const int nt = waves == 8 ? (px + 127) / 128 : (px + 63) / 64;   // 16-pixel groups per wave
+  size_t shmem = ((size_t)r.w_off16 + 2 * B3P_W4) * 16;
+  r.ep_off = (int)(shmem / 4);
+  shmem += (size_t)waves * 16 * (nt * 16 + 4) * 4;  // per-wave transposition scratch
+  r.b_off = (int)(shmem / 4);
+  shmem += (B3_CO_CHUNK + 8) * sizeof(float);
+  B3_ROUTE_REQUIRE(shmem <= (size_t)80 * 1024, PG_ESHAPE, "pg_conv2d_mfma(bf16x3, pipelined): %zu B of LDS", shmem);
+  r.launch.kernel = B3K_PIPELINED;
+  r.launch.MT = 4;
+  r.launch.nt = nt;
+  r.launch.waves = waves;
+  r.launch.grid = b3_grid(512, b3_chunks(p.Cout), r.tiles_per_img, (long)p.N * r.tiles_per_img);  // 2 workgroups per CU
+  r.launch.shmem = shmem;
+  return 0;
+}
+
+// ---- the overlapped 16-wave kernel (conv_b3q_kernel.h, round 6): >= 64 output channels, any tap count. Its LDS (one
+// workgroup per CU, up to 160 KB) = x tiles [NXT][2 buffers][cgs][3 pieces][plane16] | dump entry | slab ring [2][NCH][768] |
+// bias, K-group table; two output chunks share one x tile when Cout % 128 == 0, otherwise two tiles share one slab.
+// Returns 1 = takes the launch, 0 = does not, < 0 = refused.
+int b3_route_overlapped(const B3Problem& p, const B3Plan& pl, int hr, int hc, B3Route& r) {
+  static const bool q_on = PG_AB_ON("PG_CONV_B3Q");
+  // Measured on MI355X (round 6, tools/exp/q_ab.py, same box, median of 5 x 20 launches, forward; profiles/r06_conv_q_ab.txt):
+  //   two tiles per workgroup (ST): PixelCNN++'s 2x3 160 -> 320 265 -> 243 us, 320 -> 160 301 -> 283 us at batch 64 — taken;
+  //     2x3 160 -> 160 152 -> 160 us and the 16 x 16 level (one 256-pixel tile per image: 96-160 workgroups for 256 CUs) 97 -> 147 us — not;
+  //   two output chunks per workgroup (CG, GatedPixelCNN / PixelSNAIL 64 -> 128): 3-6 % SLOWER than the 8-wave wide kernel on every
+  //     shape (1x1 256 -> 256 446 -> 463 us, 2x1 755 -> 792, 1x2 426 -> 439, 1x3 641 -> 675, 2x2 64 -> 128 392 -> 416): sixteen waves that
+  //     meet at one barrier per K step run their phases in lockstep, and the kernel's ablation (profiles/r06_conv_q_ablation.txt) shows the
+  //     phases ADD UP (MFMA 200 + loads / commit 130 + epilogue 95 + slab DMA 28 + empty K-step loop 100 of 564 us) instead of overlapping:
+  //     the epilogue alone streams at 5.6 TB/s, i.e. at the HBM write rate, while no wave computes. Not taken (PG_CONV_B3Q_CG=1 in the ab
+  //     library runs it for A/B).
+  static const bool q_cg = PG_AB_OFF("PG_CONV_B3Q_CG", '1');
+  const bool stm = p.Cout % (2 * B3_CO_CHUNK) != 0;
+  const int NCH = stm ? 1 : 2, NXT = stm ? 2 : 1, GT = stm ? 512 : 1024;
+  const long tail = (long)(NCH * B3_CO_CHUNK + B3_MAXG + 4) * 4 + 16 * 16 + 256;
+  long cap = (160L * 1024 - 2L * NCH * B3Q_SLAB16 * 16 - tail) / ((long)NXT * 2 * pl.cgs * 48);
+  cap = (cap / 16) * 16;
+  const bool q_shape = !p.gate && (stm ? (p.T >= 6 && (p.Cin >= 256 || p.Cout >= 256)) : q_cg);
+  const int TRq = (q_on && q_shape && pl.MT == 4 && !pl.pipelined && cap >= 64) ? b3_rows(p.T, p.OH, p.OW, hr, hc, (int)cap) : 0;
+  if (TRq < 1) return 0;
+  const int xs = (pl.cgs * (TRq + hr) * (p.OW + hc) + GT - 1) / GT;
+  // at least 6 of the 8 pixel slices of 32 must be busy (small images stay on the 4-wave kernels), and in ST mode the
+  // batch must provide pairs of images
+  if (!(xs <= 2 && TRq * p.OW >= 192 && (!stm || p.N >= 2) && (p.OH + TRq - 1) / TRq >= 2)) return 0;
+  b3_set_tile(p, TRq, hr, hc, r);
+  b3_group_table(p, pl, r);
+  r.xslots = pl.cgs * r.tile_h * r.tile_w;
+  const size_t x16 = (size_t)NXT * 2 * pl.cgs * 3 * r.plane16;
+  r.dump16 = (int)x16;
+  r.w_off16 = (int)(((x16 + 1 + 15) / 16) * 16);
+  size_t shmem = ((size_t)r.w_off16 + 2 * NCH * B3Q_SLAB16) * 16;
+  r.ep_off = 0;
+  r.b_off = (int)(shmem / 4);
+  shmem += (size_t)(NCH * B3_CO_CHUNK + B3_MAXG + 4) * sizeof(float);
+  B3_ROUTE_REQUIRE(shmem <= (size_t)160 * 1024, PG_ESHAPE, "pg_conv2d_mfma(bf16x3, overlapped): %zu B of LDS", shmem);
+  r.launch.kernel = B3K_OVERLAPPED;
+  r.launch.MT = 4;
+  r.launch.xslots_per_thread = xs;
+  r.launch.two_tiles = stm ? 1 : 0;
+  // 1 workgroup per CU; ST: a workgroup takes images in pairs
+  r.launch.grid = b3_grid(256, stm ? b3_chunks(p.Cout) : p.Cout / (2 * B3_CO_CHUNK), r.tiles_per_img,
+                          (stm ? (long)(p.N + 1) / 2 : (long)p.N) * r.tiles_per_img);
+  r.launch.shmem = shmem;
+  return 1;
+}
+
+// ---- the staged kernel (conv_b3_kernel): LDS = x[cgs][3 pieces][plane16] | dump entry | CG weight slabs | 4 CG x epilogue scratch |
+// bias, K-group table. Narrow (CG = 1, 4 waves) or wide (CG = 2, 8 waves: two output chunks share one staged x tile).
+int b3_route_staged(const B3Problem& p, const B3Plan& pl, bool ms, B3Route& r) {
+  b3_group_table(p, pl, r);
+  r.xslots = pl.cgs * r.tile_h * r.tile_w;
+  const size_t x16 = (size_t)pl.cgs * 3 * r.plane16;
+  r.dump16 = (int)x16;              // one spare 16-byte entry (+ padding to a 256-byte boundary)
+  r.w_off16 = (int)(((x16 + 1 + 15) / 16) * 16);
+  // wide workgroups: default; PG_CONV_B3_WIDE=0 for A/B
+  static const bool wide_on = PG_AB_ON("PG_CONV_B3_WIDE");
+  const int CG = ((wide_on || p.gate) && pl.MT == 4 && p.Cout % (2 * B3_CO_CHUNK) == 0) ? 2 : 1;
+  size_t shmem = (size_t)r.w_off16 * 16 + pl.w_bytes * CG;
+  r.ep_off = (int)(shmem / 4);
+  shmem += (size_t)4 * CG * 16 * 68 * 4;
+  r.b_off = (int)(shmem / 4);
+  shmem += (B3_CO_CHUNK * CG + B3_MAXG + 4) * sizeof(float);
+  B3_ROUTE_REQUIRE(shmem <= (size_t)(CG == 1 ? 80 : 160) * 1024, PG_ESHAPE, "pg_conv2d_mfma(bf16x3): %zu B of LDS", shmem);
+  B3_ROUTE_REQUIRE(!ms || pl.MT == 4, PG_ESHAPE,
+                   "pg_conv2d_mfma_ex(bf16x3): the multi-stream epilogue is instantiated for >= 64 output channels");
+  B3_ROUTE_REQUIRE(!p.gate || (CG == 2 && !ms), PG_ESHAPE, "pg_conv2d_mfma_gate: not the wide kernel's plain epilogue");
+  r.launch.kernel = B3K_STAGED;
+  r.launch.MT = pl.MT;
+  r.launch.nt = (r.TR * p.OW + 63) / 64;
+  r.launch.CG = CG;
+  r.launch.ms = ms ? 1 : 0;
+  r.launch.gate = p.gate ? 1 : 0;
+  // resident workgroups: 2 per CU (4 waves) / 1 per CU (8 waves)
+  r.launch.grid = b3_grid(CG == 1 ? 512 : 256, b3_chunks(p.Cout) / CG, r.tiles_per_img, (long)p.N * r.tiles_per_img);
+  r.launch.shmem = shmem;
+  return 0;
+}
+
+int b3_route(const B3Problem& p, B3Route& r) {
+  r = B3Route{};
+  r.res_scale = 1.f;
+  int hr, hc;
+  pg_tap_extent(p.T, p.tap_dr, p.tap_dc, r.min_dr, hr, r.min_dc, hc);
+  const B3Plan pl = b3_plan(p.Cin, p.Cout, p.T);
+  int TR = b3_plan_rows(pl, p.T, p.OH, p.OW, hr, hc);
+  B3_ROUTE_REQUIRE(TR >= 1, PG_ESHAPE, "pg_conv2d_mfma(bf16x3): shape not covered");
+  r.CIB = pl.CIB; r.cgs = pl.cgs; r.groups = pl.groups; r.ksteps = pl.ksteps;
+  r.wslab4 = pl.ksteps * pl.MT * 192;
+  // the instantiations with the GELU paths live in conv_b3_gelu.hip (conv_b3_kernels.h says why)
+  r.launch.gelu = p.in_act == PG_ACT_GELU || p.out_act == PG_ACT_GELU || p.dact == PG_ACT_GELU;
+  // multi-stream epilogue (two residuals, residual + derivative, batch-strided residual): own instantiations
+  const bool ms = p.res2 || (p.res && p.dact_src) || (p.res && p.res_strided);
+  if (b3_route_pw(p, pl, ms, r)) return 0;
+  B3_ROUTE_REQUIRE(!p.dual, PG_ESHAPE, "pg_conv2d_mfma_dual: shape not on the 1x1 kernel (pg_conv_dual_ok)");
+  TR = b3_bigtile_rows(p, pl, hr, hc, TR);
+  b3_set_tile(p, TR, hr, hc, r);
+  B3_ROUTE_REQUIRE(!p.gate || (!pl.pipelined && pl.MT == 4 && p.Cout % (2 * B3_CO_CHUNK) == 0 && !r.launch.gelu), PG_ESHAPE,
+                   "pg_conv2d_mfma_gate: the fused gate needs the wide bf16x3 kernel with a multiple of 128 output channels");
+  // (Round 6, measured and NOT shipped: a row-ring forward kernel with register-resident weights for the 64-channel 4-tap layers —
+  // tools/exp/rejected/conv_b3r_kernel.h (its README has the routing block that stood here) — parity green, 225 against 235 us on the
+  // 2x2 64 -> 64 at batch 1024, PixelSNAIL +0.3 %: profiles/r06_conv_ring_forward_ab.txt.)
+  if (pl.pipelined && r.tile_h * r.tile_w <= B3P_PX) return b3_route_pipelined(p, r);
+  const int q = b3_route_overlapped(p, pl, hr, hc, r);
+  if (q) return q < 0 ? q : 0;
+  return b3_route_staged(p, pl, ms, r);
+}
+
+// flags: PG_B3R_* (include/pg_hip.h)
+B3Problem b3_problem(int N, int Cin, int IH, int IW, int Cout, int OH, int OW, int T, const int* tap_dr, const int* tap_dc, int in_act,
+                     int dact, int out_act, int gate, int flags) {
+  B3Problem p;
+  p.N = N; p.Cin = Cin; p.IH = IH; p.IW = IW; p.Cout = Cout; p.OH = OH; p.OW = OW; p.T = T;
+  p.tap_dr = tap_dr; p.tap_dc = tap_dc;
+  p.in_act = in_act; p.dact = dact; p.out_act = out_act; p.gate = gate;
+  p.res = flags & PG_B3R_RES; p.res2 = flags & PG_B3R_RES2; p.res2_same = flags & PG_B3R_RES2_SAME;
+  p.res_strided = flags & PG_B3R_RES_STRIDED; p.dact_src = flags & PG_B3R_DACT_SRC; p.dual = flags & PG_B3R_DUAL;
+  p.in_aligned8 = !(flags & PG_B3R_IN_MISALIGNED);
+  return p;
+}
+// the problem a fusion query stands for: no batch, no operands yet — one image, input = output size, aligned
+B3Problem b3_query_problem(int Cin, int Cout, int OH, int OW, int T, const int* tap_dr, const int* tap_dc, int gate, int flags) {
+  return b3_problem(1, Cin, OH, OW, Cout, OH, OW, T, tap_dr, tap_dc, PG_ACT_NONE, PG_ACT_NONE, PG_ACT_NONE, gate, flags);
 }
 
 }  // namespace
@@ -209,16 +466,17 @@ static long long* g_b3_prof = nullptr;
 PG_EXPORT void pg_b3_set_prof(void* p) { g_b3_prof = (long long*)p; }
 #endif
 
-// ---- interface used by conv_mfma.hip's exported entry points --------------------------------------
+// ---- interface used by conv_mfma.hip's exported entry points (conv_b3.h) --------------------------------------
+// Not asked of b3_route: the caller has the extents of the tap list only, not the taps, and no batch. It shares the route's first
+// check (b3_plan_rows); every later check of the route that can refuse a plain problem is an LDS bound the plan already guarantees.
 int pg_b3_applicable(int Kc, int M, int T, int OH, int OW, int hr, int hc) {
   // Round 5: images down to 16 pixels (4 x 4) run here as well — a bf16x3 tile lives inside one image, so an 8 x 8 image fills a
   // quarter of the 256-pixel tile, and the six bf16 MFMAs per product still beat the fp32-MFMA kernel's multi-image tiles:
   // PixelCNN++ (its 8 x 8 level: 320-channel 2x3 / 2x2 convolutions) 606 -> 659 images/s, VD-VAE +2.7 %, beta-VAE +1.6 %
   // (same box, ab library; PG_CONV_B3_MIN_PX=256 there restores the round-4 routing)
-  static const int min_px = []() { const char* e = PG_AB_ENV("PG_CONV_B3_MIN_PX"); const int v = e ? atoi(e) : 16; return v >= 16 ? v : 16; }();
-  if (OW > 256 || OH * OW < min_px) return 0;
-  const B3Plan pl = b3_plan(Kc, M, T);
-  return pl.ok && b3_rows(T, OH, OW, hr, hc, pl.px_cap) >= 1;
+  static const int min_px = PG_AB_INT("PG_CONV_B3_MIN_PX", 16);
+  if (OH * OW < (min_px >= 16 ? min_px : 16)) return 0;
+  return b3_plan_rows(b3_plan(Kc, M, T), T, OH, OW, hr, hc) >= 1;
 }
 
 size_t pg_b3_frag_floats(int Kc, int M, int T) {
@@ -227,19 +485,22 @@ size_t pg_b3_frag_floats(int Kc, int M, int T) {
   return (size_t)b3_chunks(M) * (Kc / pl.CIB) * pl.ksteps * pl.MT * 3 * 64 * 4;
 }
 
-// the 1x1 kernel's multi-stream instantiation takes the launch (the conditions of pg_b3_conv's routing, restated)
+// the dual problem (a 1x1 data gradient with a derivative source and r) routes to the 1x1 kernel's multi-stream instantiation
 int pg_b3_dual_ok(int Cin, int Cout, int OH, int OW) {
-  const B3Plan pl = b3_plan(Cin, Cout, 1);
-  if (!pl.ok || pl.MT != 4 || pl.ksteps != 1 || (OH * OW) % 2 != 0 || OH * OW < 16 || OW > 256) return 0;
-  return (size_t)(Cin / pl.CIB) * pl.MT * 3 * 1024 <= 24 * 1024;
+  const int zero = 0;
+  const B3Problem p = b3_query_problem(Cin, Cout, OH, OW, 1, &zero, &zero, 0, PG_B3R_RES | PG_B3R_DACT_SRC | PG_B3R_DUAL);
+  B3Route r;
+  return b3_route(p, r) == 0 && r.launch.kernel == B3K_PW && r.launch.MT == 4 && r.launch.ms;
 }
 
-int pg_b3_gate_fusable(int Cin, int Cout, int T, int OH, int OW, int hr, int hc) {
-  if (Cout % (2 * B3_CO_CHUNK) != 0 || OW > 256 || OH * OW < 16) return 0;
-  const B3Plan pl = b3_plan(Cin, Cout, T);
-  // (one tap whose weights fit the 1x1 kernel runs without an x tile: pg_b3_conv's routing, restated)
-  if (T == 1 && pl.ok && pl.ksteps == 1 && (size_t)(Cin / pl.CIB) * pl.MT * 3 * 1024 <= 24 * 1024) return 0;
-  return pl.ok && !pl.pipelined && !pl.w9 && pl.MT == 4 && b3_rows(T, OH, OW, hr, hc, pl.px_cap) >= 1;
+// the gated problem routes to the wide kernel's gate instantiation — and the convolution is not one the 1x1 kernel's format takes (one
+// tap whose weights fit its slab runs without an x tile: those keep the standalone gate behind the faster kernel). The second half is
+// the format condition b3_route_pw itself tests, not its launch-only facts (operand alignment, tap position), which a query cannot know.
+int pg_b3_gate_fusable(int Cin, int Cout, int T, int OH, int OW, const int* tap_dr, const int* tap_dc) {
+  const B3Problem p = b3_query_problem(Cin, Cout, OH, OW, T, tap_dr, tap_dc, 1 + PG_GATE_TANH, 0);
+  B3Route r;
+  if (b3_route(p, r) != 0) return 0;
+  return r.launch.kernel == B3K_STAGED && r.launch.CG == 2 && r.launch.gate && !b3_pw_format(b3_plan(Cin, Cout, T), Cin, T);
 }
 
 static int b3_pack_job(B3PackJob& p, float* wfrag, int Cout, int Cin, int T, int transpose, int gate_order = 0) {
@@ -258,7 +519,6 @@ static int b3_pack_job(B3PackJob& p, float* wfrag, int Cout, int Cin, int T, int
   return 0;
 }
 
-// either destination may be null (then only the other orientation is packed)
 int pg_b3_pack2(const float* w, float* wfrag_fwd, float* wfrag_dgrad, int Cout, int Cin, int KH, int KW,
                 int T, const int* tap_u, const int* tap_v, hipStream_t st, int gate_order) {
   B3PackArgs a;
@@ -281,239 +541,88 @@ int pg_b3_pack2(const float* w, float* wfrag_fwd, float* wfrag_dgrad, int Cout, 
   return 0;
 }
 
-// gate != 0 (1 + PG_GATE_*; round 6): the launch must be the wide kernel (Cout % 128 == 0, at most one dense residual) — it then also writes
-// gate_out = gate_res + act(a) * sigmoid(b) for [a | b] = out (+ res); pg_b3_gate_fusable() says beforehand whether a shape qualifies
-int pg_b3_gate_fusable(int Cin, int Cout, int T, int OH, int OW, int hr, int hc);
 int pg_b3_conv(const float* in, const float* wfrag, const float* bias, const float* res, float* out,
                int N, int Cin, int IH, int IW, int Cout, int OH, int OW, int T, const int* tap_dr,
                const int* tap_dc, int in_act, const float* dact_src, int dact, int out_act,
                const float* res2, long res_bs, long res2_bs, hipStream_t st, int gate, const float* gate_res,
                float* gate_out, float* dual_out2) {
-  B3Args a;
-  a.gate = gate; a.gate_res = gate_res; a.gate_out = gate_out;
-  a.out2 = dual_out2;
+  // 1. what only the operands can say
   PG_REQUIRE(!dual_out2 || (res && dact_src && !res2 && !gate && out_act == PG_ACT_NONE && !bias && T == 1), PG_EINVAL,
              "pg_conv2d_mfma_dual: a 1x1 data gradient with a derivative source and r, nothing else");
   PG_REQUIRE(gate == 0 || (gate_out && !res2 && !dact_src && out_act == PG_ACT_NONE &&
                            (gate == 1 + PG_GATE_TANH || gate == 1 + PG_GATE_IDENTITY)), PG_EINVAL,
              "pg_conv2d_mfma_gate: the fused gate takes one residual of the convolution, no second one / derivative / output activation");
-  a.in = in; a.wfrag = wfrag; a.bias = bias; a.res = res; a.dact_src = dact_src; a.out = out;
   PG_REQUIRE(res2 == nullptr || res != nullptr, PG_EINVAL, "pg_conv2d_mfma(bf16x3): res2 without res");
   // the weight slabs are moved by LDS-DMA in 16-byte units (conv_b3_kernel, round 5)
   PG_REQUIRE((((uintptr_t)wfrag) & 15) == 0, PG_EINVAL, "pg_conv2d_mfma(bf16x3): the fragment buffer must be 16-byte aligned");
-  a.res2 = res2;
-  a.res_scale = 1.f;
+  B3Args a;
+  a.in = in; a.wfrag = wfrag; a.bias = bias; a.res = res; a.res2 = res2; a.dact_src = dact_src; a.out = out;
+  a.gate = gate; a.gate_res = gate_res; a.gate_out = gate_out; a.out2 = dual_out2;
   a.res_bs = res_bs > 0 ? res_bs : (long)Cout * OH * OW;
   a.res2_bs = res2_bs > 0 ? res2_bs : (long)Cout * OH * OW;
   a.N = N; a.Cin = Cin; a.IH = IH; a.IW = IW; a.Cout = Cout; a.OH = OH; a.OW = OW; a.T = T;
   a.in_act = in_act; a.dact = dact; a.out_act = out_act;
-  // the instantiations with the GELU paths live in conv_b3_gelu.hip (conv_b3_kernels.h says why)
-  const bool gelu = in_act == PG_ACT_GELU || out_act == PG_ACT_GELU || dact == PG_ACT_GELU;
 #ifdef PG_ABLATE
   { const char* e = getenv("PG_B3_DBG"); a.dbg = e ? atoi(e) : 0; }
   a.prof = g_b3_prof;
 #else
   a.dbg = 0;
 #endif
-  int hr, hc;
-  tap_extent(T, tap_dr, tap_dc, a.min_dr, hr, a.min_dc, hc);
-  const B3Plan pl = b3_plan(Cin, Cout, T);
-  int TR = b3_rows(T, OH, OW, hr, hc, pl.px_cap);
-  PG_REQUIRE(pl.ok && TR >= 1 && OH * OW >= 16 && OW <= 256, PG_ESHAPE,
-             "pg_conv2d_mfma(bf16x3): shape not covered");
-  a.CIB = pl.CIB; a.cgs = pl.cgs; a.groups = pl.groups; a.ksteps = pl.ksteps;
-  a.wslab4 = pl.ksteps * pl.MT * 192;
-  // multi-stream epilogue (two residuals, residual + derivative, batch-strided residual): own instantiations
-  const bool ms = res2 != nullptr || (res != nullptr && dact_src != nullptr) ||
-                  (res != nullptr && a.res_bs != (long)Cout * OH * OW);
-  {
-    // 1x1 without an LDS x tile (conv_b3_pw_kernel) up to 64 input channels (weight slab of an output chunk <= 24 KB).
-    // Measured forward, old -> new kernel (tools/exp/pw_ab.py): 64 -> 64 at N = 512, 32x32: 76.8 -> 65.4 us (4.1 TB/s of
-    // algorithmic traffic), with ELU on both sides 83.0 -> 74.8; 64 -> 32 at N = 1024, 28x28: 84.1 -> 64.7; 32 -> 64:
-    // 99.4 -> 88.7. 128 input channels are compute-heavy enough for the staged kernel: 182 -> 197 us, left there.
-    static const bool pw_on = []() { const char* e = PG_AB_ENV("PG_CONV_B3_PW"); return !(e && e[0] == '0'); }();
-    const int nchunk = Cin / pl.CIB;
-    const size_t wbytes = (size_t)nchunk * pl.MT * 3 * 1024;
-    // both residual operands the SAME tensor (PixelCNN's x + (x + net(x)) and the two equal skip gradients of its
-    // backward): one stream, added twice
-    const bool twice = res2 != nullptr && res2 == res && a.res2_bs == a.res_bs;
-    const bool ms_pw = twice ? ((dact_src != nullptr) || a.res_bs != (long)Cout * OH * OW) : ms;  // (dual: res + dact_src => ms)
-    if (pw_on && !gate && (!ms_pw || pl.MT == 4) && T == 1 && pl.ksteps == 1 && tap_dr[0] == 0 && tap_dc[0] == 0 && IH == OH && IW == OW &&
-        (OH * OW) % 2 == 0 && (((uintptr_t)in) & 7) == 0 && wbytes <= 24 * 1024) {
-      a.TR = 0; a.tile_h = a.tile_w = a.plane16 = a.tiles_per_img = 0;
-      a.xslots = 0; a.dump16 = 0; a.w_off16 = 0;
-      for (int g = 0; g < B3_MAXG; ++g) { a.g_tapoff[g] = 0; a.g_cg[g] = 0; }
-      a.ep_off = (int)(wbytes / 4);
-      a.b_off = a.ep_off + PW_WAVES * 16 * PW_EPS;
-      const size_t shmem = ((size_t)a.b_off + B3_CO_CHUNK + 4) * sizeof(float);
-      const int chunks_y = b3_chunks(Cout);
-      const long items = (long)N * ((OH * OW + 31) / 32);
-      // resident workgroups per CU: what the registers allow (waves per SIMD = 4 / 3 / 2 for 1 / 2 / 3-4 output
-      // tiles of 16 channels), LDS permitting
-      // (round 6: four output tiles WITHOUT the multi-stream epilogue hold their A fragments in halves: 167 registers, three too)
-      const int by_regs = pl.MT == 1 ? 4 : ((pl.MT == 2 || (pl.MT == 4 && !ms_pw && !gelu)) ? 3 : 2);
-      const int by_lds = (int)((160 * 1024) / shmem);
-      const int per_cu = by_lds < by_regs ? by_lds : by_regs;
-      long gx = (long)256 * per_cu / chunks_y;
-      if (gx > (items + PW_WAVES - 1) / PW_WAVES) gx = (items + PW_WAVES - 1) / PW_WAVES;
-      if (gx < 1) gx = 1;
-      const dim3 grid((unsigned)gx, (unsigned)chunks_y);
-      if (twice) { a.res2 = nullptr; a.res_scale = 2.f; }
-      const B3Launch l = {1, pl.MT, 0, 1, ms_pw ? 1 : 0, 0, 0, grid, shmem};
-      if (gelu) pg_b3_dispatch_gelu(a, l, st);
-      else b3_dispatch<false>(a, l, st);
-      PG_LAUNCH_CHECK("pg_conv2d_mfma(bf16x3, 1x1)");
-      return 0;
-    }
-    PG_REQUIRE(!dual_out2, PG_ESHAPE, "pg_conv2d_mfma_dual: shape not on the 1x1 kernel (pg_conv_dual_ok)");
+  // 2. the problem
+  const int flags = (res ? PG_B3R_RES : 0) | (res2 ? PG_B3R_RES2 : 0) |
+                    (res2 && res2 == res && a.res2_bs == a.res_bs ? PG_B3R_RES2_SAME : 0) |
+                    (res && a.res_bs != (long)Cout * OH * OW ? PG_B3R_RES_STRIDED : 0) | (dact_src ? PG_B3R_DACT_SRC : 0) |
+                    (dual_out2 ? PG_B3R_DUAL : 0) | ((((uintptr_t)in) & 7) != 0 ? PG_B3R_IN_MISALIGNED : 0);
+  const B3Problem p = b3_problem(N, Cin, IH, IW, Cout, OH, OW, T, tap_dr, tap_dc, in_act, dact, out_act, gate, flags);
+  // 3. its route
+  B3Route r;
+  const int rc = b3_route(p, r);
+  if (rc) {
+    pg_set_error("%s", r.msg);
+    return rc;
   }
-  if (T > 1 && !pl.pipelined) {
-    // conv_b3_kernel: the staged tile may be larger than the format-level 352 pixels if THIS launch's LDS has the room
-    // (one 64-channel chunk per workgroup assumed here; the wide kernel is re-checked below and falls back)
-    static const bool big_on = []() { const char* e = PG_AB_ENV("PG_CONV_B3_BIGTILE"); return !(e && e[0] == '0'); }();
-    const long fixed = (long)pl.w_bytes + 4L * 16 * 68 * 4 + (B3_CO_CHUNK + B3_MAXG + 4) * 4 + 16 * 16 + 512;
-    long cap = (80L * 1024 - fixed) / ((long)pl.cgs * 48);        // 16-byte entries per (group, piece) plane
-    const long slot_cap = (pl.w9 ? 2L : (long)B3_XS) * B3_THREADS / pl.cgs;  // staging slots per thread
-    if (cap > slot_cap) cap = slot_cap;
-    cap = (cap / 16) * 16;
-    const bool wide = !pl.w9 && pl.MT == 4 && Cout % (2 * B3_CO_CHUNK) == 0;  // (its LDS holds two weight slabs: keep the plan's tile)
-    if (big_on && !wide && cap > (pl.px_cap ? pl.px_cap : B3_PX_CAP)) {
-      const int TR2 = b3_rows(T, OH, OW, hr, hc, (int)cap);
-      if (TR2 > TR) TR = TR2;
-    }
+  // 4. launch it
+  a.TR = r.TR; a.tile_h = r.tile_h; a.tile_w = r.tile_w; a.plane16 = r.plane16; a.tiles_per_img = r.tiles_per_img;
+  a.CIB = r.CIB; a.cgs = r.cgs; a.groups = r.groups; a.ksteps = r.ksteps; a.wslab4 = r.wslab4; a.xslots = r.xslots;
+  a.dump16 = r.dump16; a.w_off16 = r.w_off16; a.ep_off = r.ep_off; a.b_off = r.b_off;
+  a.min_dr = r.min_dr; a.min_dc = r.min_dc;
+  for (int g = 0; g < B3_MAXG; ++g) { a.g_tapoff[g] = r.g_tapoff[g]; a.g_cg[g] = r.g_cg[g]; }
+  a.res_scale = r.res_scale;
+  if (r.res2_folded) a.res2 = nullptr;
+  if (r.launch.gelu) pg_b3_dispatch_gelu(a, r.launch, st);
+  else b3_dispatch<false>(a, r.launch, st);
+  static const char* const what[] = {"pg_conv2d_mfma(bf16x3)", "pg_conv2d_mfma(bf16x3, 1x1)", "pg_conv2d_mfma(bf16x3, pipelined)",
+                                     "pg_conv2d_mfma(bf16x3, overlapped)"};
+  PG_LAUNCH_CHECK(what[r.launch.kernel]);
+  return 0;
+}
+
+// Host only, no device call: the route of a problem given as integers. flags: PG_B3R_*; gate: 0 or 1 + PG_GATE_*. Fills out[0 ..
+// PG_B3_ROUTE_INTS): kernel id (B3Kernel), GELU instantiation, template arguments (MT, NT, CG, MS, GT | pipelined: waves | overlapped:
+// staging slots per thread, two tiles per workgroup), grid x / y, block size, LDS bytes, then B3Args' geometry in the order of B3Route.
+PG_EXPORT int pg_conv_b3_route(int N, int Cin, int IH, int IW, int Cout, int OH, int OW, int T, const int* tap_dr, const int* tap_dc,
+                               int in_act, int dact, int out_act, int gate, int flags, int* out, int out_len) {
+  PG_REQUIRE(tap_dr && tap_dc && out && out_len >= PG_B3_ROUTE_INTS, PG_EINVAL, "pg_conv_b3_route: null pointer or short output array");
+  PG_REQUIRE(N > 0 && Cin > 0 && Cout > 0 && IH > 0 && IW > 0 && OH > 0 && OW > 0 && T >= 1 && T <= PG_MAX_TAPS, PG_EINVAL,
+             "pg_conv_b3_route: non-positive dimension or T not in [1,%d]", PG_MAX_TAPS);
+  const B3Problem p = b3_problem(N, Cin, IH, IW, Cout, OH, OW, T, tap_dr, tap_dc, in_act, dact, out_act, gate, flags);
+  B3Route r;
+  const int rc = b3_route(p, r);
+  if (rc) {
+    pg_set_error("%s", r.msg);
+    return rc;
   }
-  a.TR = TR; a.tile_h = TR + hr; a.tile_w = OW + hc;
-  a.plane16 = ((a.tile_h * a.tile_w + 15) / 16) * 16;
-  a.tiles_per_img = (OH + TR - 1) / TR;
-  PG_REQUIRE(!gate || (!pl.pipelined && !pl.w9 && pl.MT == 4 && Cout % (2 * B3_CO_CHUNK) == 0 && !gelu), PG_ESHAPE,
-             "pg_conv2d_mfma_gate: the fused gate needs the wide bf16x3 kernel with a multiple of 128 output channels");
-  // (Round 6, measured and NOT shipped: a row-ring forward kernel with register-resident weights for the 64-channel 4-tap layers —
-  // tools/exp/rejected/conv_b3r_kernel.h (its README has the routing block that stood here) — parity green, 225 against 235 us on the
-  // 2x2 64 -> 64 at batch 1024, PixelSNAIL +0.3 %: profiles/r06_conv_ring_forward_ab.txt.)
-  if (pl.pipelined && a.tile_h * a.tile_w <= B3P_PX) {
-    // ---- the pipelined kernel: LDS = x[2][3 pieces][plane16] | dump entry | w[2][768] | 4 x epilogue scratch | bias, taps
-    for (int g = 0; g < B3_MAXG; ++g) { a.g_tapoff[g] = 0; a.g_cg[g] = 0; }
-    for (int t = 0; t < 4; ++t) a.g_tapoff[t] = (tap_dr[t] - a.min_dr) * a.tile_w + (tap_dc[t] - a.min_dc);
-    a.xslots = a.tile_h * a.tile_w;
-    const size_t x16 = (size_t)2 * 3 * a.plane16;
-    a.dump16 = (int)x16;
-    a.w_off16 = (int)(((x16 + 1 + 15) / 16) * 16);
-    // waves per workgroup: 8 (a wave owns 32 pixels, 128 registers, four waves per SIMD) unless PG_CONV_B3P_WAVES=4
-    static const int env_waves = []() { const char* e = PG_AB_ENV("PG_CONV_B3P_WAVES"); return (e && atoi(e) == 4) ? 4 : 8; }();
-    const int p_waves = env_waves;
-    const int px = TR * OW;
-    const int nt = p_waves == 8 ? (px + 127) / 128 : (px + 63) / 64;   // 16-pixel groups per wave
-    size_t shmem = ((size_t)a.w_off16 + 2 * B3P_W4) * 16;
-    a.ep_off = (int)(shmem / 4);
-    shmem += (size_t)p_waves * 16 * (nt * 16 + 4) * 4;  // per-wave transposition scratch
-    a.b_off = (int)(shmem / 4);
-    shmem += (B3_CO_CHUNK + 8) * sizeof(float);
-    PG_REQUIRE(shmem <= (size_t)80 * 1024, PG_ESHAPE, "pg_conv2d_mfma(bf16x3, pipelined): %zu B of LDS", shmem);
-    const int chunks_y = b3_chunks(Cout);
-    long want = 512 / chunks_y;  // resident workgroups: 2 per CU
-    if (want < a.tiles_per_img) want = a.tiles_per_img;
-    long gx = (want / a.tiles_per_img) * a.tiles_per_img;
-    if (gx > (long)N * a.tiles_per_img) gx = (long)N * a.tiles_per_img;
-    const dim3 grid((unsigned)gx, (unsigned)chunks_y);
-    const B3Launch l = {2, 4, nt, p_waves, 0, 0, 0, grid, shmem};
-    if (gelu) pg_b3_dispatch_gelu(a, l, st);
-    else b3_dispatch<false>(a, l, st);
-    PG_LAUNCH_CHECK("pg_conv2d_mfma(bf16x3, pipelined)");
-    return 0;
-  }
-  {
-    // ---- the overlapped 16-wave kernel (conv_b3q_kernel.h, round 6): >= 64 output channels, any tap count. Its LDS (one
-    // workgroup per CU, up to 160 KB) = x tiles [NXT][2 buffers][cgs][3 pieces][plane16] | dump entry | slab ring [2][NCH][768] |
-    // bias, K-group table; two output chunks share one x tile when Cout % 128 == 0, otherwise two tiles share one slab.
-    static const bool q_on = []() { const char* e = PG_AB_ENV("PG_CONV_B3Q"); return !(e && e[0] == '0'); }();
-    // Measured on MI355X (round 6, tools/exp/q_ab.py, same box, median of 5 x 20 launches, forward; profiles/r06_conv_q_ab.txt):
-    //   two tiles per workgroup (ST): PixelCNN++'s 2x3 160 -> 320 265 -> 243 us, 320 -> 160 301 -> 283 us at batch 64 — taken;
-    //     2x3 160 -> 160 152 -> 160 us and the 16 x 16 level (one 256-pixel tile per image: 96-160 workgroups for 256 CUs) 97 -> 147 us — not;
-    //   two output chunks per workgroup (CG, GatedPixelCNN / PixelSNAIL 64 -> 128): 3-6 % SLOWER than the 8-wave wide kernel on every
-    //     shape (1x1 256 -> 256 446 -> 463 us, 2x1 755 -> 792, 1x2 426 -> 439, 1x3 641 -> 675, 2x2 64 -> 128 392 -> 416): sixteen waves that
-    //     meet at one barrier per K step run their phases in lockstep, and the kernel's ablation (profiles/r06_conv_q_ablation.txt) shows the
-    //     phases ADD UP (MFMA 200 + loads / commit 130 + epilogue 95 + slab DMA 28 + empty K-step loop 100 of 564 us) instead of overlapping:
-    //     the epilogue alone streams at 5.6 TB/s, i.e. at the HBM write rate, while no wave computes. Not taken (PG_CONV_B3Q_CG=1 in the ab
-    //     library runs it for A/B).
-    static const bool q_cg = []() { const char* e = PG_AB_ENV("PG_CONV_B3Q_CG"); return e && e[0] == '1'; }();
-    const bool stm = Cout % (2 * B3_CO_CHUNK) != 0;
-    const int NCH = stm ? 1 : 2, NXT = stm ? 2 : 1, GT = stm ? 512 : 1024;
-    const long tail = (long)(NCH * B3_CO_CHUNK + B3_MAXG + 4) * 4 + 16 * 16 + 256;
-    long cap = (160L * 1024 - 2L * NCH * B3Q_SLAB16 * 16 - tail) / ((long)NXT * 2 * pl.cgs * 48);
-    cap = (cap / 16) * 16;
-    const bool q_shape = !gate && (stm ? (T >= 6 && (Cin >= 256 || Cout >= 256)) : q_cg);
-    const int TRq = (q_on && q_shape && pl.MT == 4 && !pl.pipelined && cap >= 64) ? b3_rows(T, OH, OW, hr, hc, (int)cap) : 0;
-    if (TRq >= 1) {
-      const int th = TRq + hr, tw = OW + hc;
-      const int xs = (pl.cgs * th * tw + GT - 1) / GT;
-      // at least 6 of the 8 pixel slices of 32 must be busy (small images stay on the 4-wave kernels), and in ST mode the
-      // batch must provide pairs of images
-      if (xs <= 2 && TRq * OW >= 192 && (!stm || N >= 2) && (OH + TRq - 1) / TRq >= 2) {
-        a.TR = TRq; a.tile_h = th; a.tile_w = tw;
-        a.plane16 = ((th * tw + 15) / 16) * 16;
-        a.tiles_per_img = (OH + TRq - 1) / TRq;
-        for (int g = 0; g < pl.groups; ++g) {
-          const int t = g / pl.cgs, cg = g - t * pl.cgs;
-          a.g_tapoff[g] = (tap_dr[t] - a.min_dr) * tw + (tap_dc[t] - a.min_dc);
-          a.g_cg[g] = cg;
-        }
-        for (int g = pl.groups; g < B3_MAXG; ++g) { a.g_tapoff[g] = 0; a.g_cg[g] = 0; }
-        a.xslots = pl.cgs * th * tw;
-        const size_t x16 = (size_t)NXT * 2 * pl.cgs * 3 * a.plane16;
-        a.dump16 = (int)x16;
-        a.w_off16 = (int)(((x16 + 1 + 15) / 16) * 16);
-        size_t shmem = ((size_t)a.w_off16 + 2 * NCH * B3Q_SLAB16) * 16;
-        a.ep_off = 0;
-        a.b_off = (int)(shmem / 4);
-        shmem += (size_t)(NCH * B3_CO_CHUNK + B3_MAXG + 4) * sizeof(float);
-        PG_REQUIRE(shmem <= (size_t)160 * 1024, PG_ESHAPE, "pg_conv2d_mfma(bf16x3, overlapped): %zu B of LDS", shmem);
-        const int chunks_y = stm ? b3_chunks(Cout) : Cout / (2 * B3_CO_CHUNK);
-        long want = 256 / chunks_y;  // resident workgroups: 1 per CU
-        if (want < a.tiles_per_img) want = a.tiles_per_img;
-        long gx = (want / a.tiles_per_img) * a.tiles_per_img;
-        const long units = (stm ? (long)(N + 1) / 2 : (long)N) * a.tiles_per_img;  // ST: a workgroup takes images in pairs
-        if (gx > units) gx = units;
-        const dim3 grid((unsigned)gx, (unsigned)chunks_y);
-        const B3Launch l = {3, 4, xs, stm ? 1 : 0, 0, 0, 0, grid, shmem};
-        if (gelu) pg_b3_dispatch_gelu(a, l, st);
-        else b3_dispatch<false>(a, l, st);
-        PG_LAUNCH_CHECK("pg_conv2d_mfma(bf16x3, overlapped)");
-        return 0;
-      }
-    }
-  }
-  for (int g = 0; g < pl.groups; ++g) {
-    const int t = g / pl.cgs, cg = g - t * pl.cgs;
-    a.g_tapoff[g] = (tap_dr[t] - a.min_dr) * a.tile_w + (tap_dc[t] - a.min_dc);
-    a.g_cg[g] = cg;
-  }
-  for (int g = pl.groups; g < B3_MAXG; ++g) { a.g_tapoff[g] = 0; a.g_cg[g] = 0; }
-  a.xslots = pl.cgs * a.tile_h * a.tile_w;
-  const size_t x16 = (size_t)pl.cgs * 3 * a.plane16;
-  a.dump16 = (int)x16;              // one spare 16-byte entry (+ padding to a 256-byte boundary)
-  a.w_off16 = (int)(((x16 + 1 + 15) / 16) * 16);
-  // wide workgroups (two output chunks share one staged x tile): default; PG_CONV_B3_WIDE=0 for A/B
-  static const bool wide_on = []() { const char* e = PG_AB_ENV("PG_CONV_B3_WIDE"); return !(e && e[0] == '0'); }();
-  const int CG = ((wide_on || gate) && !pl.w9 && pl.MT == 4 && Cout % (2 * B3_CO_CHUNK) == 0) ? 2 : 1;
-  size_t shmem = (size_t)a.w_off16 * 16 + pl.w_bytes * CG;
-  a.ep_off = (int)(shmem / 4);
-  shmem += (size_t)4 * CG * 16 * 68 * 4;
-  a.b_off = (int)(shmem / 4);
-  shmem += (B3_CO_CHUNK * CG + B3_MAXG + 4) * sizeof(float);
-  PG_REQUIRE(shmem <= (size_t)(CG == 1 ? 80 : 160) * 1024, PG_ESHAPE, "pg_conv2d_mfma(bf16x3): %zu B of LDS", shmem);
-  const int nt = (TR * OW + 63) / 64;
-  const int chunks_y = b3_chunks(Cout) / CG;
-  long want = (CG == 1 ? 512 : 256) / chunks_y;  // resident workgroups: 2 per CU (4 waves) / 1 per CU (8 waves)
-  if (want < a.tiles_per_img) want = a.tiles_per_img;
-  long gx = (want / a.tiles_per_img) * a.tiles_per_img;
-  if (gx > (long)N * a.tiles_per_img) gx = (long)N * a.tiles_per_img;
-  dim3 grid((unsigned)gx, (unsigned)chunks_y);
-  PG_REQUIRE(!ms || pl.MT == 4, PG_ESHAPE,
-             "pg_conv2d_mfma_ex(bf16x3): the multi-stream epilogue is instantiated for >= 64 output channels");
-  PG_REQUIRE(!gate || (CG == 2 && !ms), PG_ESHAPE, "pg_conv2d_mfma_gate: not the wide kernel's plain epilogue");
-  const B3Launch l = {0, pl.MT, nt, CG, ms ? 1 : 0, pl.w9, gate ? 1 : 0, grid, shmem};
-  if (gelu) pg_b3_dispatch_gelu(a, l, st);
-  else b3_dispatch<false>(a, l, st);
-  PG_LAUNCH_CHECK("pg_conv2d_mfma(bf16x3)");
+  const B3Launch& l = r.launch;
+  const int block = l.kernel == B3K_STAGED ? B3_THREADS * l.CG : l.kernel == B3K_PW ? 64 * PW_WAVES
+                  : l.kernel == B3K_PIPELINED ? 64 * l.waves : B3Q_THREADS;
+  const int v[PG_B3_ROUTE_INTS - 2 * B3_MAXG] = {
+      l.kernel, l.gelu, l.MT, l.nt, l.CG, l.ms, l.gate, l.waves, l.xslots_per_thread, l.two_tiles,
+      (int)l.grid.x, (int)l.grid.y, block, (int)l.shmem,
+      r.TR, r.tile_h, r.tile_w, r.plane16, r.tiles_per_img, r.CIB, r.cgs, r.groups, r.ksteps, r.wslab4, r.xslots,
+      r.dump16, r.w_off16, r.ep_off, r.b_off, (int)r.res_scale, r.res2_folded ? 1 : 0, r.min_dr, r.min_dc};
+  int i = 0;
+  for (int x : v) out[i++] = x;
+  for (int g = 0; g < B3_MAXG; ++g) out[i++] = r.g_tapoff[g];
+  for (int g = 0; g < B3_MAXG; ++g) out[i++] = r.g_cg[g];
   return 0;
 }

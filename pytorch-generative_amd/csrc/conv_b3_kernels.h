@@ -65,10 +65,23 @@ struct B3Args {
 
 // Which instantiation takes a launch: decided by the host code of conv_b3.hip, executed in the translation unit
 // that holds the instantiations for GL (conv_b3.hip: GL = false; conv_b3_gelu.hip: GL = true).
-struct B3Launch {
-  int pw;            // 3: conv_b3q_kernel (overlapped, 16 waves), 2: conv_b3p_kernel (pipelined, 4 taps), 1: conv_b3_pw_kernel, 0: conv_b3_kernel
-  int MT, nt, CG, ms, w9;
-  int gate;          // the wide kernel's gate-fusing instantiation
+enum B3Kernel {
+  B3K_STAGED = 0,      // conv_b3_kernel: narrow (CG = 1) and wide (CG = 2), multi-stream and gate forms
+  B3K_PW = 1,          // conv_b3_pw_kernel: 1x1 without an LDS x tile
+  B3K_PIPELINED = 2,   // conv_b3p_kernel: 4 taps
+  B3K_OVERLAPPED = 3,  // conv_b3q_kernel: 16 waves
+};
+struct B3Launch {  // a field its kernel has no template argument for stays 0
+  B3Kernel kernel;
+  int gelu;               // the instantiation with the GELU paths (conv_b3_gelu.hip)
+  int MT;                 // staged, 1x1: output tiles of 16 channels per chunk
+  int nt;                 // staged, pipelined: 16-pixel groups per wave
+  int CG;                 // staged: output chunks per workgroup (2 = wide)
+  int ms;                 // staged, 1x1: the multi-stream epilogue
+  int gate;               // staged: the wide kernel's gate-fusing instantiation
+  int waves;              // pipelined: waves per workgroup (8 or 4)
+  int xslots_per_thread;  // overlapped: staging slots per thread (1 or 2)
+  int two_tiles;          // overlapped: two tiles per workgroup share one slab (else two output chunks share one x tile)
   dim3 grid;
   size_t shmem;
 };
@@ -84,8 +97,6 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 constexpr int B3_THREADS = 256;
 constexpr int B3_CO_CHUNK = 64;
 constexpr int B3_XS = 4;       // (pixel, channel-group) staging slots per thread per step: 8 loads each
-constexpr int B3_WS = 6;       // float4 weight-fragment slots per thread per step of the FORMAT-level plan (conv_b3.hip; the kernel itself
-                               // has moved its weight slabs by LDS-DMA since round 5 and holds no weight registers)
 
 
 
@@ -148,20 +159,17 @@ __device__ __forceinline__ void split8t(const float (&x)[8], u32x4& h, u32x4& m,
 // MS ("multi-stream epilogue"): v * act'(dact_src) + res + res2 with pipelined operand requests — its
 // own instantiation, because the three operand buffers cost registers that the common kernels (at 256
 // already) must not pay: with the code shared, the plain forward launch went from 136 to 185 us.
-// W9 ("wide weights"): 9 weight slots and 2 x slots per thread instead of 6 and 4 — the plan of a 3x3 with 64 output
-// channels (8-channel chunks: one channel group x 9 taps = 3 K steps, a 36 KB weight slab per step), which otherwise
-// does not fit the staging slots and runs on the fp32-MFMA kernel.
 // GT ("gate", round 6; CG = 2, Cout == 128): convolution + GatedActivation (+ residual) of PixelSNAIL's ResidualBlock
 // (pixel_snail.py:41-56) in one launch. The fragments come in the gate-interleaved order (PG_CONV_FMT_B3_GATE): each chunk = the
 // [a | b] halves of 32 gate channels, so a wave holds both operands of its gate channels in its own accumulators and writes
 // z (natural order, for backward) and y = res + act(a) * sigmoid(b) from the same transposed tiles. (A first version kept the natural
 // order and exchanged tiles between the two waves of a pixel quarter through their scratch, two barriers per tile: +0.7 % on
 // PixelSNAIL instead of the gate kernel's 4.3 % — with one workgroup per CU every barrier behind a global load idles the CU.)
-template <bool GL, int MT, int NT, int CG, bool MS = false, bool W9 = false, bool GT = false>
+template <bool GL, int MT, int NT, int CG, bool MS = false, bool GT = false>
 __global__ void __launch_bounds__(B3_THREADS * CG, CG == 1 ? 2 : 1) conv_b3_kernel(const B3Args a) {
-  static_assert(!GT || (CG == 2 && MT == 4 && !MS && !W9), "gate fusion: the wide kernel's plain epilogue");
+  static_assert(!GT || (CG == 2 && MT == 4 && !MS), "gate fusion: the wide kernel's plain epilogue");
   constexpr int THREADS = B3_THREADS * CG;
-  constexpr int XS = W9 ? 2 : (CG == 1 ? B3_XS : (B3_XS + 1) / 2);  // the tile's slots over twice the threads
+  constexpr int XS = CG == 1 ? B3_XS : (B3_XS + 1) / 2;  // the tile's slots over twice the threads
   extern __shared__ __attribute__((aligned(16))) float lds[];
   u32x4* lds16 = reinterpret_cast<u32x4*>(lds);
   const int tid = threadIdx.x, lane = tid & 63;
@@ -1418,17 +1426,17 @@ if constexpr (GL) {
 
 #include "conv_b3q_kernel.h"
 
-template <bool GL, int MT, int CG = 1, bool MS = false, bool W9 = false, bool GT = false>
+template <bool GL, int MT, int CG = 1, bool MS = false, bool GT = false>
 void b3_launch(const B3Args& a, int nt, dim3 grid, size_t shmem, hipStream_t st) {
   // the LDS opt-in is set once per instantiation by a function-local static initialiser: thread-safe
   // (the library is entered from the main thread and from the autograd thread)
 #define PG_B3_L(NTV)                                                                                  \
   {                                                                                                   \
     static const hipError_t attr_##NTV = hipFuncSetAttribute(                                         \
-        reinterpret_cast<const void*>(conv_b3_kernel<GL, MT, NTV, CG, MS, W9, GT>),                       \
+        reinterpret_cast<const void*>(conv_b3_kernel<GL, MT, NTV, CG, MS, GT>),                           \
         hipFuncAttributeMaxDynamicSharedMemorySize, CG == 1 ? 80 * 1024 : 160 * 1024);                \
     (void)attr_##NTV;                                                                                 \
-    hipLaunchKernelGGL((conv_b3_kernel<GL, MT, NTV, CG, MS, W9, GT>), grid, dim3(B3_THREADS * CG), shmem, st, a); \
+    hipLaunchKernelGGL((conv_b3_kernel<GL, MT, NTV, CG, MS, GT>), grid, dim3(B3_THREADS * CG), shmem, st, a); \
   }
   switch (nt) {
     case 1: PG_B3_L(1) break;
@@ -1472,15 +1480,15 @@ void b3_pw_launch(const B3Args& a, dim3 grid, size_t shmem, hipStream_t st) {
 
 template <bool GL>
 void b3_dispatch(const B3Args& a, const B3Launch& l, hipStream_t st) {
-  if (l.pw == 3) {  // the overlapped 16-wave kernel (conv_b3q_kernel.h): nt = staging slots per thread, CG = 1 for two tiles per workgroup
-    b3q_launch<GL>(a, l.nt, l.CG != 0, l.grid, l.shmem, st);
+  if (l.kernel == B3K_OVERLAPPED) {
+    b3q_launch<GL>(a, l.xslots_per_thread, l.two_tiles != 0, l.grid, l.shmem, st);
     return;
   }
-  if (l.pw == 2) {  // the pipelined 4-tap kernel
-    b3p_launch<GL>(a, l.nt, l.CG, l.grid, l.shmem, st);  // (CG carries the waves per workgroup: 4 / 8)
+  if (l.kernel == B3K_PIPELINED) {
+    b3p_launch<GL>(a, l.nt, l.waves, l.grid, l.shmem, st);
     return;
   }
-  if (l.pw) {
+  if (l.kernel == B3K_PW) {
     if (l.ms) b3_pw_launch<GL, 4, true>(a, l.grid, l.shmem, st);
     else switch (l.MT) {
       case 1: b3_pw_launch<GL, 1>(a, l.grid, l.shmem, st); break;
@@ -1493,13 +1501,8 @@ void b3_dispatch(const B3Args& a, const B3Launch& l, hipStream_t st) {
   if (l.CG == 2) {
     if (l.ms) b3_launch<GL, 4, 2, true>(a, l.nt, l.grid, l.shmem, st);
     else if (l.gate) {
-      if constexpr (!GL) b3_launch<GL, 4, 2, false, false, true>(a, l.nt, l.grid, l.shmem, st);  // (no GELU variant: the host refuses)
+      if constexpr (!GL) b3_launch<GL, 4, 2, false, true>(a, l.nt, l.grid, l.shmem, st);  // (no GELU variant: the host refuses)
     } else b3_launch<GL, 4, 2>(a, l.nt, l.grid, l.shmem, st);
-    return;
-  }
-  if (l.w9) {
-    if (l.ms) b3_launch<GL, 4, 1, true, true>(a, l.nt, l.grid, l.shmem, st);
-    else b3_launch<GL, 4, 1, false, true>(a, l.nt, l.grid, l.shmem, st);
     return;
   }
   if (l.ms) {

@@ -380,21 +380,16 @@ PG_EXPORT int pg_conv2d_taps(const float* in, const float* wpk, const float* bia
   a.b_pad = b_pad; a.in_act = in_act; a.dact = dact;
   a.vec = ((OW % 4) == 0) && (((uintptr_t)out & 15) == 0) && (!res || ((uintptr_t)res & 15) == 0) &&
           (!dact_src || ((uintptr_t)dact_src & 15) == 0);
-  int min_dr = tap_dr[0], max_dr = tap_dr[0], min_dc = tap_dc[0], max_dc = tap_dc[0];
-  for (int t = 1; t < T; ++t) {
-    min_dr = tap_dr[t] < min_dr ? tap_dr[t] : min_dr;
-    max_dr = tap_dr[t] > max_dr ? tap_dr[t] : max_dr;
-    min_dc = tap_dc[t] < min_dc ? tap_dc[t] : min_dc;
-    max_dc = tap_dc[t] > max_dc ? tap_dc[t] : max_dc;
-  }
+  int min_dr, min_dc, hr, hc;
+  pg_tap_extent(T, tap_dr, tap_dc, min_dr, hr, min_dc, hc);
   a.Wg = (OW + PX - 1) / PX;
   PG_REQUIRE(a.Wg <= 256, PG_ESHAPE, "pg_conv2d_taps: OW=%d too wide", OW);
   int TR = 256 / a.Wg;
   if (TR > OH) TR = OH;
   a.TR = TR;
   a.tiles_per_img = (OH + TR - 1) / TR;
-  a.tile_h = TR + (max_dr - min_dr);
-  a.tile_w = a.Wg * PX + (max_dc - min_dc);
+  a.tile_h = TR + hr;
+  a.tile_w = a.Wg * PX + hc;
   a.min_dr = min_dr; a.min_dc = min_dc;
   a.ch_stride = a.tile_h * a.tile_w;
   {

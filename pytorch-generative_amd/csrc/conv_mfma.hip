@@ -25,7 +25,7 @@
 //  * weights arrive as ready-made A fragments (pg_pack_conv_weight_frag) and are copied to LDS with
 //    float4 loads; every lane reads its own dword (conflict free).
 #include "common.h"
-#include <stdlib.h>
+#include "conv_b3.h"
 
 namespace {
 
@@ -477,18 +477,7 @@ static void mf_pack_job(FragPackJob& j, float* wfrag, int Cout, int Cin, int T, 
 
 }  // namespace
 
-// conv_b3.hip: the same convolution with its fp32 products on the bf16 matrix pipe (format 2)
-int pg_b3_applicable(int Kc, int M, int T, int OH, int OW, int hr, int hc);
-size_t pg_b3_frag_floats(int Kc, int M, int T);
-int pg_b3_pack2(const float* w, float* wfrag_fwd, float* wfrag_dgrad, int Cout, int Cin, int KH, int KW,
-                int T, const int* tap_u, const int* tap_v, hipStream_t st, int gate_order = 0);
-int pg_b3_conv(const float* in, const float* wfrag, const float* bias, const float* res, float* out,
-               int N, int Cin, int IH, int IW, int Cout, int OH, int OW, int T, const int* tap_dr,
-               const int* tap_dc, int in_act, const float* dact_src, int dact, int out_act,
-               const float* res2, long res_bs, long res2_bs, hipStream_t st, int gate = 0, const float* gate_res = nullptr,
-               float* gate_out = nullptr, float* dual_out2 = nullptr);
-int pg_b3_dual_ok(int Cin, int Cout, int OH, int OW);
-int pg_b3_gate_fusable(int Cin, int Cout, int T, int OH, int OW, int hr, int hc);
+// (conv_b3.h — conv_b3.hip: the same convolution with its fp32 products on the bf16 matrix pipe, format 2)
 
 // Geometry of one fp32-MFMA launch: pixel tile, channel chunk, LDS layout. Needs a.N / Cin / IW / Cout / OH / OW / T; hr / hc = row /
 // column extent of the tap list. Shared by the launch (pg_conv2d_mfma_ex) and by the routing query (pg_conv_mfma_supported), so that
@@ -499,7 +488,8 @@ static int mf_geometry(MfArgs& a, int hr, int hc, size_t* shmem_out) {
   const int N = a.N, Cin = a.Cin, IW = a.IW, Cout = a.Cout, OH = a.OH, OW = a.OW, T = a.T;
   // pixel tile: whole rows of one image (TR rows), or NI whole images when an image is <= 128 px
   const int L = OH * OW;
-  static const int px_cap = []() { const char* e = PG_AB_ENV("PG_MF_PX"); const int v = e ? atoi(e) : 256; return (v == 64 || v == 128 || v == 192) ? v : 256; }();
+  static const int px_env = PG_AB_INT("PG_MF_PX", 256);
+  const int px_cap = (px_env == 64 || px_env == 128 || px_env == 192) ? px_env : 256;
   if (L <= 128) {
     a.NI = 256 / L;
     if (a.NI > 15) a.NI = 15;  // the image index of a staging slot is packed into 4 bits
@@ -575,7 +565,8 @@ PG_EXPORT int pg_conv_mfma_supported(int Cin, int Cout, int T, int OH, int OW, i
   // 64-channel outputs at ~1.1 TB/s): beta-VAE 45.7 -> 47.9 k img/s, PixelSNAIL / GatedPixelCNN +0.7 % (same box;
   // PG_CONV_MFMA_MIN_CIN=8 restores the old routing for A/B. The ONE-channel input layers stay on the tap kernel: ImageGPT's
   // 3x3 1 -> 16 measured no different, PixelCNN's 24-tap 7x7 does not fit this kernel's tap table)
-  static const int min_cin = []() { const char* e = PG_AB_ENV("PG_CONV_MFMA_MIN_CIN"); const int v = e ? atoi(e) : 3; return v >= 3 ? v : 3; }();
+  static const int min_cin_env = PG_AB_INT("PG_CONV_MFMA_MIN_CIN", 3);
+  const int min_cin = min_cin_env >= 3 ? min_cin_env : 3;
   if (!((Cin < 8 && Cin >= min_cin && Cout >= 32) || (Cin >= 8 && Cout >= 8))) return 0;
   // ... and only if the launch geometry fits (the batch is not known here: the largest image group, i.e. the most slots and LDS)
   MfArgs g;
@@ -645,12 +636,7 @@ PG_EXPORT int pg_pack_conv_weight_frag(const float* w, float* wfrag, int Cout, i
 // (N, C, OH, OW) = gate_res + act(out[:, :C]) * sigmoid(out[:, C:]) (res, gate_res may be NULL); 2C a multiple of 128.
 PG_EXPORT int pg_conv_gate_fusable(int Cin, int Cout, int OH, int OW, int T, const int* tap_dr, const int* tap_dc) {
   if (!tap_dr || !tap_dc || T < 1 || T > PG_MAX_TAPS) return 0;
-  int a0 = tap_dr[0], a1 = tap_dr[0], b0 = tap_dc[0], b1 = tap_dc[0];
-  for (int t = 1; t < T; ++t) {
-    a0 = tap_dr[t] < a0 ? tap_dr[t] : a0; a1 = tap_dr[t] > a1 ? tap_dr[t] : a1;
-    b0 = tap_dc[t] < b0 ? tap_dc[t] : b0; b1 = tap_dc[t] > b1 ? tap_dc[t] : b1;
-  }
-  return pg_b3_gate_fusable(Cin, Cout, T, OH, OW, a1 - a0, b1 - b0);
+  return pg_b3_gate_fusable(Cin, Cout, T, OH, OW, tap_dr, tap_dc);
 }
 
 PG_EXPORT int pg_conv2d_mfma_gate(const float* in, const float* wfrag, const float* bias, const float* res, float* out, int N, int Cin,
@@ -674,7 +660,7 @@ PG_EXPORT int pg_conv2d_mfma_gate(const float* in, const float* wfrag, const flo
 // derivatives from the stored ELU outputs (y > 0 ? 1 : y + 1). Replaces two pg_act_bwd_from_out launches (7 streams) by one more
 // read and one more write in this launch's epilogue.
 PG_EXPORT int pg_conv_dual_ok(int Cin, int Cout, int OH, int OW) {
-  static const bool on = []() { const char* e = PG_AB_ENV("PG_CONV_DUAL"); return !(e && e[0] == '0'); }();
+  static const bool on = PG_AB_ON("PG_CONV_DUAL");
   return on && pg_b3_dual_ok(Cin, Cout, OH, OW);
 }
 
@@ -734,18 +720,13 @@ PG_EXPORT int pg_conv2d_mfma_ex(const float* in, const float* wfrag, const float
   a.in = in; a.wfrag = wfrag; a.bias = bias; a.res = res; a.dact_src = dact_src; a.out = out;
   a.N = N; a.Cin = Cin; a.IH = IH; a.IW = IW; a.Cout = Cout; a.OH = OH; a.OW = OW; a.T = T;
   a.in_act = in_act; a.dact = dact; a.out_act = out_act;
-  int min_dr = tap_dr[0], max_dr = tap_dr[0], min_dc = tap_dc[0], max_dc = tap_dc[0];
-  for (int t = 1; t < T; ++t) {
-    min_dr = tap_dr[t] < min_dr ? tap_dr[t] : min_dr;
-    max_dr = tap_dr[t] > max_dr ? tap_dr[t] : max_dr;
-    min_dc = tap_dc[t] < min_dc ? tap_dc[t] : min_dc;
-    max_dc = tap_dc[t] > max_dc ? tap_dc[t] : max_dc;
-  }
+  int min_dr, min_dc, hr, hc;
+  pg_tap_extent(T, tap_dr, tap_dc, min_dr, hr, min_dc, hc);
   a.min_dr = min_dr; a.min_dc = min_dc;
   PG_REQUIRE((IW % 4) == 0 && (((uintptr_t)in & 15) == 0), PG_ESHAPE,
              "pg_conv2d_mfma: input rows must be 16-byte aligned (IW %% 4 == 0)");
   size_t shmem = 0;
-  const int fit = mf_geometry(a, max_dr - min_dr, max_dc - min_dc, &shmem);
+  const int fit = mf_geometry(a, hr, hc, &shmem);
   PG_REQUIRE(fit != MF_FIT_SLOTS, PG_ESHAPE, "pg_conv2d_mfma: %d taps x %d-row tile exceeds the staging slots", T, a.tile_h);
   PG_REQUIRE(fit != MF_FIT_LDS, PG_ESHAPE, "pg_conv2d_mfma: tile %dx%d x %d taps needs %zu B of LDS (> 80 KB)", a.tile_h,
              a.tile_w, T, shmem);

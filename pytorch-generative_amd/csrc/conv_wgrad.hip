@@ -590,7 +590,7 @@ PG_EXPORT int pg_conv2d_wgrad(const float* x, const float* dy, float* dw, float*
   const long max_rows = wgrad_max_rows(Cout, Cin, T);
   // 1x1 convolutions whose shape the bf16x3 kernel takes (Cout % 64 == 0, Cin % 32 == 0, W % 8 == 0) go there
   // first (PG_WGRAD_B3_PW=0: the fp32 direct-fragment kernel below, for A/B)
-  static const bool b3_pw = []() { const char* e = PG_AB_ENV("PG_WGRAD_B3_PW"); return !(e && e[0] == '0'); }();
+  static const bool b3_pw = PG_AB_ON("PG_WGRAD_B3_PW");
   if (b3_pw && T == 1 && KH == 1 && KW == 1 && tap_dr[0] == 0 && tap_dc[0] == 0 && IH == OH && IW == OW) {
     const int g = pg_wgrad_b3_launch(x, dy, workspace, stride, max_rows, db != nullptr, N, Cin, IH, IW,
                                      Cout, OH, OW, T, tap_dr, tap_dc, in_act, st);
@@ -637,7 +637,7 @@ PG_EXPORT int pg_conv2d_wgrad(const float* x, const float* dy, float* dw, float*
     // tuned on), else — or when its x copies do not fit LDS (3x3 on 64-wide rows) — the shifted-dy variant
     // (measured, PG_WGRAD_B3S=2 prefers the shifted-dy kernel everywhere: PixelSNAIL 12.43 -> 12.31 k img/s,
     // GatedPixelCNN 5.26 -> 5.06 k, beta-VAE 38.1 -> 38.5 k: only the 3x3 grids gain, so those go there first)
-    static const bool s_all = []() { const char* e = PG_AB_ENV("PG_WGRAD_B3S"); return e && e[0] == '2'; }();
+    static const bool s_all = PG_AB_OFF("PG_WGRAD_B3S", '2');
     const bool s_first = s_all || T == 9;
     int g = (Cout % 64 == 0 && !s_first) ? pg_wgrad_b3_launch(x, dy, workspace, stride, max_rows, db != nullptr, N, Cin, IH, IW,
                                                 Cout, OH, OW, T, tap_dr, tap_dc, in_act, st)
@@ -659,15 +659,9 @@ PG_EXPORT int pg_conv2d_wgrad(const float* x, const float* dy, float* dw, float*
   a.x = x; a.dy = dy; a.dw = dw; a.db = db;
   a.N = N; a.Cin = Cin; a.IH = IH; a.IW = IW; a.Cout = Cout; a.OH = OH; a.OW = OW;
   a.KH = KH; a.KW = KW; a.T = T; a.in_act = in_act;
-  int min_dr = tap_dr[0], max_dr = tap_dr[0], min_dc = tap_dc[0], max_dc = tap_dc[0];
   a.part = workspace; a.part_stride = stride;
-  for (int t = 0; t < T; ++t) {
-    min_dr = tap_dr[t] < min_dr ? tap_dr[t] : min_dr;
-    max_dr = tap_dr[t] > max_dr ? tap_dr[t] : max_dr;
-    min_dc = tap_dc[t] < min_dc ? tap_dc[t] : min_dc;
-    max_dc = tap_dc[t] > max_dc ? tap_dc[t] : max_dc;
-  }
-  const int hr = max_dr - min_dr, hc = max_dc - min_dc;
+  int min_dr, min_dc, hr, hc;
+  pg_tap_extent(T, tap_dr, tap_dc, min_dr, hr, min_dc, hc);
   a.min_dr = min_dr; a.min_dc = min_dc;
   a.SW = OW + hc;
   const int nco = Cout < CO_CHUNK ? ((Cout + 15) / 16) * 16 : CO_CHUNK;
@@ -679,7 +673,7 @@ PG_EXPORT int pg_conv2d_wgrad(const float* x, const float* dy, float* dw, float*
   PG_REQUIRE(TR >= 1, PG_ESHAPE, "pg_conv2d_wgrad: row of %d (+%d halo) too wide for LDS", OW, hc);
   if (TR > OH) TR = OH;
   // register-prefetch staging: rows of both tensors 16-byte aligned in global memory
-  static const bool pf_on = []() { const char* e = PG_AB_ENV("PG_WGRAD_PREFETCH"); return !(e && e[0] == '0'); }();
+  static const bool pf_on = PG_AB_ON("PG_WGRAD_PREFETCH");
   a.prefetch = pf_on && (OW % 4 == 0) && (IW % 4 == 0) && ((((uintptr_t)x | (uintptr_t)dy) & 15) == 0);
   a.Qd = OW / 4;
   a.Qx = IW / 4;

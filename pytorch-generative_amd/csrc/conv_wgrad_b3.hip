@@ -912,7 +912,7 @@ __global__ void __launch_bounds__(WB_THREADS, 2) conv_wgrad_b3s_kernel(const WsA
 int pg_wgrad_b3_launch(const float* x, const float* dy, float* part, long part_stride, long max_rows,
                        int has_bias, int N, int Cin, int IH, int IW, int Cout, int OH, int OW, int T,
                        const int* tap_dr, const int* tap_dc, int in_act, hipStream_t st) {
-  static const bool on = []() { const char* e = PG_AB_ENV("PG_WGRAD_B3"); return !(e && e[0] == '0'); }();
+  static const bool on = PG_AB_ON("PG_WGRAD_B3");
   if (!on) return 0;
   if (IH != OH || IW != OW || OW % 4 != 0 || Cout % 32 != 0 || Cin % WB_CI != 0) return 0;
   int MR = Cout % WB_CO == 0 ? 2 : 1;  // 64 or 32 dy channels per workgroup
@@ -941,8 +941,8 @@ int pg_wgrad_b3_launch(const float* x, const float* dy, float* part, long part_s
   //   (2, 2) = 128 x 64 when Cout % 128 == 0: dy AND x of a 64 -> 128 layer staged once;
   //   (4, 4) = 256 x 128 for one tap (GatedPixelCNN's 1x1 128 -> 256 / 256 -> 256), one workgroup per CU.
   // PG_WGRAD_B3_RING_CFG=<WM><WN> forces a tile in the ab library.
-  static const bool ring_on = []() { const char* e = PG_AB_ENV("PG_WGRAD_B3_RING"); return !(e && e[0] == '0'); }();
-  static const int ring_cfg = []() { const char* e = PG_AB_ENV("PG_WGRAD_B3_RING_CFG"); return e ? atoi(e) : 0; }();
+  static const bool ring_on = PG_AB_ON("PG_WGRAD_B3_RING");
+  static const int ring_cfg = PG_AB_INT("PG_WGRAD_B3_RING_CFG", 0);
   const bool ring_one_tap = T == 1 && Cout % 128 == 0 && Cin % 128 == 0;  // 128 x 128 tiles, two workgroups per CU: 0.357 / 0.672 ms against the
                                                                           // big-tile kernel's 0.366 / 0.702 on 1x1 128->256 / 256->256 at batch 512
   if (ring_on && OW == 32 && Cout % 64 == 0 && Cin % 64 == 0 && (T >= 2 || ring_one_tap || ring_cfg) && (T <= 4 || T == 6) && hr <= 2) {
@@ -1019,7 +1019,7 @@ int pg_wgrad_b3_launch(const float* x, const float* dy, float* part, long part_s
     }
   }
   // 64 dy channels per workgroup: 8 waves (four per SIMD, 2 staging slots per thread); PG_WGRAD_B3_WAVES=4 for A/B
-  static const int env_waves = []() { const char* e = PG_AB_ENV("PG_WGRAD_B3_WAVES"); return (e && atoi(e) == 4) ? 4 : 8; }();
+  static const int env_waves = PG_AB_INT("PG_WGRAD_B3_WAVES", 8) == 4 ? 4 : 8;
   // tile rows: K steps of 4 pixel blocks, staging slots within the per-thread caps, LDS within budget
   auto pick_rows = [&](int co_, int ci_, long slot_cap_, long xslot_cap_ = 0) {
     if (xslot_cap_ == 0) xslot_cap_ = slot_cap_;
@@ -1037,7 +1037,7 @@ int pg_wgrad_b3_launch(const float* x, const float* dy, float* part, long part_s
   // big tiles (round 5; at most 2 taps, 8 waves): 64 x channels per workgroup, and 128 dy channels for one tap — the
   // 1x1 / 2x1 / 1x2 weight gradients are bound by staging (split + LDS writes per MFMA: profiles/r05_wgrad_pmc.json),
   // not by the matrix pipe. PG_WGRAD_B3_BIG=0 for A/B. A shape whose big tile does not fit LDS keeps the 64 x 32 tile.
-  static const bool big_on = []() { const char* e = PG_AB_ENV("PG_WGRAD_B3_BIG"); return !(e && e[0] == '0'); }();
+  static const bool big_on = PG_AB_ON("PG_WGRAD_B3_BIG");
   bool big = big_on && MR == 2 && T <= 2 && Cin % 64 == 0;
   int TR = 0;
   if (big && T == 1 && Cout % 128 == 0 && (TR = pick_rows(128, 64, 2L * 512, 512)) > 0) MR = 4;
@@ -1107,22 +1107,14 @@ int pg_wgrad_b3_launch(const float* x, const float* dy, float* part, long part_s
 int pg_wgrad_b3s_launch(const float* x, const float* dy, float* part, long part_stride, long max_rows,
                         int has_bias, int N, int Cin, int IH, int IW, int Cout, int OH, int OW, int T,
                         const int* tap_dr, const int* tap_dc, int in_act, hipStream_t st) {
-  static const bool on = []() {
-    const char* e = PG_AB_ENV("PG_WGRAD_B3");
-    const char* s = PG_AB_ENV("PG_WGRAD_B3S");
-    return !(e && e[0] == '0') && !(s && s[0] == '0');
-  }();
+  static const bool on = PG_AB_ON("PG_WGRAD_B3") && PG_AB_ON("PG_WGRAD_B3S");
   if (!on) return 0;
   if (IH != OH || IW != OW || OW % 4 != 0 || Cout % 32 != 0 || Cin % WB_CI != 0 || T < 2 || T > 9) return 0;
   if ((((uintptr_t)x | (uintptr_t)dy) & 15) != 0) return 0;
-  int min_dr = tap_dr[0], max_dr = tap_dr[0], min_dc = tap_dc[0], max_dc = tap_dc[0];
-  for (int t = 1; t < T; ++t) {
-    min_dr = tap_dr[t] < min_dr ? tap_dr[t] : min_dr;
-    max_dr = tap_dr[t] > max_dr ? tap_dr[t] : max_dr;
-    min_dc = tap_dc[t] < min_dc ? tap_dc[t] : min_dc;
-    max_dc = tap_dc[t] > max_dc ? tap_dc[t] : max_dc;
-  }
-  const int NR = max_dr - min_dr + 1, NC = max_dc - min_dc + 1;
+  int min_dr, min_dc, hr, hc;
+  pg_tap_extent(T, tap_dr, tap_dc, min_dr, hr, min_dc, hc);
+  const int max_dc = min_dc + hc;
+  const int NR = hr + 1, NC = hc + 1;
   if (min_dc < -1 || max_dc > 1 || NR > 3 || NR * NC != T) return 0;
   if (has_bias && (min_dc > 0 || max_dc < 0)) return 0;  // the bias sums read the unshifted copy
   WsArgs a;
@@ -1132,7 +1124,6 @@ int pg_wgrad_b3s_launch(const float* x, const float* dy, float* part, long part_
     if (a.tap_of[slot] >= 0) return 0;  // a repeated tap: not a full grid
     a.tap_of[slot] = t;
   }
-  const int hr = NR - 1;
   const int PBR = (OW + 7) / 8;
   int TR = 0;
   for (int tr = 1; tr <= OH + 3; ++tr) {

@@ -130,19 +130,15 @@ __global__ void __launch_bounds__(SW_THREADS) conv_wgrad_small_kernel(const SwAr
 int pg_wgrad_small_launch(const float* x, const float* dy, float* part, long part_stride, long max_rows,
                           int has_bias, int N, int Cin, int IH, int IW, int Cout, int OH, int OW, int T,
                           const int* tap_dr, const int* tap_dc, int in_act, hipStream_t st) {
-  static const bool on = []() { const char* e = PG_AB_ENV("PG_WGRAD_SMALL"); return !(e && e[0] == '0'); }();
+  static const bool on = PG_AB_ON("PG_WGRAD_SMALL");
   if (!on) return 0;
   // >= 32 output channels: with 16 (ImageGPT's 3x3 input layer) three of the four waves idle and the general
   // kernel measured faster (ImageGPT 100.0 k vs 99.2 k img/s)
   if (Cin > 4 || Cout < 32 || IH != OH || IW != OW || OW % 4 != 0 || Cin * T + (has_bias ? 1 : 0) > SW_COLS || T < 2) return 0;
   if ((((uintptr_t)dy) & 15) != 0) return 0;
   SwArgs a;
-  int min_dr = tap_dr[0], max_dr = tap_dr[0], min_dc = tap_dc[0], max_dc = tap_dc[0];
-  for (int t = 1; t < T; ++t) {
-    min_dr = tap_dr[t] < min_dr ? tap_dr[t] : min_dr; max_dr = tap_dr[t] > max_dr ? tap_dr[t] : max_dr;
-    min_dc = tap_dc[t] < min_dc ? tap_dc[t] : min_dc; max_dc = tap_dc[t] > max_dc ? tap_dc[t] : max_dc;
-  }
-  const int hr = max_dr - min_dr, hc = max_dc - min_dc;
+  int min_dr, min_dc, hr, hc;
+  pg_tap_extent(T, tap_dr, tap_dc, min_dr, hr, min_dc, hc);
   // rows per tile: about 128 pixels of dy per channel (64 x 132 floats = 33 KB) — two workgroups per CU
   int TR = 128 / OW;
   if (TR < 1) TR = 1;

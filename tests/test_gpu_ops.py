@@ -204,6 +204,26 @@ def test_conv_random_shapes(dev, seed):
     test_conv_fwd_dgrad_wgrad(dev, _random_conv_case(1000 + seed))
 
 
+def _family_cases():
+    import _conv_b3_routes as R
+
+    return R.FAMILY_CASES
+
+
+@pytest.mark.parametrize("what,case,want", _family_cases(), ids=[c[0] for c in _family_cases()])
+def test_conv_b3_kernel_families(dev, what, case, want):
+    """One small convolution per bf16x3 kernel family (staged narrow / wide, 1x1, pipelined, overlapped): pg_conv_b3_route says the
+    forward launch lands on the named instantiation, then forward and data gradient against the oracle as in
+    test_conv_fwd_dgrad_wgrad."""
+    import _conv_b3_routes as R
+    from pytorch_generative_amd import _lib
+
+    rc, r = R.route(_lib.load(), R.family_problem(case))
+    got = R.named(r)
+    assert rc == 0 and {k: got[k] for k in want} == want, (what, got)
+    test_conv_fwd_dgrad_wgrad(dev, case)
+
+
 SKIP_CASES = [
     # (N, C, H, W, Cmid, k, in_act): x -> conv1 (k x k, C -> Cmid, n_skip = 2) -> conv2 (1x1, Cmid -> C, res, res2)
     (3, 64, 28, 28, 32, 1, "relu"),   # PixelCNN's block: barrier-free 1x1 kernel, multi-stream epilogues both ways
