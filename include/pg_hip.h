@@ -552,6 +552,36 @@ int pg_attn_decode(const float* qkv, float* k_cache, float* v_cache, float* o, i
                    void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * One raster position of ALL transformer blocks of ImageGPT in one launch (csrc/gpt_decode.hip): one workgroup per
+ * sample, activations in LDS, any width. x and out: (C, ld) planes, column n = sample n, as pg_sample_embed writes them;
+ * out may be x. Per block, on one column (image_gpt.py:50-52 with :107-108):
+ *   a = LN1(h); [q | k | v] = Wqkv a + b; caches[:, p] = k, v; o = softmax_{j <= p - strict}(q . k_j / sqrt(dk)) v_j per
+ *   head (0 when no key is admitted); b = h + Wproj o + bproj; m = W2 gelu(W1 LN2(b) + b1) + b2 (erf GELU); h = h + (b + m).
+ * k_cache, v_cache: (blocks, N, C, L). The launch writes cache column p of every block and no other cache entry, and reads
+ * none beyond p. p from the host, or *pos_dev (device int, or NULL) clamped to [0, L - 1] as pg_attn_decode does.
+ * pack: the parameters of all blocks in one float buffer, block i at i * block_floats, inside a block the PG_GD_* fields
+ * at the offsets the plan reports; every weight matrix is stored TRANSPOSED, (in, out) row-major:
+ *   LN1_W, LN1_B (C) | WQKV (C, 3C) = [_q ; _kv] weights transposed, BQKV (3C) | WPROJ (C, C), BPROJ (C) |
+ *   LN2_W, LN2_B (C) | W1 (C, 4C), B1 (4C) | W2 (4C, C), B2 (C)
+ * No float atomics, every reduction in a fixed order: column n of out is bit-identical from run to run and for any N, ld.
+ * pg_gpt_decode_plan (host only, no device call) is the one function that decides the domain; the launch calls it too.
+ * It fills out[0 .. PG_GPT_DECODE_PLAN_INTS): pack floats, floats per block, LDS bytes per workgroup (at most 64 KB),
+ * threads per workgroup, then the PG_GPT_DECODE_FIELDS field offsets. C a multiple of 4 in 4..256, heads dividing C,
+ * blocks in 1..64, L in 1..4096 (PG_ESHAPE otherwise, from the plan and the launch alike, nothing launched); PG_EINVAL for
+ * a null pointer, a short array, a non-positive dimension, ld < N, strict not 0/1 or a host p outside [0, L).
+ * ------------------------------------------------------------------------------------- */
+enum {
+  PG_GD_LN1_W = 0, PG_GD_LN1_B, PG_GD_WQKV, PG_GD_BQKV, PG_GD_WPROJ, PG_GD_BPROJ,
+  PG_GD_LN2_W, PG_GD_LN2_B, PG_GD_W1, PG_GD_B1, PG_GD_W2, PG_GD_B2
+};
+#define PG_GPT_DECODE_FIELDS 12
+#define PG_GPT_DECODE_PLAN_INTS 16
+int pg_gpt_decode_plan(int C, int heads, int blocks, int L, int* out, int out_len);
+int pg_gpt_decode_step(const float* x, float* out, const float* pack, float* k_cache, float* v_cache, int N, int C,
+                       int heads, int blocks, int L, int ld, int p, int strict, float eps, const int* pos_dev,
+                       void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Optimiser step as timed by the reference (trainer.py:183-191): global grad L2 norm
  * (clip_grad_norm_) + torch.optim.Adam over ONE flat parameter/grad buffer.
  * state (device, 8 floats): [0]=step count, [1]=lr, [2]=sum of squares (scratch),

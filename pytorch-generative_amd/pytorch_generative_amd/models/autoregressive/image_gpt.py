@@ -114,27 +114,48 @@ class ImageGPT(base.AutoregressiveModel):
         return ops.add_broadcast_batch(x, self._position_term())
 
     # ---- incremental sampling -------------------------------------------------
-    def _incremental_ok(self, n):
+    def _decode_route(self, n):
+        """Which block kernels the K/V-cached sampler runs for n samples: "blocks" — the fused head / tail block kernels with
+        pg_attn_decode between them (the BASELINE shape: 16 channels, 64 hidden units), "step" — all blocks of a position in
+        one launch (ops.gpt_decode_step: any width the planner accepts), None — no cached route (a full forward per pixel)."""
+        if self._input.bias is None:
+            return None
         ld = (n + 15) // 16 * 16
         probe = torch.empty(1, self._input.weight.shape[0], 1, ld, device="meta")
-        return all(blk._fused_ok(probe) for blk in self._transformer) and self._input.bias is not None
+        if all(blk._fused_ok(probe) for blk in self._transformer):
+            return "blocks"
+        return "step" if ops.gpt_decode_supported(self) else None
+
+    def _incremental_ok(self, n):
+        return self._decode_route(n) is not None
 
     @base.dense_head
     @torch.no_grad()
-    def sample(self, n_samples=None, conditioned_on=None, *, incremental=True, return_logits=False):
+    def sample(self, n_samples=None, conditioned_on=None, *, incremental=True, return_logits=False, route=None):
         """Same contract as the reference's AutoregressiveModel.sample (models/base.py:97-120: raster
         order, only entries < 0 are drawn, `_sample_fn` called once per pixel on (n, c) logits) — but
         each step evaluates ONLY the current position: the model is causal, so the activations of
         pixel p are final once pixels < p are. One position of all samples is a (channels, batch)
         matrix, i.e. the (C, L) plane layout of the block kernels with the batch as the pixel axis:
         the fused head / tail kernels run unchanged, attention becomes a one-query-per-(n, head)
-        decode against per-layer K / V caches. The reference (and `incremental=False`) instead runs
-        one full forward per pixel: H*W times the work.
+        decode against per-layer K / V caches. At any other width the planner accepts, ONE launch per
+        position carries every sample through all blocks (ops.gpt_decode_step, `_decode_route`). The
+        reference (and `incremental=False`) instead runs one full forward per pixel: H*W times the work.
 
-        return_logits (extension): also returns the (H*W, n, c) logits the draws were made from."""
+        return_logits (extension): also returns the (H*W, n, c) logits the draws were made from.
+        route (measurement aid, tools/gpt_decode_bench.py): "step" runs the one-launch step kernel on a model that would
+        take the block kernels. The route that ran is left in `_sample_route` ("blocks", "step" or "full")."""
         canvas = self._start_canvas(n_samples, conditioned_on)
         n, c, h, w = canvas.shape
-        if not incremental or not self._incremental_ok(n):
+        decode = self._decode_route(n) if incremental else None
+        if route is not None and decode is not None:
+            if route not in ("blocks", "step") or (route == "blocks" and decode != "blocks"):
+                raise ValueError(f"sample: route {route!r} is not available for this model")
+            if route == "step" and not ops.gpt_decode_supported(self):
+                raise ValueError("sample: the step kernel does not cover this model")
+            decode = route
+        self._sample_route = decode or "full"
+        if decode is None:
             if return_logits:
                 raise ValueError("return_logits needs the incremental sampler")
             return super().sample(conditioned_on=canvas)
@@ -147,11 +168,10 @@ class ImageGPT(base.AutoregressiveModel):
         kh, kw = conv.weight.shape[2], conv.weight.shape[3]
         ops.mul_inplace_(conv.weight.data, conv.mask)  # nn/convolution.py:42, as on every forward
         blocks = list(self._transformer)
-        caches = []
-        for blk in blocks:
-            a = blk._attn
-            caches.append((torch.zeros(n, a._embed_channels, L, device=dev),
-                           torch.zeros(n, a._out_channels, L, device=dev)))
+        attn0 = blocks[0]._attn
+        k_cache = torch.zeros(len(blocks), n, attn0._embed_channels, L, device=dev)
+        v_cache = torch.zeros(len(blocks), n, attn0._out_channels, L, device=dev)
+        pack = ops.gpt_decode_pack(blocks) if decode == "step" else None  # once per call
         x = torch.zeros(1, emb, 1, ld, device=dev)
         pos_dev = torch.zeros(1, dtype=torch.int32, device=dev)  # raster position, advanced on the device
 
@@ -174,20 +194,24 @@ class ImageGPT(base.AutoregressiveModel):
                                                conv.weight.data_ptr(), conv.bias.data_ptr(), x.data_ptr(),
                                                n, c, h, w, emb, kh, kw, 0, 0, ld, pos_dev.data_ptr(), st),
                            "pg_sample_embed")
-            cur = x
-            for blk, (kc, vc) in zip(blocks, caches):
-                a = blk._attn
-                qkv, xs = ops.gpt_block_head(cur, blk._ln1, a._q, a._kv)
-                o = torch.empty(1, a._out_channels, 1, ld, device=dev)
-                _lib.check(lib.pg_attn_decode(qkv.data_ptr(), kc.data_ptr(), vc.data_ptr(),
-                                              o.data_ptr(), n, a._n_heads, L, 0,
-                                              a._embed_channels // a._n_heads,
-                                              a._out_channels // a._n_heads, ld, int(a._mask_center),
-                                              pos_dev.data_ptr(), st), "pg_attn_decode")
-                cur = ops.gpt_block_tail(o, xs, a._proj, blk._ln2, blk._out[0], blk._out[2])
+            if decode == "step":  # every block of the position in one launch, in place
+                cur = ops.gpt_decode_step(x, pack, k_cache, v_cache, pos_dev, heads=attn0._n_heads,
+                                          strict=int(attn0._mask_center), eps=blocks[0]._ln1.eps)
+            else:
+                cur = x
+                for blk, kc, vc in zip(blocks, k_cache, v_cache):
+                    a = blk._attn
+                    qkv, xs = ops.gpt_block_head(cur, blk._ln1, a._q, a._kv)
+                    o = torch.empty(1, a._out_channels, 1, ld, device=dev)
+                    _lib.check(lib.pg_attn_decode(qkv.data_ptr(), kc.data_ptr(), vc.data_ptr(),
+                                                  o.data_ptr(), n, a._n_heads, L, 0,
+                                                  a._embed_channels // a._n_heads,
+                                                  a._out_channels // a._n_heads, ld, int(a._mask_center),
+                                                  pos_dev.data_ptr(), st), "pg_attn_decode")
+                    cur = ops.gpt_block_tail(o, xs, a._proj, blk._ln2, blk._out[0], blk._out[2])
             return self._out(self._ln(cur))[0, :, 0, :n].t().contiguous()
 
-        # One hipGraph = one position of every layer (~30 launches) + the position increment; only the
+        # One hipGraph = one position of every layer (~30 launches; a handful on the step kernel) + the position increment; only the
         # draw (`_sample_fn` is user code) and the canvas update stay eager. Falls back to eager
         # launches if the capture is refused.
         graph, static_logits = None, None

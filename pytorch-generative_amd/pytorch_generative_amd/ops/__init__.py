@@ -115,6 +115,12 @@ from pytorch_generative_amd.ops.gpt_ends import (  # noqa: F401
     _GPTOutHead,
     gpt_out_head,
 )
+from pytorch_generative_amd.ops.gpt_decode import (  # noqa: F401
+    gpt_decode_plan,
+    gpt_decode_supported,
+    gpt_decode_pack,
+    gpt_decode_step,
+)
 from pytorch_generative_amd.ops.attention import (  # noqa: F401
     _CausalAttention,
     _CausalAttentionQKV,

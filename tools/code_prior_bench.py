@@ -18,8 +18,9 @@ routes alternate, window by window, in the same run (helpers of tools/linear_cat
     (torch.cuda.max_memory_allocated over what was allocated before its model was built),
     `input_codes` on, and off with the one-hot tensor built inside the step.
 (c) `sample`: one sample(64) of a prior over 8 x 8 code images, incremental and incremental=False, wall clock around a
-    device synchronise: the recipe's 64-channel model (its blocks are outside the incremental sampler's kernels, so both
-    calls run a full forward per position) and a 16-channel, 4-head one (K/V-cached sampler with pg_sample_embed_codes).
+    device synchronise: the recipe's 64-channel model (K/V-cached on the one-launch step kernel, ops.gpt_decode_step;
+    tools/gpt_decode_bench.py measures it at more shapes) and a 16-channel, 4-head one (K/V-cached on the block kernels),
+    both with pg_sample_embed_codes.
 No routing threshold is derived from this: input_codes is the user's switch. `code_is_slower` marks the shapes where it loses."""
 
 import argparse
