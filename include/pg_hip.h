@@ -582,6 +582,33 @@ int pg_gpt_decode_step(const float* x, float* out, const float* pack, float* k_c
                        void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Row-cached sampling of the convolutional models with attention (PixelSNAIL; csrc/attention_row.hip): the W queries of
+ * image row r against K / V caches of the rows above, one launch of a static shape. All tensors contiguous fp32, dk / dv
+ * per head, head h owning the channel block [h*d, (h+1)*d) (reference nn/attention.py, _to_multihead):
+ *   q_row (N, heads*dk, 1, W); kv_row (N, heads*dk + heads*dv, 1, W), keys first; k_cache (N, heads*dk, H, W);
+ *   v_cache (N, heads*dv, H, W); o_row (N, heads*dv, 1, W).
+ * Query column x of row r admits every cache key of rows y < r, the keys x' < x of row r, and x' == x when mask_center is 0;
+ * the keys and values of row r itself come from kv_row, never from the cache.
+ *   o = sum_j softmax_j(q . k_j / sqrt(dk)) v_j over the admitted set; exactly 0 when nothing is admitted.
+ * write_cache = 1: the launch also stores kv_row's k and v, bit for bit, into cache row r. It reads no cache row >= r and
+ * writes no row other than r. r from the host, or *row_dev (device int, or NULL) clamped to [0, H - 1], the host r then
+ * being ignored, as pg_attn_decode treats pos_dev: one captured hipGraph replays for every row.
+ * No float atomics, every reduction in a fixed order: sample n's output is bit-identical from run to run and for any N.
+ * pg_attn_row_plan (host only, no device call) is the one function that decides the domain and the launch geometry; the
+ * launch calls it too. It fills out[0 .. PG_ATTN_ROW_PLAN_INTS): threads per workgroup, LDS bytes per workgroup, keys per
+ * LDS tile, grid x (workgroups per row), grid y (heads; grid z is N), queries per workgroup. heads >= 1, dk in 1..64,
+ * dv in 1..128, W in 1..256, H*W <= 4096 (PG_ESHAPE otherwise, from the plan and the launch alike, and from the launch for
+ * N above 65535; nothing launched); PG_EINVAL for a null pointer, a short array, a non-positive dimension, a host r outside
+ * [0, H) or a flag that is not 0/1.
+ *   pg_row_gather: dst (N, C, 1, W) = src (N, C, H, W)[:, :, r], r as above (the positional-encoding row of the step).
+ * ------------------------------------------------------------------------------------- */
+#define PG_ATTN_ROW_PLAN_INTS 6
+int pg_attn_row_plan(int heads, int dk, int dv, int H, int W, int* out, int out_len);
+int pg_attn_row(const float* q_row, const float* kv_row, float* k_cache, float* v_cache, float* o_row, int N, int heads,
+                int dk, int dv, int H, int W, int r, int mask_center, int write_cache, const int* row_dev, void* stream);
+int pg_row_gather(const float* src, float* dst, int N, int C, int H, int W, int r, const int* row_dev, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Optimiser step as timed by the reference (trainer.py:183-191): global grad L2 norm
  * (clip_grad_norm_) + torch.optim.Adam over ONE flat parameter/grad buffer.
  * state (device, 8 floats): [0]=step count, [1]=lr, [2]=sum of squares (scratch),

@@ -88,6 +88,9 @@ SIGNATURES = {
     "pg_attn_decode": (c_i, [c_f] * 4 + [c_i] * 8 + [c_f, c_s]),
     "pg_gpt_decode_plan": (c_i, [c_i] * 4 + [c_ip, c_i]),
     "pg_gpt_decode_step": (c_i, [c_f] * 5 + [c_i] * 8 + [c_flt, c_f, c_s]),
+    "pg_attn_row_plan": (c_i, [c_i] * 5 + [c_ip, c_i]),
+    "pg_attn_row": (c_i, [c_f] * 5 + [c_i] * 9 + [c_f, c_s]),
+    "pg_row_gather": (c_i, [c_f, c_f] + [c_i] * 5 + [c_f, c_s]),
     "pg_mlp_gelu_fwd": (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_s]),
     "pg_mlp_gelu_bwd": (
         c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_f, c_z, c_s]),

@@ -118,7 +118,14 @@ class PixelSNAILBlock(nn.Module):
 
 class PixelSNAIL(base.AutoregressiveModel):
     _row_decode = True  # every layer is row-causal: sample() runs row by row (models/base.py)
-    _row_decode_min_batch = 64  # its row step (attention over a growing prefix) runs eagerly: pays off at larger batches
+    # Its attention reads K / V caches with the row index taken from the device (ops.attention_row, ops.row_gather): the row
+    # step is the same sequence of launches for every row, so sample() captures it as it does for the PixelCNNs.
+    _row_graph = True
+    # The smallest measured batch at which the graphed row route beats one full forward per pixel is 1 (it was 64 while the row
+    # step ran eagerly). profiles/pixelsnail_sampling.json, whole sample() calls, graphed row route / full forward per pixel:
+    # 1 x 28 x 28: 1.54 / 2.87 s at n = 1, 1.76 / 3.00 s at 16, 1.86 / 2.98 s at 64, 2.01 / 3.98 s at 256;
+    # 3 x 32 x 32: 2.16 / 4.22 s at n = 1, 2.41 / 3.90 s at 16, 2.53 / 3.96 s at 64, 2.79 / 6.04 s at 256.
+    _row_decode_min_batch = 1
 
     def __init__(
         self,

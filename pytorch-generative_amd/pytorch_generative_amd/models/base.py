@@ -89,7 +89,7 @@ class AutoregressiveModel(GenerativeModel):
     # Models whose every layer is row-causal set this: sample() then evaluates one image ROW per step
     # against per-layer caches of the rows above (ops.RowDecode) instead of the whole image.
     _row_decode = False
-    _row_graph = False            # the row step is identical for every row (no attention): hipGraph it
+    _row_graph = False            # the row step is identical for every row (attention: row index from the device): hipGraph it
     _row_decode_min_batch = 1     # below this batch the per-pixel full forward is used (launch-bound row steps)
 
     # True (extension; an attribute, not a constructor argument: signatures and state_dict stay the reference's): the models
@@ -143,8 +143,8 @@ class AutoregressiveModel(GenerativeModel):
             reset()
             row_in = torch.empty((n, c, 1, w), device=canvas.device, dtype=canvas.dtype)
             with ops.RowDecode(h) as ctx:
-                # Row-invariant models (no attention): the row step touches the same buffers for every
-                # row, so it is captured ONCE into two hipGraphs (evaluate / evaluate-and-commit) and
+                # Row-invariant models (no attention, or attention that takes the row index from ctx.row_dev):
+                # the row step touches the same buffers for every row, so it is captured ONCE into two hipGraphs (evaluate / evaluate-and-commit) and
                 # replayed H*W + H times — the eager row step is ~100 tiny launches, launch bound.
                 step_graph = commit_graph = step_out = None
                 if self._row_graph:

@@ -31,7 +31,7 @@ def image_positional_encoding(shape, device=None):
     if ctx is not None:  # row-cached sampling: `shape` is one image row; return that row of the full map
         n, c, _, w = (int(s) for s in shape)
         full = _posenc_cached((n, c, ctx.height, w), torch.device(device))
-        return full[:, :, ctx.row:ctx.row + 1, :].contiguous()
+        return ops.row_gather(full, ctx.row_dev)  # the row index from the device: the same launch for every row
     return _posenc_cached(tuple(int(s) for s in shape), torch.device(device))
 
 
@@ -67,15 +67,41 @@ class CausalAttention(nn.Module):
             self._kv.weight._pg_follows = self._q.weight
             self._kv.bias._pg_follows = self._q.bias
 
+    # Route of the row-cached sampler (extension; an attribute like `defer_head`, not a constructor argument):
+    #   "decode": ops.attention_row on K / V caches — the row's queries only, the row index from the device, so the step is
+    #             the same for every row and base.sample captures it; shapes outside the kernel's domain take "prefix";
+    #   "prefix": the training kernel over all rows <= r, of which the last row is kept (cannot be captured).
+    row_attention = "decode"
+
     def _row_reset(self):
-        self._row_q = self._row_kv = None
+        self._row_q = self._row_kv = self._row_k = self._row_v = None
 
     def _row_forward(self, ctx, x, extra_x, res):
-        """Row-cached sampling: x / extra_x are row `ctx.row`. The row's q / k / v are written into
-        full-size caches and the attention core runs over rows <= ctx.row (everything an earlier
-        position contributed is final); only the current row of the output is kept."""
+        """Row-cached sampling: x / extra_x are row `ctx.row`. The row's queries attend to the K / V caches of the rows
+        above and to the row's own keys (ops.attention_row); a committing pass stores the row's k / v into the caches. No
+        cache row >= ctx.row is ever read, so what an earlier pass left there (the warm-up's rows) does not matter."""
+        if self.row_attention not in ("decode", "prefix"):
+            raise ValueError(f"CausalAttention.row_attention: {self.row_attention!r} (expected 'decode' or 'prefix')")
         q = self._q(x)
         kv = self._kv(x if extra_x is None else torch.cat((x, extra_x), dim=1))
+        n, _, _, w = q.shape
+        e, o, heads = self._embed_channels, self._out_channels, self._n_heads
+        if (self.row_attention == "decode" and e % heads == 0 and o % heads == 0
+                and ops.attention_row_supported(heads, e // heads, o // heads, ctx.height, w)):
+            if getattr(self, "_row_k", None) is None or self._row_k.shape[0] != n or self._row_k.shape[3] != w:
+                self._row_k = torch.zeros((n, e, ctx.height, w), device=q.device)
+                self._row_v = torch.zeros((n, o, ctx.height, w), device=q.device)
+            out = ops.attention_row(q, kv, self._row_k, self._row_v, heads, self._mask_center, row=ctx.row_dev,
+                                    write_cache=ctx.commit)
+            return self._proj(out, res=res)
+        return self._row_forward_prefix(ctx, q, kv, res)
+
+    def _row_forward_prefix(self, ctx, q, kv, res):
+        """The row's q / k / v are written into full-size caches and the attention core runs over rows <= ctx.row
+        (everything an earlier position contributed is final); only the current row of the output is kept."""
+        if torch.cuda.is_current_stream_capturing():
+            # the prefix length is a tensor shape and the row a host int: a capture would freeze row 0 into the graph
+            raise RuntimeError("CausalAttention: the 'prefix' row route depends on the row index and cannot be captured")
         n, _, _, w = q.shape
         if getattr(self, "_row_q", None) is None or self._row_q.shape[0] != n or self._row_q.shape[3] != w:
             self._row_q = torch.zeros((n, q.shape[1], ctx.height, w), device=q.device)

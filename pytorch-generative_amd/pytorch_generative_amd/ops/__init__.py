@@ -121,6 +121,12 @@ from pytorch_generative_amd.ops.gpt_decode import (  # noqa: F401
     gpt_decode_pack,
     gpt_decode_step,
 )
+from pytorch_generative_amd.ops.attention_row import (  # noqa: F401
+    attention_row_plan,
+    attention_row_supported,
+    attention_row,
+    row_gather,
+)
 from pytorch_generative_amd.ops.attention import (  # noqa: F401
     _CausalAttention,
     _CausalAttentionQKV,

@@ -26,14 +26,39 @@ class RowDecode:
     While active, the convolutional models' ordinary forward() is called on ONE image row
     (N, C, 1, W): every layer of these models is row-causal (its output row r depends on input rows
     <= r only), so nn.Conv2d keeps the last k input rows it needs (k = upward reach of its taps) in a
-    private band buffer and evaluates only the current row; nn.CausalAttention keeps its q / k / v
-    maps; image_positional_encoding returns the current row of the full-size encoding. `commit`
-    marks the pass that runs once a row is final and pushes it into the caches."""
+    private band buffer and evaluates only the current row; nn.CausalAttention keeps K / V caches of
+    the rows above (ops.attention_row); image_positional_encoding returns the current row of the full-size encoding. `commit`
+    marks the pass that runs once a row is final and pushes it into the caches.
+
+    `row_dev` is the row index as an int32 device scalar for the kernels that take it from the device (ops.attention_row,
+    ops.row_gather): a row step that uses it instead of `row` is the same sequence of launches for every row, so it can be
+    captured into a hipGraph. It is created on first request (on `device`, default the current GPU) and from then on every
+    assignment to `row` also fills it — a fill on the current stream, no host synchronisation."""
 
     current = None
 
-    def __init__(self, height):
-        self.height, self.row, self.commit = int(height), 0, False
+    def __init__(self, height, device=None):
+        self.height, self.commit = int(height), False
+        self._device, self._row, self._row_dev = device, 0, None
+
+    @property
+    def row(self):
+        return self._row
+
+    @row.setter
+    def row(self, value):
+        self._row = int(value)
+        if self._row_dev is not None:
+            self._row_dev.fill_(self._row)
+
+    @property
+    def row_dev(self):
+        if self._row_dev is None:
+            if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("RowDecode.row_dev: first requested inside a stream capture (its fill would be replayed)")
+            device =self._device if self._device is not None else torch.device("cuda", torch.cuda.current_device())
+            self._row_dev = torch.full((1,), self._row, dtype=torch.int32, device=device)
+        return self._row_dev
 
     def __enter__(self):
         RowDecode.current = self
