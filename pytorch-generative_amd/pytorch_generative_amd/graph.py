@@ -23,7 +23,64 @@ step; `trainer.Trainer` therefore uses the graph only when its `train_one_batch`
 overridden (or the caller opts in).
 """
 
+import contextlib
+import gc
+import os
+
 import torch
+
+
+@contextlib.contextmanager
+def no_gc():
+    """No cyclic garbage collection while a capture is open: a collection that happens to run inside the region may destroy
+    an older step's graph / tensors (closures of the step functions form cycles), and freeing device memory or a graph
+    while the stream is capturing aborts the process (round 6: the reference-suite tier died in the VD-VAE capture once the
+    model's forward created enough objects to trigger a collection there). torch.cuda.graph collects BEFORE it begins.
+    The previous state comes back on exit, also after an exception; collection that was off stays off."""
+    was_on = gc.isenabled()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if was_on:
+            gc.enable()
+
+
+def warm_up(fn):
+    """fn() on a side stream that joins the current stream before and after, as a capture needs it: every buffer the step
+    allocates lazily exists afterwards. Returns fn's result."""
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        result = fn()
+    torch.cuda.current_stream().wait_stream(side)
+    return result
+
+
+def capture(fn):
+    """Captures fn() into a hipGraph under no_gc(); returns (graph, fn's result: static tensors the replays overwrite)."""
+    with no_gc():
+        graph = torch.cuda.CUDAGraph()
+        # thread_local: RCCL's watchdog thread may touch the HIP runtime while we capture
+        with torch.cuda.graph(graph, capture_error_mode="thread_local"):
+            result = fn()
+    return graph, result
+
+
+def try_capture(steps, warmup=None):
+    """A capture that is an optimisation only (the samplers): warm_up(warmup), then capture() of every callable that the
+    iterable `steps` yields (a generator may prepare host state between two captures); returns the [(graph, result)].
+    The first Exception ends the attempt: the device is synchronised and None returned, for the caller to drop whatever the
+    warm-up cached and launch eagerly. PG_DEBUG prints the reason (the fallback is silent otherwise)."""
+    try:
+        if warmup is not None:
+            warm_up(warmup)
+        return [capture(step) for step in steps]
+    except Exception as e:  # noqa: BLE001
+        if os.environ.get("PG_DEBUG"):
+            print(f"[sample] row-step capture failed: {type(e).__name__}: {e}")
+        torch.cuda.synchronize()
+        return None
 
 
 class GraphedTrainStep:
@@ -52,22 +109,21 @@ class GraphedTrainStep:
         self.split = self.reduce and (not reducer.capturable or getattr(reducer, "force_split", False))
         self.static_x = example_x.clone()
         self.static_y = None if example_y is None else example_y.clone()
-        self.static_out = None
 
         saved = None
         if preserve_state:
             saved = [t.clone() for t in (optimizer.flat_param, optimizer.exp_avg, optimizer.exp_avg_sq,
                                          optimizer.state_block)]
             saved_buffers = [(b, b.clone()) for b in model.buffers()]
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
+
+        def warm():
             for _ in range(warmup_iters):
                 self._fwd_bwd()
                 if self.reduce:
                     reducer.all_reduce()
                 self.opt.step()
-        torch.cuda.current_stream().wait_stream(side)
+
+        warm_up(warm)
         torch.cuda.synchronize()
         if saved is not None:
             for dst, src in zip((optimizer.flat_param, optimizer.exp_avg, optimizer.exp_avg_sq,
@@ -76,32 +132,16 @@ class GraphedTrainStep:
             for b, src in saved_buffers:
                 b.copy_(src)
 
-        # thread_local: RCCL's watchdog thread may touch the HIP runtime while we capture
-        mode = dict(capture_error_mode="thread_local")
-        # No cyclic garbage collection while a capture is open: a collection that happens to run inside the region may destroy
-        # an older step's graph / tensors (closures of the step functions form cycles), and freeing device memory or a graph
-        # while the stream is capturing aborts the process (round 6: the reference-suite tier died in the VD-VAE capture once the
-        # model's forward created enough objects to trigger a collection there). torch.cuda.graph collects BEFORE it begins.
-        import gc
+        def step_a():
+            out = self._fwd_bwd()
+            if not self.split:
+                if self.reduce:
+                    reducer.all_reduce()  # captured: an ordinary stream op of the C-ABI
+                self.opt.step()
+            return out
 
-        gc_was_on = gc.isenabled()
-        gc.disable()
-        try:
-            self.graph_a = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph_a, **mode):
-                self.static_out = self._fwd_bwd()
-                if not self.split:
-                    if self.reduce:
-                        reducer.all_reduce()  # captured: an ordinary stream op of the C-ABI
-                    self.opt.step()
-            self.graph_b = None
-            if self.split:
-                self.graph_b = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(self.graph_b, **mode):
-                    self.opt.step()
-        finally:
-            if gc_was_on:
-                gc.enable()
+        self.graph_a, self.static_out = capture(step_a)
+        self.graph_b = capture(self.opt.step)[0] if self.split else None
 
     def _fwd_bwd(self):
         self.opt.zero_grad()

@@ -11,6 +11,7 @@ import torch
 from torch import nn
 
 from pytorch_generative_amd import _lib
+from pytorch_generative_amd import graph as pg_graph
 from pytorch_generative_amd import nn as pg_nn
 from pytorch_generative_amd import ops
 from pytorch_generative_amd.models import base
@@ -211,23 +212,16 @@ class ImageGPT(base.AutoregressiveModel):
                     cur = ops.gpt_block_tail(o, xs, a._proj, blk._ln2, blk._out[0], blk._out[2])
             return self._out(self._ln(cur))[0, :, 0, :n].t().contiguous()
 
+        def step():
+            logits = position_logits()
+            pos_dev.add_(1)
+            return logits
+
         # One hipGraph = one position of every layer (~30 launches; a handful on the step kernel) + the position increment; only the
         # draw (`_sample_fn` is user code) and the canvas update stay eager. Falls back to eager
-        # launches if the capture is refused.
-        graph, static_logits = None, None
-        try:
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                position_logits()  # warm-up at position 0 (rewrites cache column 0 with the same values)
-            torch.cuda.current_stream().wait_stream(side)
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph, capture_error_mode="thread_local"):
-                static_logits = position_logits()
-                pos_dev.add_(1)
-        except Exception:  # noqa: BLE001 — capture is an optimisation only
-            graph = None
-            torch.cuda.synchronize()
+        # launches if the capture is refused. (The warm-up at position 0 rewrites cache column 0 with the same values.)
+        pairs = pg_graph.try_capture([step], position_logits)
+        graph, static_logits = pairs[0] if pairs else (None, None)
         pos_dev.zero_()
         all_logits = []
         for row in range(h):
@@ -236,13 +230,10 @@ class ImageGPT(base.AutoregressiveModel):
                     graph.replay()
                     logits = static_logits.clone() if return_logits else static_logits
                 else:
-                    logits = position_logits()
-                    pos_dev.add_(1)
+                    logits = step()
                 if return_logits:
                     all_logits.append(logits)
-                drawn = self._sample_fn(logits).view(n, c)
-                current = canvas[:, :, row, col]
-                canvas[:, :, row, col] = torch.where(current < 0, drawn, current)
+                self._draw_into(canvas, row, col, logits)
         if return_logits:
             return canvas, torch.stack(all_logits)
         return canvas

@@ -294,11 +294,6 @@ class PixelCNNpp(base.AutoregressiveModel):
         row_in = torch.zeros((n, 3, 1, w), device=dev)
         pos_dev = torch.zeros(1, dtype=torch.int32, device=dev)  # the raster position the captured draw reads
 
-        def reset():
-            for m in self.modules():
-                if hasattr(m, "_row_reset"):
-                    m._row_reset()
-
         def step(ctx, target, host_pos=None):
             """The parameters of row ctx.row and (without a sample_fn) the draw of one pixel of `target` from them"""
             out = self._row_net(ctx, row_in)
@@ -308,45 +303,13 @@ class PixelCNNpp(base.AutoregressiveModel):
                                 pos_dev=pos_dev if host_pos is None else None)
             return out
 
-        reset()
+        ops.RowDecode.drop_caches(self)
         with ops.RowDecode(h) as ctx:
-            # The row step differs only by which levels are due: three row classes, each captured ONCE into a step graph
-            # (row forward + the draw at pos_dev) and a commit graph (the pattern of base.AutoregressiveModel.sample).
-            class_rows = {2: 0, 1: 2, 0: 1}  # deepest level evaluated -> a row of that class
-            graphs = None
-            if self._row_graph:
-                try:
-                    side = torch.cuda.Stream()
-                    side.wait_stream(torch.cuda.current_stream())
-                    scratch = canvas.clone()  # the warm-up's draws land here
-                    with torch.cuda.stream(side):  # warm-up: allocates every band buffer and constant
-                        for r0 in class_rows.values():
-                            ctx.row, ctx.commit = r0, False
-                            step(ctx, scratch)
-                            ctx.commit = True
-                            step(ctx, scratch)
-                    torch.cuda.current_stream().wait_stream(side)
-                    graphs = {}
-                    for cls, r0 in class_rows.items():
-                        sg, cg = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-                        ctx.row, ctx.commit = r0, False
-                        with torch.cuda.graph(sg, capture_error_mode="thread_local"):
-                            out = step(ctx, canvas)
-                        ctx.commit = True
-                        with torch.cuda.graph(cg, capture_error_mode="thread_local"):
-                            step(ctx, canvas)
-                        graphs[cls] = (sg, cg, out)
-                    for m in self.modules():  # the warm-up pushed rows of zeros: start clean
-                        band = getattr(m, "_row_band", None)
-                        if band is not None:
-                            band.zero_()
-                except Exception as e:  # noqa: BLE001 — capture is an optimisation only
-                    import os
-                    if os.environ.get("PG_DEBUG"):
-                        print(f"[sample] row-step capture failed: {type(e).__name__}: {e}")
-                    graphs = None
-                    torch.cuda.synchronize()
-                    reset()
+            # The row step differs only by which levels are due: three row classes (deepest level evaluated -> a row of that
+            # class), each with a step graph (row forward + the draw at pos_dev) and a commit graph
+            scratch = canvas.clone() if self._row_graph else None  # the warm-up's draws land here
+            graphs = self._capture_row_steps(ctx, lambda: step(ctx, canvas), {2: 0, 1: 2, 0: 1},
+                                             warm_step=lambda: step(ctx, scratch))
             schedule = row_schedule(h)
             for row in range(h):
                 cls = schedule[row][-1][0]
@@ -372,7 +335,7 @@ class PixelCNNpp(base.AutoregressiveModel):
                     graphs[cls][1].replay()
                 else:
                     step(ctx, canvas)
-        reset()
+        ops.RowDecode.drop_caches(self)
         return (canvas, params_map) if return_params else canvas
 
 

@@ -119,6 +119,42 @@ class AutoregressiveModel(GenerativeModel):
             return conv(pre_ln(features))
         return conv(features, in_act=in_act)
 
+    def _draw_into(self, canvas, row, col, logits):
+        """One pixel of every image: what was given (>= 0) is kept, the rest drawn by `_sample_fn` from the (N, C) logits."""
+        n, c = canvas.shape[:2]
+        drawn = self._sample_fn(logits).view(n, c)
+        current = canvas[:, :, row, col]
+        canvas[:, :, row, col] = torch.where(current < 0, drawn, current)
+
+    def _capture_row_steps(self, ctx, step, class_rows, warm_step=None):
+        """The row graphs of a row-cached sampler: step() is the row step under `ctx` (an open ops.RowDecode) and class_rows
+        {class: a row of that class, None = the step is the same for every row and ctx.row stays as it is}. Per class the
+        step is captured ONCE into two hipGraphs, evaluate and evaluate-and-commit — the eager row step is ~100 tiny launches,
+        launch bound. All warm-up passes (warm_step, default step: evaluate, then commit, per class; they allocate every
+        cache) run first on a side stream, then the captures; then the caches are cleared of what those passes pushed.
+        Returns {class: (step graph, commit graph, step's static result)}, or None with the caches dropped when `_row_graph`
+        is off or the capture was refused (`_row_step_captured` tells which: the fallback is silent)."""
+        from pytorch_generative_amd import graph, ops
+
+        def passes(fn):
+            for row in class_rows.values():
+                for commit in (False, True):
+                    if row is not None:
+                        ctx.row = row
+                    ctx.commit = commit
+                    yield fn
+
+        pairs = None
+        if self._row_graph:
+            pairs = graph.try_capture(passes(step), lambda: [fn() for fn in passes(warm_step or step)])
+            if pairs is None:
+                ops.RowDecode.drop_caches(self)
+        self._row_step_captured = pairs is not None
+        if pairs is None:
+            return None
+        ops.RowDecode.clear_caches(self)
+        return {cls: (pairs[2 * i][0], pairs[2 * i + 1][0], pairs[2 * i][1]) for i, cls in enumerate(class_rows)}
+
     @dense_head
     @torch.no_grad()
     def sample(self, n_samples=None, conditioned_on=None, *, incremental=True, return_logits=False):
@@ -135,51 +171,15 @@ class AutoregressiveModel(GenerativeModel):
         if incremental and self._row_decode and (n >= self._row_decode_min_batch or return_logits):
             from pytorch_generative_amd import ops
 
-            def reset():
-                for m in self.modules():
-                    if hasattr(m, "_row_reset"):
-                        m._row_reset()
-
-            reset()
+            ops.RowDecode.drop_caches(self)
             row_in = torch.empty((n, c, 1, w), device=canvas.device, dtype=canvas.dtype)
             with ops.RowDecode(h) as ctx:
-                # Row-invariant models (no attention, or attention that takes the row index from ctx.row_dev):
-                # the row step touches the same buffers for every row, so it is captured ONCE into two hipGraphs (evaluate / evaluate-and-commit) and
-                # replayed H*W + H times — the eager row step is ~100 tiny launches, launch bound.
-                step_graph = commit_graph = step_out = None
+                # Row-invariant models (no attention, or attention that takes the row index from ctx.row_dev): the row step
+                # touches the same buffers for every row, so one pair of graphs is replayed H*W + H times
                 if self._row_graph:
-                    try:
-                        row_in.fill_(0.0)
-                        side = torch.cuda.Stream()
-                        side.wait_stream(torch.cuda.current_stream())
-                        with torch.cuda.stream(side):  # warm-up: allocates every band buffer
-                            ctx.commit = False
-                            self.forward(row_in)
-                            ctx.commit = True
-                            self.forward(row_in)
-                        torch.cuda.current_stream().wait_stream(side)
-                        step_graph, commit_graph = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-                        ctx.commit = False
-                        with torch.cuda.graph(step_graph, capture_error_mode="thread_local"):
-                            step_out = self.forward(row_in)
-                        ctx.commit = True
-                        with torch.cuda.graph(commit_graph, capture_error_mode="thread_local"):
-                            self.forward(row_in)
-                        for m in self.modules():  # the warm-up pushed rows of zeros: start clean
-                            band = getattr(m, "_row_band", None)
-                            if band is not None:
-                                band.zero_()
-                            band = getattr(m, "_row_code_band", None)
-                            if band is not None:  # a band of levels: -1 = no code (Conv2d.forward_codes)
-                                band.fill_(-1.0)
-                    except Exception as e:  # noqa: BLE001 — capture is an optimisation only
-                        import os
-                        if os.environ.get("PG_DEBUG"):
-                            print(f"[sample] row-step capture failed: {type(e).__name__}: {e}")
-                        step_graph = commit_graph = None
-                        torch.cuda.synchronize()
-                        reset()
-                self._row_step_captured = step_graph is not None  # for inspection: the capture falls back silently
+                    row_in.fill_(0.0)
+                graphs = self._capture_row_steps(ctx, lambda: self.forward(row_in), {0: None})
+                step_graph, commit_graph, step_out = graphs[0] if graphs else (None, None, None)
                 for row in range(h):
                     ctx.row, ctx.commit = row, False
                     for col in range(w):
@@ -191,23 +191,19 @@ class AutoregressiveModel(GenerativeModel):
                             logits = self.forward(row_in)[:, :, 0, col]
                         if return_logits:
                             logits_map[:, :, row, col] = logits
-                        drawn = self._sample_fn(logits).view(n, c)
-                        current = canvas[:, :, row, col]
-                        canvas[:, :, row, col] = torch.where(current < 0, drawn, current)
+                        self._draw_into(canvas, row, col, logits)
                     ctx.commit = True  # the row is final: push it into every layer's cache
                     row_in.copy_(canvas[:, :, row:row + 1, :])
                     if commit_graph is not None:
                         commit_graph.replay()
                     else:
                         self.forward(row_in)
-            reset()
+            ops.RowDecode.drop_caches(self)
             return (canvas, logits_map) if return_logits else canvas
         for row in range(h):
             for col in range(w):
                 logits = self.forward(canvas)[:, :, row, col]
                 if return_logits:
                     logits_map[:, :, row, col] = logits
-                drawn = self._sample_fn(logits).view(n, c)
-                current = canvas[:, :, row, col]
-                canvas[:, :, row, col] = torch.where(current < 0, drawn, current)
+                self._draw_into(canvas, row, col, logits)
         return (canvas, logits_map) if return_logits else canvas

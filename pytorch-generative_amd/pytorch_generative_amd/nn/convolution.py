@@ -70,39 +70,57 @@ class Conv2d(nn.Conv2d):
         self._row_code_band = None
         self._row_spec_cached = None
 
-    def _row_forward(self, ctx, x, crop, in_act, res, out_act):
-        """x is row `ctx.row` of this convolution's input: evaluates the same row of the output from
-        a band of the k + 1 most recent input rows (k = how far the active taps reach upward)."""
-        if self._down2:
-            raise ValueError("row decode: strided convolutions are not row-causal")
+    def _row_clear(self):
+        """The bands as a new image finds them, in place (captured row steps hold their addresses)."""
+        if getattr(self, "_row_band", None) is not None:
+            self._row_band.zero_()
+        if getattr(self, "_row_code_band", None) is not None:
+            self._row_code_band.fill_(-1.0)  # a band of levels: -1 = no code (forward_codes)
+
+    def _row_step(self, ctx, x, crop, band_name, empty, launch):
+        """What _row_forward and _row_forward_codes share: x is row `ctx.row` of this convolution's input; the same row of
+        the output is launch(band, row spec, (1, output width)) on a band of the k + 1 most recent input rows (k = how far
+        the active taps reach upward), kept in the attribute `band_name` and allocated full of `empty`. A committing pass
+        (the row is final) makes it the newest cached row."""
         spec = self._conv_spec()
         reach = [spec.pad_h - u for u, _ in spec.fwd_taps]  # rows above the output row a tap reads
         if min(reach) < 0:
             raise ValueError("row decode: a tap below the output row (the layer is not row-causal)")
         k = max(reach)
-        n, c, one, w = x.shape
-        if one != 1:
-            raise ValueError("row decode expects one image row")
+        n, c, _, w = x.shape
         if getattr(self, "_row_spec_cached", None) is None:
-            self._row_spec_cached = ops.ConvSpec(spec.kh, spec.kw, spec.pad_h - k, spec.pad_w,
-                                                 active=spec.fwd_taps)
+            self._row_spec_cached = ops.ConvSpec(spec.kh, spec.kw, spec.pad_h - k, spec.pad_w, active=spec.fwd_taps)
         if k == 0:
             band = x
         else:
-            if getattr(self, "_row_band", None) is None or self._row_band.shape != (n, c, k + 1, w):
-                self._row_band = torch.zeros((n, c, k + 1, w), device=x.device, dtype=x.dtype)
-            band = self._row_band
+            band = getattr(self, band_name, None)
+            if band is None or band.shape != (n, c, k + 1, w):
+                band = torch.full((n, c, k + 1, w), empty, device=x.device, dtype=x.dtype)
+                setattr(self, band_name, band)
             band[:, :, k:, :].copy_(x)
         ow = crop[1] if crop is not None else spec.full_out(1, w)[1]
-        y = ops.conv2d_taps(band, self.weight, self.bias, self._row_spec_cached, out_hw=(1, ow),
-                            in_act=_ACTS[in_act], res=None if out_act is not None else res)
-        if out_act is not None:  # (one row: the unfused epilogue is three tiny launches)
-            y = ops._Act.apply(y, _ACTS[out_act])
-            if res is not None:
-                y = ops.add(y, res)
-        if ctx.commit and k > 0:  # the row is final: it becomes the newest cached row
+        y = launch(band, self._row_spec_cached, (1, ow))
+        if ctx.commit and k > 0:
             band[:, :, :k, :].copy_(band[:, :, 1:, :].clone())
         return y
+
+    def _row_forward(self, ctx, x, crop, in_act, res, out_act):
+        """x is row `ctx.row` of this convolution's input: evaluates the same row of the output (_row_step)."""
+        if self._down2:
+            raise ValueError("row decode: strided convolutions are not row-causal")
+        if x.shape[2] != 1:
+            raise ValueError("row decode expects one image row")
+
+        def launch(band, row_spec, out_hw):
+            y = ops.conv2d_taps(band, self.weight, self.bias, row_spec, out_hw=out_hw, in_act=_ACTS[in_act],
+                                res=None if out_act is not None else res)
+            if out_act is not None:  # (one row: the unfused epilogue is three tiny launches)
+                y = ops._Act.apply(y, _ACTS[out_act])
+                if res is not None:
+                    y = ops.add(y, res)
+            return y
+
+        return self._row_step(ctx, x, crop, "_row_band", 0.0, launch)
 
     # ---- code-index input (ops.code_conv2d) ---------------------------------------------------------
     def _check_n_codes(self, n_codes):
@@ -125,28 +143,10 @@ class Conv2d(nn.Conv2d):
     def _row_forward_codes(self, ctx, levels, n_codes, crop):
         """_row_forward for a row of levels: the band is (N, 1, k + 1, W), cleared to -1 (no code: rows above the image
         contribute nothing, as zero padding does); same commit rule, no host synchronisation."""
-        spec = self._conv_spec()
-        reach = [spec.pad_h - u for u, _ in spec.fwd_taps]
-        if min(reach) < 0:
-            raise ValueError("row decode: a tap below the output row (the layer is not row-causal)")
-        k = max(reach)
-        n, c, one, w = levels.shape
-        if one != 1 or c != 1:
+        if levels.shape[2] != 1 or levels.shape[1] != 1:
             raise ValueError("row decode expects one row of a level image (N, 1, 1, W)")
-        if getattr(self, "_row_spec_cached", None) is None:
-            self._row_spec_cached = ops.ConvSpec(spec.kh, spec.kw, spec.pad_h - k, spec.pad_w, active=spec.fwd_taps)
-        if k == 0:
-            band = levels
-        else:
-            if getattr(self, "_row_code_band", None) is None or self._row_code_band.shape != (n, 1, k + 1, w):
-                self._row_code_band = torch.full((n, 1, k + 1, w), -1.0, device=levels.device, dtype=levels.dtype)
-            band = self._row_code_band
-            band[:, :, k:, :].copy_(levels)
-        ow = crop[1] if crop is not None else spec.full_out(1, w)[1]
-        y = ops.code_conv2d(band, self.weight, self.bias, self._row_spec_cached, n_codes, out_hw=(1, ow))
-        if ctx.commit and k > 0:
-            band[:, :, :k, :].copy_(band[:, :, 1:, :].clone())
-        return y
+        return self._row_step(ctx, levels, crop, "_row_code_band", -1.0, lambda band, row_spec, out_hw: ops.code_conv2d(
+            band, self.weight, self.bias, row_spec, n_codes, out_hw=out_hw))
 
     def two_residuals_ok(self, x, crop=None):
         return (not self._down2) and ops.RowDecode.current is None and ops.conv_two_residuals_ok(

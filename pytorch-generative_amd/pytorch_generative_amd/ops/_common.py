@@ -33,9 +33,30 @@ class RowDecode:
     `row_dev` is the row index as an int32 device scalar for the kernels that take it from the device (ops.attention_row,
     ops.row_gather): a row step that uses it instead of `row` is the same sequence of launches for every row, so it can be
     captured into a hipGraph. It is created on first request (on `device`, default the current GPU) and from then on every
-    assignment to `row` also fills it — a fill on the current stream, no host synchronisation."""
+    assignment to `row` also fills it — a fill on the current stream, no host synchronisation.
+
+    The caches belong to the layers; a sampler speaks to them through two hooks a caching module may define, called on every
+    module of a model: `_row_reset()` drops its caches (drop_caches: before and after a call, and when a capture was refused)
+    and `_row_clear()` puts them back to their start-of-image contents WITHOUT reallocating (clear_caches: after the warm-up
+    and capture passes pushed rows into buffers whose addresses the graphs now hold). A cache that is never read at rows >=
+    the current one (attention's K / V) needs no `_row_clear`."""
 
     current = None
+
+    @staticmethod
+    def _call_hook(model, hook):
+        for m in model.modules():
+            fn = getattr(m, hook, None)
+            if fn is not None:
+                fn()
+
+    @staticmethod
+    def drop_caches(model):
+        RowDecode._call_hook(model, "_row_reset")
+
+    @staticmethod
+    def clear_caches(model):
+        RowDecode._call_hook(model, "_row_clear")
 
     def __init__(self, height, device=None):
         self.height, self.commit = int(height), False

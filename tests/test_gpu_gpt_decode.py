@@ -349,6 +349,29 @@ def test_eager_fallback_equals_graph_path(dev, monkeypatch):
     assert torch.equal(out_e, out_g) and torch.equal(logits_e, logits_g)
 
 
+def test_refused_capture_still_equals_the_full_forward(dev, monkeypatch, capsys):
+    """With the graph constructor refusing (as in test_gpu_pcnnpp_sampling), the 64-channel sampler gives up after that one
+    construction and its eagerly launched steps still produce the logits of one full forward; PG_DEBUG names the fallback."""
+    model, canvas = _model(dev, 64, 2), _binary_canvas(dev)
+    with torch.no_grad():
+        full = model(canvas)
+    refused = []
+
+    class Refused:
+        def __init__(self, *a, **k):
+            refused.append(1)
+            raise RuntimeError("graph capture refused")
+
+    monkeypatch.setattr(torch.cuda, "CUDAGraph", Refused)
+    monkeypatch.setenv("PG_DEBUG", "1")
+    out, logits = model.sample(conditioned_on=canvas, return_logits=True)
+    assert refused == [1], "not exactly one graph construction was attempted"
+    assert "capture failed: RuntimeError: graph capture refused" in capsys.readouterr().out
+    assert model._sample_route == "step"
+    assert torch.equal(out, canvas)
+    _util.assert_close(logits, full.flatten(2).permute(2, 0, 1), TOL, "eager step-kernel sampler logits, 64 channels")
+
+
 def test_seeded_draws_repeat(dev):
     """Two sample(n_samples=3) calls with the same seeded CategoricalSampler generator give equal canvases."""
     k, size = 12, 9

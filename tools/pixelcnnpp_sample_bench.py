@@ -86,9 +86,7 @@ def launches_per_pixel(model, n, dev):
     canvas = torch.zeros((n, 3, H, W), device=dev)
     unknown = torch.ones((n, 3, H, W), device=dev, dtype=torch.bool)
     uniforms = torch.rand((H * W, n, k + 3), device=dev)
-    for m in model.modules():
-        if hasattr(m, "_row_reset"):
-            m._row_reset()
+    ops.RowDecode.drop_caches(model)
     with torch.no_grad(), ops.RowDecode(H) as ctx:
         for name, row in (("row_with_all_levels", 0), ("odd_row", 1)):
             ctx.row, ctx.commit = row, False
@@ -109,9 +107,7 @@ def launches_per_pixel(model, n, dev):
                 torch.Tensor.copy_, torch.Tensor.clone = real_copy, real_clone
             rec = {"library_calls": counter.calls, "aten_copies": aten[0], "launches": counter.calls + aten[0]}
             out[name] = rec
-    for m in model.modules():
-        if hasattr(m, "_row_reset"):
-            m._row_reset()
+    ops.RowDecode.drop_caches(model)
     out["graphed_host_launches_per_pixel"] = 2  # one position fill + one graph replay
     out["full_forward_note"] = ("the full-forward sampler launches the whole network (about 90 convolutions and their "
                                 "element-wise kernels) plus about two dozen ATen kernels of sample_from_mixture per pixel")

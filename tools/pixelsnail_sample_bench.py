@@ -62,14 +62,11 @@ def compare(variants, repeats):
 def full_forward_pixels(model, empty, k):
     """The loop body of sample(incremental=False) over the first k raster positions."""
     canvas = empty.clone()
-    n, c, h, w = canvas.shape
+    w = canvas.shape[3]
     with torch.no_grad():
         for p in range(k):
             row, col = divmod(p, w)
-            logits = model.forward(canvas)[:, :, row, col]
-            drawn = model._sample_fn(logits).view(n, c)
-            current = canvas[:, :, row, col]
-            canvas[:, :, row, col] = torch.where(current < 0, drawn, current)
+            model._draw_into(canvas, row, col, model.forward(canvas)[:, :, row, col])
     return canvas
 
 
@@ -115,31 +112,27 @@ def sample_row(model, what, n, shape, repeats, k):
 
 def row_step_replay(model, n, shape, replays=100):
     """The captured row step (evaluate, no commit) at the last row over full caches: microseconds per replay."""
+    from pytorch_generative_amd import graph as pg_graph
     from pytorch_generative_amd import ops
 
     c, h, w = shape
     dev = next(model.parameters()).device
-    for m in model.modules():
-        if hasattr(m, "_row_reset"):
-            m._row_reset()
+    ops.RowDecode.drop_caches(model)
     row_in = torch.bernoulli(torch.full((n, c, 1, w), 0.5, device=dev))
     with torch.no_grad(), ops.RowDecode(h) as ctx:
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
+        def warm():
             ctx.commit = True  # allocates every band and cache
             model.forward(row_in)
             ctx.commit = False
             model.forward(row_in)
-        torch.cuda.current_stream().wait_stream(side)
+
+        pg_graph.warm_up(warm)
         for m in model.modules():  # full caches: what the last row of an image sees
             for name in ("_row_k", "_row_v"):
                 if getattr(m, name, None) is not None:
                     getattr(m, name).normal_()
         ctx.row = h - 1
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            model.forward(row_in)
+        graph, _ = pg_graph.capture(lambda: model.forward(row_in))
         for _ in range(10):
             graph.replay()
         torch.cuda.synchronize()
@@ -152,9 +145,7 @@ def row_step_replay(model, n, shape, replays=100):
             b.record()
             torch.cuda.synchronize()
             per.append(a.elapsed_time(b) * 1e3 / replays)
-    for m in model.modules():
-        if hasattr(m, "_row_reset"):
-            m._row_reset()
+    ops.RowDecode.drop_caches(model)
     return {"us_median_of_5": statistics.median(per), "us_min_max": [min(per), max(per)], "replays_per_timing": replays,
             "row": h - 1}
 
