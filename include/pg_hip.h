@@ -531,6 +531,19 @@ int pg_gpt_block_tail_bwd_partial(const float* o, const float* x, const float* w
 int pg_gpt_block_head_bwd_partial(const float* x, const float* ln_w, const float* ln_b, const float* wq, const float* wkv,
                                   const float* dqkv, const float* gx, float* dx, int N, int C, int L, float eps,
                                   float* workspace, size_t workspace_floats, void* stream);
+/* A block boundary of the backward pass in ONE launch: pg_gpt_block_head_bwd_partial of block i+1 (next_*: its x, parameters,
+ * dqkv and gx) and pg_gpt_block_tail_bwd_partial of block i (the rest) on the head's dx tile while it is still in registers; dx
+ * itself, the tail's dx_new, is not written anywhere. d_o and gx hold the same bits as after the two launches. head_workspace and
+ * tail_workspace (pg_gpt_block_head_bwd_workspace_floats / pg_gpt_block_tail_bwd_workspace_floats floats) receive the partial rows
+ * of block i+1's head job and block i's tail job for pg_gpt_model_reduce: one row per workgroup of this launch and zeros in the
+ * rest, so the parameter gradients equal those of the two launches up to the order of the sums. eps is used by both LayerNorms. */
+int pg_gpt_block_head_tail_bwd_partial(const float* next_x, const float* next_ln_w, const float* next_ln_b,
+                                       const float* next_wq, const float* next_wkv, const float* next_dqkv,
+                                       const float* next_gx, const float* o, const float* x, const float* wp, const float* bp,
+                                       const float* ln_w, const float* ln_b, const float* w1, const float* b1, const float* w2,
+                                       float* d_o, float* gx, int N, int C, int Hd, int L, float eps, float* head_workspace,
+                                       size_t head_workspace_floats, float* tail_workspace, size_t tail_workspace_floats,
+                                       void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * Incremental autoregressive sampling (models/base.py:97-120 runs H*W full forwards; the causal

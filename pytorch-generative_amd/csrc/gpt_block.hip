@@ -1,6 +1,7 @@
 // gpt_block.hip — everything of an ImageGPT transformer block that is not the attention core, as two
 // forward and two backward kernels working on 16-pixel tiles held in registers, a fifth that runs
-// a block's tail and the next block's head forward in one launch, and the model's one segmented-reduce
+// a block's tail and the next block's head forward in one launch, a sixth that runs the next block's head and the block's tail
+// backward in one launch, and the model's one segmented-reduce
 // kernel, which adds the rows of partial weight-gradient sums that the backward kernels here and in
 // gpt_ends.hip leave.
 //
@@ -41,7 +42,8 @@ constexpr int GB_THREADS = 256;  // 4 waves
 constexpr int TS = 20;           // LDS row stride (floats) of a transposed [channel][16 px] tile
 constexpr float INV_C = 1.f / 16.f;
 
-constexpr int TB_WAVE_ROWS = 2 * HD + 4 * C;  // tail_bwd's per-wave LDS tiles: G, dH [64] + LN2, dx_mid, D, o [16] rows of TS
+constexpr int TB_WAVE_ROWS = 6 * C;  // the tail backward chain's per-wave LDS tiles: G, dH of one hidden chunk, LN2, dx_mid, D, o; 16 rows of TS each
+constexpr int TB_FRAGS = 64;         // its per-lane operands kept in LDS: w1f, w2t, w1t, b1r [4][4]
 // partial-row layouts (floats)
 constexpr int T_W1 = 0, T_B1 = T_W1 + HD * C, T_W2 = T_B1 + HD, T_B2 = T_W2 + C * HD, T_WP = T_B2 + C,
               T_BP = T_WP + C * C, T_G2 = T_BP + C, T_BE2 = T_G2 + C, T_PART = T_BE2 + C;          // 2432
@@ -57,6 +59,9 @@ struct BlockArgs {
   const float* w1; const float* b1; const float* w2; const float* b2;
   float* xnew; const float* dxnew; float* d_o; float* gx_out;
   float* part;
+  // head(i+1) + tail(i) backward: x of the tail's block (x is the head's), the tail's partial rows (part is the head's) and the
+  // rows that the two reduce jobs count
+  const float* tx; float* tpart; int head_rows, tail_rows;
   int N, L, tiles_per_img, total_tiles;
   float eps;
 };
@@ -214,8 +219,131 @@ __global__ void __launch_bounds__(GB_THREADS) head_fwd_kernel(const BlockArgs a)
 
 // ---------------------------------------------------------------------------------- head, backward
 // dx = LN1'(W^T dqkv) + gx ; dW += dqkv^T LN1(x) ; db += sum dqkv ; dgamma1, dbeta1
+constexpr int HB_WAVE_ROWS = C + QKV;  // head backward's per-wave LDS tiles: LN1(x)^T [16] + dqkv^T [48] rows of TS
+constexpr int HB_FRAGS = 20;           // per-lane operands of the head's backward chain: wt[3][4], gamma1[4], beta1[4]
+
+__device__ __forceinline__ float sum4(const f32x4& v) { return (v[0] + v[1]) + (v[2] + v[3]); }
+
+// The sums a wave keeps over all of its tiles. accb[m] belongs to channel 16m+j and holds the pixels 4g..4g+3 of every tile: it is
+// summed from the transposed row that the weight-gradient MFMAs read anyway, one register per 16 channels where a D-layout sum
+// takes four; the final cross-lane sum runs over the lane groups g.
+struct HeadBwdAcc {
+  f32x4 accw[3], dgam, dbet;
+  float accb[3];
+  __device__ __forceinline__ HeadBwdAcc() {
+    const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+    dgam = zero4; dbet = zero4;
+#pragma unroll
+    for (int m = 0; m < 3; ++m) { accw[m] = zero4; accb[m] = 0.f; }
+  }
+};
+// The chain's per-lane operands, wt(m, r) = A[i = in channel j][k = g <-> out channel 16m+4g+r] and LN1's affine in D layout:
+// in registers (head_bwd_kernel) or in the workgroup's [fragment][lane] LDS copy (head_tail_bwd_kernel)
+struct HeadBwdRegs {
+  float w[3][4]; f32x4 gamv, betv;
+  __device__ __forceinline__ HeadBwdRegs(const BlockArgs& a, int j, int g) {
+#pragma unroll
+    for (int m = 0; m < 3; ++m) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) w[m][r] = qkv_row(a, 16 * m + 4 * g + r)[j];
+    }
+    gamv = load_vec(a.g1, g);
+    betv = load_vec(a.be1, g);
+  }
+  __device__ __forceinline__ float wt(int m, int r) const { return w[m][r]; }
+  __device__ __forceinline__ float gam(int r) const { return gamv[r]; }
+  __device__ __forceinline__ float bet(int r) const { return betv[r]; }
+};
+struct HeadBwdLds {
+  const float* wlane;  // [HB_FRAGS fragments][64 lanes] + lane
+  static __device__ __forceinline__ void fill(float* wl, const BlockArgs& a, int lane, int j, int g) {
+#pragma unroll
+    for (int m = 0; m < 3; ++m) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) wl[(4 * m + r) * 64 + lane] = qkv_row(a, 16 * m + 4 * g + r)[j];
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      wl[(12 + r) * 64 + lane] = a.g1[4 * g + r];
+      wl[(16 + r) * 64 + lane] = a.be1[4 * g + r];
+    }
+  }
+  __device__ __forceinline__ float wt(int m, int r) const { return wlane[(4 * m + r) * 64]; }
+  __device__ __forceinline__ float gam(int r) const { return wlane[(12 + r) * 64]; }
+  __device__ __forceinline__ float bet(int r) const { return wlane[(16 + r) * 64]; }
+};
+// head backward chain of one tile; returns dx. ty [16][TS] and tq [48][TS] are the wave's LDS tiles. The ONE copy of this
+// arithmetic: head_bwd_kernel stores the dx tile, head_tail_bwd_kernel hands it to the previous block's tail chain as D.
+template <class Ops>
+__device__ __forceinline__ f32x4 head_bwd_chain(const f32x4& xv, const f32x4& gxv, const f32x4 (&dqv)[3], const Ops& f, float eps,
+                                                float* ty, float* tq, int j, int g, HeadBwdAcc& acc) {
+  // Every fused multiply-add of this chain is written out: left to itself the compiler contracts a product that has several uses
+  // (gy) differently from one kernel to the next (scalar or packed, operands from registers or LDS), and dx would differ in
+  // its last bit between head_bwd_kernel and head_tail_bwd_kernel. The forms below are the ones head_bwd_kernel was compiled to
+  // before it shared this function (s1 and, except for element 0, gy - m1 take the unrounded product), so dx keeps its bits.
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int m = 0; m < 3; ++m) lds_put_tile(tq + 16 * m * TS, j, g, dqv[m]);
+  const Ln s = ln_stats(xv, eps);
+  f32x4 dy = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int m = 0; m < 3; ++m) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) dy = MFMA16(f.wt(m, r), dqv[m][r], dy);
+  }
+  // LayerNorm backward (dy is the gradient of y = xhat * gamma + beta)
+  f32x4 gy;
+  float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    gy[r] = dy[r] * f.gam(r);
+    s1 = fmaf(dy[r], f.gam(r), s1);
+    s2 = fmaf(gy[r], s.xhat[r], s2);
+    acc.dgam[r] = fmaf(dy[r], s.xhat[r], acc.dgam[r]);
+    acc.dbet[r] += dy[r];
+    ty[(4 * g + r) * TS + j] = fmaf(s.xhat[r], f.gam(r), f.bet(r));
+  }
+  const float m1 = gsum4(s1) * INV_C, m2 = gsum4(s2) * INV_C;
+  f32x4 dxv;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const float c = r == 0 ? gy[0] - m1 : fmaf(dy[r], f.gam(r), -m1);  // element 0 from the rounded product: as compiled before
+    dxv[r] = fmaf(s.rs, fmaf(-s.xhat[r], m2, c), gxv[r]);
+  }
+  // dW[ch][c] += sum_px dqkv[px][ch] y[px][c]
+  const f32x4 yt = lds_row4(ty, j, g);  // B[k = px 4g+e][c = j]
+#pragma unroll
+  for (int m = 0; m < 3; ++m) {
+    const f32x4 dqtm = lds_row4(tq, 16 * m + j, g);  // A[i = ch 16m+j][k = px 4g+e]
+    acc.accb[m] += sum4(dqtm);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) acc.accw[m] = MFMA16(dqtm[e], yt[e], acc.accw[m]);
+  }
+  return dxv;
+}
+// a wave's sums -> its H_PART floats of LDS staging
+__device__ __forceinline__ void head_bwd_stage(float* mine, const HeadBwdAcc& acc, int j, int g) {
+#pragma unroll
+  for (int m = 0; m < 3; ++m) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) mine[H_WQ + (16 * m + 4 * g + r) * C + j] = acc.accw[m][r];  // rows 0..15 = W_q, 16..47 = W_kv
+    const float b = gsum4(acc.accb[m]);
+    if (g == 0) mine[H_BQ + 16 * m + j] = b;
+  }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const float dg = jsum16(acc.dgam[r]), db = jsum16(acc.dbet[r]);
+    if (j == 0) { mine[H_G1 + 4 * g + r] = dg; mine[H_BE1 + 4 * g + r] = db; }
+  }
+}
+// the four waves' staged rows of n floats each, at the start of lds -> the workgroup's partial row
+__device__ __forceinline__ void write_partial_row(float* __restrict__ prow, const float* lds, int n) {
+  for (int i = threadIdx.x; i < n; i += GB_THREADS)
+    prow[i] = (lds[i] + lds[n + i]) + (lds[2 * n + i] + lds[3 * n + i]);
+}
+
 // only x and gx of the next tile are prefetched (8 registers): with d qkv prefetched as well (12 more) the kernel leaves the
-// four-waves-per-SIMD budget (143 registers) unless the allocator is forced, and measured within run-to-run spread of this form
+// four-waves-per-SIMD budget unless the allocator is forced, and measured within run-to-run spread of this form
 __global__ void __launch_bounds__(GB_THREADS) head_bwd_kernel(const BlockArgs a) {
   extern __shared__ float4 lds4[];
   float* lds = reinterpret_cast<float*>(lds4);
@@ -223,20 +351,10 @@ __global__ void __launch_bounds__(GB_THREADS) head_bwd_kernel(const BlockArgs a)
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int wave = blockIdx.x * (GB_THREADS / 64) + wv;
   const int nwaves = gridDim.x * (GB_THREADS / 64);
-  float* ty = lds + (size_t)wv * (C + QKV) * TS;  // LN1(x)^T [16 c][TS]
-  float* tq = ty + C * TS;                         // dqkv^T   [48 ch][TS]
-
-  float wt[3][4];  // A[i = in channel j][k = g <-> out channel 16m+4g+r]
-#pragma unroll
-  for (int m = 0; m < 3; ++m) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) wt[m][r] = qkv_row(a, 16 * m + 4 * g + r)[j];
-  }
-  const f32x4 gam = load_vec(a.g1, g), bet = load_vec(a.be1, g);
-  const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-  f32x4 accw[3], accb[3], dgam = zero4, dbet = zero4;
-#pragma unroll
-  for (int m = 0; m < 3; ++m) { accw[m] = zero4; accb[m] = zero4; }
+  float* ty = lds + (size_t)wv * HB_WAVE_ROWS * TS;  // LN1(x)^T [16 c][TS]
+  float* tq = ty + C * TS;                           // dqkv^T   [48 ch][TS]
+  const HeadBwdRegs hf(a, j, g);
+  HeadBwdAcc acc;
 
   if (wave < a.total_tiles) {  // a wave without a tile loads nothing
     TileWalk tw(a, wave, nwaves);
@@ -259,43 +377,7 @@ __global__ void __launch_bounds__(GB_THREADS) head_bwd_kernel(const BlockArgs a)
       const f32x4 xn = load_tile(a.x + offn, a.L, g);
       const f32x4 gxn = load_tile(a.gx + offn, a.L, g);
       prefetch_fence();
-#pragma unroll
-      for (int m = 0; m < 3; ++m) lds_put_tile(tq + 16 * m * TS, j, g, dqv[m]);
-      const Ln s = ln_stats(xv, a.eps);
-      f32x4 dy = zero4;
-#pragma unroll
-      for (int m = 0; m < 3; ++m) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          dy = MFMA16(wt[m][r], dqv[m][r], dy);
-          accb[m][r] += dqv[m][r];
-        }
-      }
-      // LayerNorm backward (dy is the gradient of y = xhat * gamma + beta)
-      f32x4 gy;
-      float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        gy[r] = dy[r] * gam[r];
-        s1 += gy[r];
-        s2 = fmaf(gy[r], s.xhat[r], s2);
-        dgam[r] = fmaf(dy[r], s.xhat[r], dgam[r]);
-        dbet[r] += dy[r];
-        ty[(4 * g + r) * TS + j] = fmaf(s.xhat[r], gam[r], bet[r]);
-      }
-      const float m1 = gsum4(s1) * INV_C, m2 = gsum4(s2) * INV_C;
-      f32x4 dxv;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) dxv[r] = s.rs * (gy[r] - m1 - s.xhat[r] * m2) + gxv[r];
-      store_tile(a.dx + off, a.L, g, dxv);
-      // dW[ch][c] += sum_px dqkv[px][ch] y[px][c]
-      const f32x4 yt = lds_row4(ty, j, g);  // B[k = px 4g+e][c = j]
-#pragma unroll
-      for (int m = 0; m < 3; ++m) {
-        const f32x4 dqtm = lds_row4(tq, 16 * m + j, g);  // A[i = ch 16m+j][k = px 4g+e]
-#pragma unroll
-        for (int e = 0; e < 4; ++e) accw[m] = MFMA16(dqtm[e], yt[e], accw[m]);
-      }
+      store_tile(a.dx + off, a.L, g, head_bwd_chain(xv, gxv, dqv, hf, a.eps, ty, tq, j, g, acc));
       if (!more) break;
       xv = xn;
       gxv = gxn;
@@ -305,26 +387,9 @@ __global__ void __launch_bounds__(GB_THREADS) head_bwd_kernel(const BlockArgs a)
   }
 
   __syncthreads();
-  float* mine = lds + (size_t)wv * H_PART;
-#pragma unroll
-  for (int m = 0; m < 3; ++m) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int ch = 16 * m + 4 * g + r;
-      mine[H_WQ + ch * C + j] = accw[m][r];  // rows 0..15 = W_q, 16..47 = W_kv: contiguous in the row
-      const float b = jsum16(accb[m][r]);
-      if (j == 0) mine[H_BQ + ch] = b;
-    }
-  }
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const float dg = jsum16(dgam[r]), db = jsum16(dbet[r]);
-    if (j == 0) { mine[H_G1 + 4 * g + r] = dg; mine[H_BE1 + 4 * g + r] = db; }
-  }
+  head_bwd_stage(lds + (size_t)wv * H_PART, acc, j, g);
   __syncthreads();
-  float* prow = a.part + (size_t)blockIdx.x * H_PART;
-  for (int i = threadIdx.x; i < H_PART; i += GB_THREADS)
-    prow[i] = (lds[i] + lds[H_PART + i]) + (lds[2 * H_PART + i] + lds[3 * H_PART + i]);
+  write_partial_row(a.part + (size_t)blockIdx.x * H_PART, lds, H_PART);
 }
 
 // ---------------------------------------------------------------------------------- tail, forward
@@ -450,29 +515,31 @@ __global__ void __launch_bounds__(GB_THREADS, 3) tail_head_fwd_kernel(const Bloc
 // ---------------------------------------------------------------------------------- tail, backward
 // D = d x_new. Outputs d_o = W_p^T d x_mid and gx = D + d x_mid (everything that reaches the block
 // input x except through LN1), plus the gradients of W_p, b_p, LN2, fc1, fc2.
-__global__ void __launch_bounds__(GB_THREADS) tail_bwd_kernel(const BlockArgs a) {
-  extern __shared__ float4 lds4[];
-  float* lds = reinterpret_cast<float*>(lds4);
-  const int lane = threadIdx.x & 63, j = lane & 15, g = lane >> 4;
-  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int wave = blockIdx.x * (GB_THREADS / 64) + wv;
-  const int nwaves = gridDim.x * (GB_THREADS / 64);
-  float* tg = lds + (size_t)wv * TB_WAVE_ROWS * TS;       // G^T     [64][TS]
-  float* th = tg + HD * TS;                              // dH^T    [64][TS]
-  float* ty = th + HD * TS;                              // LN2^T   [16][TS]
-  float* tx = ty + C * TS;                               // dx_mid^T[16][TS]
-  float* td = tx + C * TS;                               // D^T     [16][TS]
-  float* to = td + C * TS;                               // o^T     [16][TS]
-
-  // Weight fragments depend on the lane only, not on the wave or the tile: the workgroup keeps ONE
-  // copy in LDS ([fragment][lane], conflict-free ds_read_b32) instead of 64 VGPRs per lane — with
-  // them in registers the kernel needs 316 registers (one wave per SIMD, measured 196 us per launch).
-  //   w1f[m][r] = W1[16m+j][4g+r]      A[i = hidden 16m+j][k <-> c 4g+r]       (H recompute)
-  //   w2t[m][r] = W2[4g+r][16m+j]      A[i = hidden 16m+j][k <-> co 4g+r]      (dG = W_2^T D)
-  //   w1t[m][r] = W1[16m+4g+r][j]      A[i = c j][k <-> hidden 16m+4g+r]       (dY = W_1^T dH)
-  //   b1r[m][r] = b1[16m+4g+r]
-  float* wl = lds + (size_t)4 * TB_WAVE_ROWS * TS;  // [64 fragments][64 lanes]
-  if (wv == 0) {
+// The sums a wave keeps over all of its tiles. The bias sums db1[m] (hidden 16m+j), db2 and dbp (channel j) hold the pixels
+// 4g..4g+3 of every tile, from the transposed rows that feed the weight-gradient MFMAs (as HeadBwdAcc::accb).
+struct TailBwdAcc {
+  f32x4 acc1[4], acc2[4], accp, dgam, dbet;
+  float db1[4], db2, dbp;
+  __device__ __forceinline__ TailBwdAcc() {
+    const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+    accp = zero4; dgam = zero4; dbet = zero4; db2 = 0.f; dbp = 0.f;
+#pragma unroll
+    for (int m = 0; m < 4; ++m) { acc1[m] = zero4; acc2[m] = zero4; db1[m] = 0.f; }
+  }
+};
+// Weight fragments depend on the lane only, not on the wave or the tile: the workgroup keeps ONE
+// copy in LDS ([fragment][lane], conflict-free ds_read_b32) instead of 64 VGPRs per lane — with
+// them in registers the kernel needs 316 registers (one wave per SIMD, measured 196 us per launch).
+//   w1f(m, r) = W1[16m+j][4g+r]      A[i = hidden 16m+j][k <-> c 4g+r]       (H recompute)
+//   w2t(m, r) = W2[4g+r][16m+j]      A[i = hidden 16m+j][k <-> co 4g+r]      (dG = W_2^T D)
+//   w1t(m, r) = W1[16m+4g+r][j]      A[i = c j][k <-> hidden 16m+4g+r]       (dY = W_1^T dH)
+//   b1r(m, r) = b1[16m+4g+r]
+// The projection's two fragments and the per-channel vectors stay in registers.
+struct TailBwdOps {
+  const float* wlane;  // [TB_FRAGS fragments][64 lanes] + lane
+  float wpf[4], wpt[4];
+  f32x4 bpv, gam, bet;
+  static __device__ __forceinline__ void fill(float* wl, const BlockArgs& a, int lane, int j, int g) {
 #pragma unroll
     for (int m = 0; m < 4; ++m) {
 #pragma unroll
@@ -484,24 +551,149 @@ __global__ void __launch_bounds__(GB_THREADS) tail_bwd_kernel(const BlockArgs a)
       }
     }
   }
-  __syncthreads();
-  const float* wlane = wl + lane;
-#define W1F(m, r) wlane[(0 + 4 * (m) + (r)) * 64]
-#define W2T(m, r) wlane[(16 + 4 * (m) + (r)) * 64]
-#define W1T(m, r) wlane[(32 + 4 * (m) + (r)) * 64]
-#define B1R(m, r) wlane[(48 + 4 * (m) + (r)) * 64]
-  float wpf[4], wpt[4];
+  __device__ __forceinline__ TailBwdOps(const float* wl, const BlockArgs& a, int lane, int j, int g) : wlane(wl + lane) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      wpf[r] = a.wp[j * C + 4 * g + r];    // A[i = co j][k <-> ci 4g+r]      (x_mid recompute)
+      wpt[r] = a.wp[(4 * g + r) * C + j];  // A[i = ci j][k <-> co 4g+r]      (d_o = W_p^T d x_mid)
+    }
+    bpv = load_vec(a.bp, g);
+    gam = load_vec(a.g2, g);
+    bet = load_vec(a.be2, g);
+  }
+  __device__ __forceinline__ float w1f(int m, int r) const { return wlane[(0 + 4 * m + r) * 64]; }
+  __device__ __forceinline__ float w2t(int m, int r) const { return wlane[(16 + 4 * m + r) * 64]; }
+  __device__ __forceinline__ float w1t(int m, int r) const { return wlane[(32 + 4 * m + r) * 64]; }
+  __device__ __forceinline__ float b1r(int m, int r) const { return wlane[(48 + 4 * m + r) * 64]; }
+};
+// tail backward chain of one tile: x, o, D = d x_new in, d_o and gx out. tiles: the wave's TB_WAVE_ROWS rows of LDS. The ONE copy of
+// this arithmetic, shared by tail_bwd_kernel (D loaded) and head_tail_bwd_kernel (D = the dx tile of the next block's head chain).
+// The 64 hidden channels go through in four chunks of 16: h, dG, GELU, GELU', the chunk's share of dY and its dW1 / dW2 MFMAs, then
+// the next chunk into the same 16-row G / dH tiles. A wave's LDS operations execute in order, so the rewrite needs no barrier (the
+// fused attention backward relies on the same). dY accumulates over (m, r) ascending in either form.
+__device__ __forceinline__ void tail_bwd_chain(const f32x4& xv, const f32x4& ov, const f32x4& dv, const TailBwdOps& f, float eps,
+                                               float* tiles, int j, int g, TailBwdAcc& acc, f32x4& dov, f32x4& gxv) {
+  // as head_bwd_chain: every fused multiply-add is written out, in the forms tail_bwd_kernel was compiled to before it shared this
+  // function (here s1 sums the rounded products gy and only gy - m1 takes the unrounded one)
+#pragma clang fp contract(off)
+  float* tg = tiles;        // G^T      [16][TS], one hidden chunk
+  float* th = tg + C * TS;  // dH^T     [16][TS], one hidden chunk
+  float* ty = th + C * TS;  // LN2^T    [16][TS]
+  float* tx = ty + C * TS;  // dx_mid^T [16][TS]
+  float* td = tx + C * TS;  // D^T      [16][TS]
+  float* to = td + C * TS;  // o^T      [16][TS]
+  const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+  lds_put_tile(td, j, g, dv);
+  lds_put_tile(to, j, g, ov);
+
+  // ---- recompute the forward: x_mid, LN2
+  f32x4 xm = xv + f.bpv;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) xm = MFMA16(f.wpf[r], ov[r], xm);
+  const Ln s = ln_stats(xm, eps);
+  f32x4 y;
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
-    wpf[r] = a.wp[j * C + 4 * g + r];    // A[i = co j][k <-> ci 4g+r]      (x_mid recompute)
-    wpt[r] = a.wp[(4 * g + r) * C + j];  // A[i = ci j][k <-> co 4g+r]      (d_o = W_p^T d x_mid)
+    y[r] = fmaf(s.xhat[r], f.gam[r], f.bet[r]);
+    ty[(4 * g + r) * TS + j] = y[r];
   }
-  const f32x4 bpv = load_vec(a.bp, g);
-  const f32x4 gam = load_vec(a.g2, g), bet = load_vec(a.be2, g);
-  const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-  f32x4 acc1[4], acc2[4], db1[4], accp = zero4, db2 = zero4, dbp = zero4, dgam = zero4, dbet = zero4;
+  // the contraction over the tile's pixels takes pixel 4g+e in K-step e
+  const f32x4 yt = lds_row4(ty, j, g);   // B[k = px][c = j]
+  const f32x4 dvt = lds_row4(td, j, g);  // A[i = co j][k = px]
+  acc.db2 += sum4(dvt);
+  // ---- per hidden chunk: H, dG = W_2^T D; G, dH = dG * gelu'(H); dY += W_1^T dH; dW2 += D^T G, dW1 += dH^T y
+  f32x4 dy = zero4;
 #pragma unroll
-  for (int m = 0; m < 4; ++m) { acc1[m] = zero4; acc2[m] = zero4; db1[m] = zero4; }
+  for (int m = 0; m < 4; ++m) {
+    f32x4 h = {f.b1r(m, 0), f.b1r(m, 1), f.b1r(m, 2), f.b1r(m, 3)}, dg = zero4;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      h = MFMA16(f.w1f(m, r), y[r], h);
+      dg = MFMA16(f.w2t(m, r), dv[r], dg);
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const float hv = h[r];
+      float cdf, ee;
+      pg_gelu_parts(hv, cdf, ee);
+      const float pdf = 0.39894228040143267794f * ee;
+      const float dh = dg[r] * fmaf(hv, pdf, cdf);
+      tg[(4 * g + r) * TS + j] = hv * cdf;
+      th[(4 * g + r) * TS + j] = dh;
+      dy = MFMA16(f.w1t(m, r), dh, dy);
+    }
+    const f32x4 gt = lds_row4(tg, j, g);  // B[k = px][hidden 16m+j]
+    const f32x4 ht = lds_row4(th, j, g);  // A[i = hidden 16m+j][k = px]
+    acc.db1[m] += sum4(ht);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      acc.acc2[m] = MFMA16(dvt[e], gt[e], acc.acc2[m]);  // dW2[co][hidden] += D[px][co] G[px][hidden]
+      acc.acc1[m] = MFMA16(ht[e], yt[e], acc.acc1[m]);   // dW1[hidden][c]  += dH[px][hidden] y[px][c]
+    }
+  }
+  // ---- LN2 backward, d x_mid = D + LN2'(dY)
+  f32x4 gy, dxm;
+  float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    gy[r] = dy[r] * f.gam[r];
+    s1 += gy[r];
+    s2 = fmaf(gy[r], s.xhat[r], s2);
+    acc.dgam[r] = fmaf(dy[r], s.xhat[r], acc.dgam[r]);
+    acc.dbet[r] += dy[r];
+  }
+  const float m1 = gsum4(s1) * INV_C, m2 = gsum4(s2) * INV_C;
+  dov = zero4;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    dxm[r] = fmaf(s.rs, fmaf(-s.xhat[r], m2, fmaf(dy[r], f.gam[r], -m1)), dv[r]);
+    tx[(4 * g + r) * TS + j] = dxm[r];
+    gxv[r] = dv[r] + dxm[r];
+  }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) dov = MFMA16(f.wpt[r], dxm[r], dov);
+  // ---- dWp[co][ci] += dx_mid[px][co] o[px][ci]
+  const f32x4 xt = lds_row4(tx, j, g);  // A[i = co j][k = px]
+  const f32x4 ot = lds_row4(to, j, g);  // B[k = px][ci = j]
+  acc.dbp += sum4(xt);
+#pragma unroll
+  for (int e = 0; e < 4; ++e) acc.accp = MFMA16(xt[e], ot[e], acc.accp);
+}
+// a wave's sums -> its T_PART floats of LDS staging
+__device__ __forceinline__ void tail_bwd_stage(float* mine, const TailBwdAcc& acc, int j, int g) {
+#pragma unroll
+  for (int m = 0; m < 4; ++m) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      mine[T_W1 + (16 * m + 4 * g + r) * C + j] = acc.acc1[m][r];    // D: lane c = j, rows hidden 16m+4g+r
+      mine[T_W2 + (4 * g + r) * HD + 16 * m + j] = acc.acc2[m][r];   // D: lane hidden 16m+j, rows co 4g+r
+    }
+    const float v = gsum4(acc.db1[m]);
+    if (g == 0) mine[T_B1 + 16 * m + j] = v;
+  }
+  const float v2 = gsum4(acc.db2), vp = gsum4(acc.dbp);
+  if (g == 0) { mine[T_B2 + j] = v2; mine[T_BP + j] = vp; }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    mine[T_WP + (4 * g + r) * C + j] = acc.accp[r];                  // D: lane ci = j, rows co 4g+r
+    const float vg = jsum16(acc.dgam[r]), vb = jsum16(acc.dbet[r]);
+    if (j == 0) { mine[T_G2 + 4 * g + r] = vg; mine[T_BE2 + 4 * g + r] = vb; }
+  }
+}
+
+__global__ void __launch_bounds__(GB_THREADS) tail_bwd_kernel(const BlockArgs a) {
+  extern __shared__ float4 lds4[];
+  float* lds = reinterpret_cast<float*>(lds4);
+  const int lane = threadIdx.x & 63, j = lane & 15, g = lane >> 4;
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int wave = blockIdx.x * (GB_THREADS / 64) + wv;
+  const int nwaves = gridDim.x * (GB_THREADS / 64);
+  float* tiles = lds + (size_t)wv * TB_WAVE_ROWS * TS;
+  float* wl = lds + (size_t)4 * TB_WAVE_ROWS * TS;  // [TB_FRAGS fragments][64 lanes]
+  if (wv == 0) TailBwdOps::fill(wl, a, lane, j, g);
+  __syncthreads();
+  const TailBwdOps tf(wl, a, lane, j, g);
+  TailBwdAcc acc;
 
   if (wave < a.total_tiles) {  // a wave without a tile loads nothing
     TileWalk tw(a, wave, nwaves);
@@ -519,92 +711,10 @@ __global__ void __launch_bounds__(GB_THREADS) tail_bwd_kernel(const BlockArgs a)
       const f32x4 on = load_tile(a.o + offn, a.L, g);
       const f32x4 dn = load_tile(a.dxnew + offn, a.L, g);
       prefetch_fence();
-      lds_put_tile(td, j, g, dv);
-      lds_put_tile(to, j, g, ov);
-
-      // ---- recompute the forward: x_mid, LN2, hidden
-      f32x4 xm = xv + bpv;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) xm = MFMA16(wpf[r], ov[r], xm);
-      const Ln s = ln_stats(xm, a.eps);
-      f32x4 y;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        y[r] = fmaf(s.xhat[r], gam[r], bet[r]);
-        ty[(4 * g + r) * TS + j] = y[r];
-        db2[r] += dv[r];
-      }
-      f32x4 h[4], dg[4];
-#pragma unroll
-      for (int m = 0; m < 4; ++m) {
-        h[m] = f32x4{B1R(m, 0), B1R(m, 1), B1R(m, 2), B1R(m, 3)};
-        dg[m] = zero4;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          h[m] = MFMA16(W1F(m, r), y[r], h[m]);
-          dg[m] = MFMA16(W2T(m, r), dv[r], dg[m]);
-        }
-      }
-      // ---- G, dH = dG * gelu'(H); dY = W_1^T dH
-      f32x4 dy = zero4;
-#pragma unroll
-      for (int m = 0; m < 4; ++m) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float hv = h[m][r];
-          float cdf, ee;
-          pg_gelu_parts(hv, cdf, ee);
-          const float pdf = 0.39894228040143267794f * ee;
-          const float dh = dg[m][r] * (cdf + hv * pdf);
-          const int hid = 16 * m + 4 * g + r;
-          tg[hid * TS + j] = hv * cdf;
-          th[hid * TS + j] = dh;
-          db1[m][r] += dh;
-          dy = MFMA16(W1T(m, r), dh, dy);
-        }
-      }
-      // ---- LN2 backward, d x_mid = D + LN2'(dY)
-      f32x4 gy, dxm;
-      float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        gy[r] = dy[r] * gam[r];
-        s1 += gy[r];
-        s2 = fmaf(gy[r], s.xhat[r], s2);
-        dgam[r] = fmaf(dy[r], s.xhat[r], dgam[r]);
-        dbet[r] += dy[r];
-      }
-      const float m1 = gsum4(s1) * INV_C, m2 = gsum4(s2) * INV_C;
-      f32x4 dov = zero4, gxv;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        dxm[r] = dv[r] + s.rs * (gy[r] - m1 - s.xhat[r] * m2);
-        tx[(4 * g + r) * TS + j] = dxm[r];
-        dbp[r] += dxm[r];
-        gxv[r] = dv[r] + dxm[r];
-      }
-#pragma unroll
-      for (int r = 0; r < 4; ++r) dov = MFMA16(wpt[r], dxm[r], dov);
+      f32x4 dov, gxv;
+      tail_bwd_chain(xv, ov, dv, tf, a.eps, tiles, j, g, acc, dov, gxv);
       store_tile(a.d_o + off, a.L, g, dov);
       store_tile(a.gx_out + off, a.L, g, gxv);
-
-      // ---- weight gradients: contraction over the tile's pixels (pixel 4g+e in K-step e)
-      const f32x4 yt = lds_row4(ty, j, g);   // B[k = px][c = j]
-      const f32x4 xt = lds_row4(tx, j, g);   // A[i = co j][k = px]
-      const f32x4 dvt = lds_row4(td, j, g);  // A[i = co j][k = px]
-      const f32x4 ot = lds_row4(to, j, g);   // B[k = px][ci = j]
-#pragma unroll
-      for (int e = 0; e < 4; ++e) accp = MFMA16(xt[e], ot[e], accp);            // dWp[co][ci]
-#pragma unroll
-      for (int m = 0; m < 4; ++m) {
-        const f32x4 gt = *reinterpret_cast<const f32x4*>(tg + (16 * m + j) * TS + 4 * g);  // B[k = px][hidden]
-        const f32x4 ht = *reinterpret_cast<const f32x4*>(th + (16 * m + j) * TS + 4 * g);  // A[hidden][k = px]
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          acc2[m] = MFMA16(dvt[e], gt[e], acc2[m]);  // dW2[co][hidden] += D[px][co] G[px][hidden]
-          acc1[m] = MFMA16(ht[e], yt[e], acc1[m]);   // dW1[hidden][c]  += dH[px][hidden] y[px][c]
-        }
-      }
       if (!more) break;
       xv = xn;
       ov = on;
@@ -614,38 +724,94 @@ __global__ void __launch_bounds__(GB_THREADS) tail_bwd_kernel(const BlockArgs a)
     }
   }
 
-#undef W1F
-#undef W2T
-#undef W1T
-#undef B1R
   // ---- one partial row per workgroup
   __syncthreads();
-  float* mine = lds + (size_t)wv * T_PART;
-#pragma unroll
-  for (int m = 0; m < 4; ++m) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      mine[T_W1 + (16 * m + 4 * g + r) * C + j] = acc1[m][r];    // D: lane c = j, rows hidden 16m+4g+r
-      mine[T_W2 + (4 * g + r) * HD + 16 * m + j] = acc2[m][r];   // D: lane hidden 16m+j, rows co 4g+r
-      const float v = jsum16(db1[m][r]);
-      if (j == 0) mine[T_B1 + 16 * m + 4 * g + r] = v;
-    }
-  }
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    mine[T_WP + (4 * g + r) * C + j] = accp[r];                  // D: lane ci = j, rows co 4g+r
-    const float v2 = jsum16(db2[r]), vp = jsum16(dbp[r]), vg = jsum16(dgam[r]), vb = jsum16(dbet[r]);
-    if (j == 0) {
-      mine[T_B2 + 4 * g + r] = v2;
-      mine[T_BP + 4 * g + r] = vp;
-      mine[T_G2 + 4 * g + r] = vg;
-      mine[T_BE2 + 4 * g + r] = vb;
-    }
-  }
+  tail_bwd_stage(lds + (size_t)wv * T_PART, acc, j, g);
   __syncthreads();
-  float* prow = a.part + (size_t)blockIdx.x * T_PART;
-  for (int i = threadIdx.x; i < T_PART; i += GB_THREADS)
-    prow[i] = (lds[i] + lds[T_PART + i]) + (lds[2 * T_PART + i] + lds[3 * T_PART + i]);
+  write_partial_row(a.part + (size_t)blockIdx.x * T_PART, lds, T_PART);
+}
+
+// ---------------------------------------------------------------------------------- head(i+1) + tail(i), backward
+// A block boundary of the backward pass in one launch: the head chain of block i+1 on x_{i+1}, gx_{i+1}, d qkv_{i+1}, then the tail
+// chain of block i on x_i, o_i with the head's dx tile as D while it is still a register tile. dx (64 B per pixel written by
+// head_bwd_kernel and read back by tail_bwd_kernel) never exists in memory, and the head's loads run under the tail's issue-bound
+// chain. Here a.x, a.gx, a.dqkv, a.part are the head's and a.tx, a.o, a.tpart the tail's. The head's operands join the tail's
+// fragments in LDS; the partial rows of the two jobs are staged in the tile space after the loop. One row per workgroup and job;
+// the reduce jobs count rows by the grids of head_bwd_kernel and tail_bwd_kernel (head_rows, tail_rows >= this grid), so the
+// workgroups leave the rows beyond this grid as zeros, which add nothing.
+__device__ __forceinline__ void zero_rows_beyond_grid(float* __restrict__ part, int stride, int rows) {
+  for (int row = blockIdx.x + gridDim.x; row < rows; row += gridDim.x)
+    for (int i = threadIdx.x; i < stride; i += GB_THREADS) part[(size_t)row * stride + i] = 0.f;
+}
+__global__ void __launch_bounds__(GB_THREADS, 2) head_tail_bwd_kernel(const BlockArgs a) {
+  extern __shared__ float4 lds4[];
+  float* lds = reinterpret_cast<float*>(lds4);
+  const int lane = threadIdx.x & 63, j = lane & 15, g = lane >> 4;
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int wave = blockIdx.x * (GB_THREADS / 64) + wv;
+  const int nwaves = gridDim.x * (GB_THREADS / 64);
+  float* tiles = lds + (size_t)wv * (TB_WAVE_ROWS + HB_WAVE_ROWS) * TS;  // the tail chain's rows, then the head chain's
+  float* ty = tiles + TB_WAVE_ROWS * TS;                                  // LN1(x)^T [16 c][TS]
+  float* tq = ty + C * TS;                                                // dqkv^T   [48 ch][TS]
+  float* wl = lds + (size_t)4 * (TB_WAVE_ROWS + HB_WAVE_ROWS) * TS;       // [TB_FRAGS + HB_FRAGS fragments][64 lanes]
+  if (wv == 0) TailBwdOps::fill(wl, a, lane, j, g);
+  if (wv == 1) HeadBwdLds::fill(wl + TB_FRAGS * 64, a, lane, j, g);
+  __syncthreads();
+  const TailBwdOps tf(wl, a, lane, j, g);
+  const HeadBwdLds hf = {wl + TB_FRAGS * 64 + lane};
+  TailBwdAcc tacc;
+  HeadBwdAcc hacc;
+
+  if (wave < a.total_tiles) {  // a wave without a tile loads nothing
+    TileWalk tw(a, wave, nwaves);
+    size_t off = tw.base(C, a.L) + j;
+    f32x4 xh = load_tile(a.x + off, a.L, g);
+    f32x4 gxh = load_tile(a.gx + off, a.L, g);
+    f32x4 xv = load_tile(a.tx + off, a.L, g);
+    f32x4 ov = load_tile(a.o + off, a.L, g);
+    wait_prologue_loads();
+    for (;;) {
+      // d qkv of the tile in hand goes first, so that waiting for it leaves the prefetch behind it in flight
+      f32x4 dqv[3];
+      {
+        const float* dqp = a.dqkv + tw.base(QKV, a.L) + j;
+#pragma unroll
+        for (int m = 0; m < 3; ++m) dqv[m] = load_tile(dqp + (size_t)(16 * m) * a.L, a.L, g);
+      }
+      // the last iteration re-reads its own tile instead of branching around the prefetch
+      const TileWalk nx = tw.next();
+      const bool more = nx.n < a.N;
+      const size_t offn = (more ? nx : tw).base(C, a.L) + j;
+      const f32x4 xhn = load_tile(a.x + offn, a.L, g);
+      const f32x4 gxhn = load_tile(a.gx + offn, a.L, g);
+      const f32x4 xn = load_tile(a.tx + offn, a.L, g);
+      const f32x4 on = load_tile(a.o + offn, a.L, g);
+      prefetch_fence();
+      const f32x4 dv = head_bwd_chain(xh, gxh, dqv, hf, a.eps, ty, tq, j, g, hacc);
+      f32x4 dov, gxv;
+      tail_bwd_chain(xv, ov, dv, tf, a.eps, tiles, j, g, tacc, dov, gxv);
+      store_tile(a.d_o + off, a.L, g, dov);
+      store_tile(a.gx_out + off, a.L, g, gxv);
+      if (!more) break;
+      xh = xhn;
+      gxh = gxhn;
+      xv = xn;
+      ov = on;
+      off = offn;
+      tw = nx;
+    }
+  }
+
+  // ---- one partial row per workgroup and job: the four tail rows, then the four head rows
+  __syncthreads();
+  float* hstage = lds + 4 * T_PART;
+  tail_bwd_stage(lds + (size_t)wv * T_PART, tacc, j, g);
+  head_bwd_stage(hstage + (size_t)wv * H_PART, hacc, j, g);
+  __syncthreads();
+  write_partial_row(a.tpart + (size_t)blockIdx.x * T_PART, lds, T_PART);
+  write_partial_row(a.part + (size_t)blockIdx.x * H_PART, hstage, H_PART);
+  zero_rows_beyond_grid(a.tpart, T_PART, a.tail_rows);
+  zero_rows_beyond_grid(a.part, H_PART, a.head_rows);
 }
 
 // ---- second stage: the segmented reduce, the one kernel that turns rows of partial sums into gradients
@@ -709,24 +875,31 @@ __global__ void __launch_bounds__(256) seg_reduce_kernel(const SegJobs an) {
 }
 
 // Workgroups per launch, at least `min_tiles` tiles per wave. which: 0 head fwd, 1 head bwd, 2 tail fwd, 3 tail bwd,
-// 4 tail + head fwd. Resident waves per SIMD by register count (75 / 126 / 125 / 248 / 164 VGPRs): 6 / 4 / 4 / 2 / 3; tail bwd
-// is also held at two workgroups per CU by its 76 KiB of LDS. PG_BLOCK_GRID="a,b,c,d[,e]" overrides the caps (tuning).
+// 4 tail + head fwd, 5 head + tail bwd. Resident waves per SIMD by register count (75 / 118 / 125 / 166 / 164 / 233 VGPRs):
+// 6 / 4 / 4 / 3 / 3 / 2; head + tail bwd is also held at two workgroups per CU by its 71 KiB of LDS. Tail bwd fits three waves
+// since its chain runs the hidden dimension in chunks, but keeps the cap of two: 768 workgroups measured 136 us against 144
+// back to back, and every row it adds is read again by the reduce. Head + tail bwd at 384 / 256 workgroups leaves SIMDs idle
+// (234 / 240 us against 191), at 768 / 1024 adds part of a second round (198 / 195): profiles/gpt_boundary_bwd.json,
+// "grid_sweep_us_per_launch". PG_BLOCK_GRID="a,b,c,d[,e[,f]]" overrides the caps (tuning).
 // A backward kernel's workgroup count is also its number of partial rows (the *_bwd_workspace_floats and the reduce jobs use it).
 int grid_blocks(int which, int N, int L) {
   // immutable init-once tables (function-local static with an initialiser: thread-safe; the library
   // is entered from the main thread and from the autograd thread)
-  struct Cfg { int cap[5]; int mt[2]; };
+  struct Cfg { int cap[6]; int mt[2]; };
   static const Cfg cfg = []() {
     Cfg c = {{2048, 1024, 2048, 512,  // the backward caps are one full round of resident waves; the re-sweep with the pipelined
                                       // loops moved nothing beyond spread (profiles/gpt_block_pipeline.json, "grid_sweep_us_per_launch")
-              1536},                  // tail + head fwd: two whole rounds like tail fwd's 2048, but of 3 waves per SIMD
+              1536,                   // tail + head fwd: two whole rounds like tail fwd's 2048, but of 3 waves per SIMD
                                       // (256 CUs x 4 SIMDs x 3 waves / 4 waves per workgroup = 768 workgroups per round)
+              512},                   // head + tail bwd: one round of two waves per SIMD, as tail bwd
              {1, 2}};                 // tiles per wave below which the grid shrinks (forward, backward);
                                       // measured at batch 64: (4, 8) 1.82 ms/step, (2, 4) 1.59, (1, 2) 1.53, (1, 1) 1.56
     if (const char* e = PG_AB_ENV("PG_BLOCK_GRID")) {
-      int v[5];
-      const int got = sscanf(e, "%d,%d,%d,%d,%d", &v[0], &v[1], &v[2], &v[3], &v[4]);
-      if (got >= 4 && v[0] > 0 && v[1] > 0 && v[2] > 0 && v[3] > 0 && (got == 4 || v[4] > 0))
+      int v[6];
+      const int got = sscanf(e, "%d,%d,%d,%d,%d,%d", &v[0], &v[1], &v[2], &v[3], &v[4], &v[5]);
+      bool ok = got >= 4;
+      for (int i = 0; i < got; ++i) ok = ok && v[i] > 0;
+      if (ok)
         for (int i = 0; i < got; ++i) c.cap[i] = v[i];
     }
     if (const char* e = PG_AB_ENV("PG_BLOCK_MINTILES")) {
@@ -741,6 +914,10 @@ int grid_blocks(int which, int N, int L) {
   const long tiles = (long)N * (L / 16);
   long b = (tiles + 4 * min_tiles - 1) / (4 * min_tiles);
   if (b > cap[which]) b = cap[which];
+  if (which == 5) {  // its rows are reduced as the rows of head bwd and tail bwd: never more workgroups than either
+    if (b > cap[1]) b = cap[1];
+    if (b > cap[3]) b = cap[3];
+  }
   return b < 1 ? 1 : (int)b;
 }
 
@@ -986,11 +1163,8 @@ int tail_bwd_impl(const float* o, const float* x, const float* wp, const float* 
   set_geometry(a, N, L, eps);
   const int blocks = grid_blocks(3, N, L);
   hipStream_t st = (hipStream_t)stream;
-  const size_t tr = (size_t)4 * TB_WAVE_ROWS * TS + 64 * 64, rd = (size_t)4 * T_PART;
-  const size_t shmem = (tr > rd ? tr : rd) * sizeof(float);  // 76 KiB: above the 64 KB default, two workgroups per CU (160 KB)
-  static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(tail_bwd_kernel),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-  (void)attr;  // thread-safe one-time opt-in
+  const size_t tr = (size_t)4 * TB_WAVE_ROWS * TS + TB_FRAGS * 64, rd = (size_t)4 * T_PART;
+  const size_t shmem = (tr > rd ? tr : rd) * sizeof(float);  // 46 KiB
   hipLaunchKernelGGL(tail_bwd_kernel, dim3((unsigned)blocks), dim3(GB_THREADS), shmem, st, a);
   PG_LAUNCH_CHECK("pg_gpt_block_tail_bwd");
   if (!reduce_now) return 0;
@@ -1018,4 +1192,43 @@ PG_EXPORT int pg_gpt_block_tail_bwd_partial(const float* o, const float* x, cons
                                             size_t workspace_floats, void* stream) {
   return tail_bwd_impl(o, x, wp, bp, ln_w, ln_b, w1, b1, w2, dx_new, d_o, gx, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
                        nullptr, nullptr, N, Cc, Hd, L, eps, workspace, workspace_floats, false, stream);
+}
+
+// head_bwd of block i+1 and tail_bwd of block i in one launch (head_tail_bwd_kernel). next_* are pg_gpt_block_head_bwd_partial's
+// inputs of block i+1 (its dx is not written: it is the tail's dx_new and stays in registers), the rest pg_gpt_block_tail_bwd_partial's
+// of block i. d_o and gx are bit for bit what the two launches write; the partial rows land in the two workspaces as those launches
+// leave them for pg_gpt_model_reduce, fewer of them non-zero. eps serves both LayerNorms.
+PG_EXPORT int pg_gpt_block_head_tail_bwd_partial(const float* next_x, const float* next_ln_w, const float* next_ln_b,
+                                                 const float* next_wq, const float* next_wkv, const float* next_dqkv,
+                                                 const float* next_gx, const float* o, const float* x, const float* wp,
+                                                 const float* bp, const float* ln_w, const float* ln_b, const float* w1,
+                                                 const float* b1, const float* w2, float* d_o, float* gx, int N, int Cc, int Hd,
+                                                 int L, float eps, float* head_workspace, size_t head_workspace_floats,
+                                                 float* tail_workspace, size_t tail_workspace_floats, void* stream) {
+  PG_REQUIRE(next_x && next_ln_w && next_ln_b && next_wq && next_wkv && next_dqkv && next_gx && o && x && wp && bp && ln_w &&
+                 ln_b && w1 && b1 && w2 && d_o && gx && head_workspace && tail_workspace, PG_EINVAL,
+             "pg_gpt_block_head_tail_bwd_partial: null pointer");
+  int rc = check_shape("pg_gpt_block_head_tail_bwd_partial", N, Cc, L);
+  if (rc) return rc;
+  PG_REQUIRE(Hd == HD, PG_ESHAPE, "pg_gpt_block_head_tail_bwd_partial: only hidden = 64 is instantiated (got %d)", Hd);
+  PG_REQUIRE(head_workspace_floats >= pg_gpt_block_head_bwd_workspace_floats(N, L) &&
+                 tail_workspace_floats >= pg_gpt_block_tail_bwd_workspace_floats(N, L), PG_EINVAL,
+             "pg_gpt_block_head_tail_bwd_partial: workspace too small");
+  PG_REQUIRE(al16(next_dqkv) && al16(o), PG_EINVAL, "pg_gpt_block_head_tail_bwd_partial: o / next_dqkv must be 16-byte aligned");
+  BlockArgs a = {};
+  a.x = next_x; a.g1 = next_ln_w; a.be1 = next_ln_b; a.wq = next_wq; a.wkv = next_wkv; a.dqkv = next_dqkv; a.gx = next_gx;
+  a.part = head_workspace; a.head_rows = grid_blocks(1, N, L);
+  a.o = o; a.tx = x; a.wp = wp; a.bp = bp; a.g2 = ln_w; a.be2 = ln_b; a.w1 = w1; a.b1 = b1; a.w2 = w2;
+  a.d_o = d_o; a.gx_out = gx; a.tpart = tail_workspace; a.tail_rows = grid_blocks(3, N, L);
+  set_geometry(a, N, L, eps);
+  const size_t tr = (size_t)4 * (TB_WAVE_ROWS + HB_WAVE_ROWS) * TS + (TB_FRAGS + HB_FRAGS) * 64, rd = (size_t)4 * (T_PART + H_PART);
+  const size_t shmem = (tr > rd ? tr : rd) * sizeof(float);  // 71 KiB: above the 64 KB default, two workgroups per CU (160 KB)
+  static_assert(((size_t)4 * (TB_WAVE_ROWS + HB_WAVE_ROWS) * TS + (TB_FRAGS + HB_FRAGS) * 64) * sizeof(float) <= 80 * 1024 &&
+                    (size_t)4 * (T_PART + H_PART) * sizeof(float) <= 80 * 1024, "two workgroups per CU");
+  static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(head_tail_bwd_kernel),
+                                                     hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
+  (void)attr;  // thread-safe one-time opt-in
+  hipLaunchKernelGGL(head_tail_bwd_kernel, dim3((unsigned)grid_blocks(5, N, L)), dim3(GB_THREADS), shmem, (hipStream_t)stream, a);
+  PG_LAUNCH_CHECK("pg_gpt_block_head_tail_bwd_partial");
+  return 0;
 }

@@ -84,6 +84,7 @@ SIGNATURES = {
     "pg_gpt_block_tail_bwd": (c_i, [c_f] * 20 + [c_i, c_i, c_i, c_i, c_flt, c_f, c_z, c_s]),
     "pg_gpt_block_tail_bwd_workspace_floats": (c_z, [c_i, c_i]),
     "pg_gpt_block_tail_bwd_partial": (c_i, [c_f] * 12 + [c_i, c_i, c_i, c_i, c_flt, c_f, c_z, c_s]),
+    "pg_gpt_block_head_tail_bwd_partial": (c_i, [c_f] * 18 + [c_i, c_i, c_i, c_i, c_flt, c_f, c_z, c_f, c_z, c_s]),
     "pg_sample_embed": (c_i, [c_f] * 5 + [c_i] * 10 + [c_f, c_s]),
     "pg_attn_decode": (c_i, [c_f] * 4 + [c_i] * 8 + [c_f, c_s]),
     "pg_gpt_decode_plan": (c_i, [c_i] * 4 + [c_ip, c_i]),

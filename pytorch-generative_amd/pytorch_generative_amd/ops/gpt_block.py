@@ -90,6 +90,9 @@ def mlp_gelu(x, conv1, conv2, res=None):
 FUSE_BLOCK = os.environ.get("PG_FUSE_BLOCK", "1") != "0"
 # A/B: 0 = tail(i) and head(i+1) as two forward launches instead of pg_gpt_block_tail_head_fwd (read by ImageGPT.forward per call)
 FUSE_BOUNDARY = os.environ.get("PG_FUSE_BOUNDARY", "1") != "0"
+# A/B: 0 = head(i+1) and tail(i) as two backward launches instead of pg_gpt_block_head_tail_bwd_partial (read by ImageGPT.forward per
+# call; it concerns only the boundaries that the forward ran fused)
+FUSE_BOUNDARY_BWD = os.environ.get("PG_FUSE_BOUNDARY_BWD", "1") != "0"
 
 
 def _grad_targets(params):
@@ -132,6 +135,9 @@ def assert_no_pending_block_reductions():
         if c is not None and (c["jobs"] or c.get("out") is not None):
             raise RuntimeError(f"{len(c['jobs']) + (c.get('out') is not None)} deferred ImageGPT weight-gradient reductions were "
                                "never flushed: the backward that flushes them (the stem's, else the first block's) did not run")
+        if c is not None and c.get("deferred") is not None:
+            raise RuntimeError("a deferred ImageGPT head backward launch never ran: the backward of the previous block's tail, "
+                               "which takes it, did not run")
 
 
 def _ptrs(tensors):
@@ -174,6 +180,33 @@ def _take_boundary_qkv(pair, x, head, eps):
     return qkv if same else None
 
 
+def _pop_deferred_head(pair):
+    """The head backward launch that the NEXT block's _GPTBlockHead.backward left to this block's tail (pair["boundary"]["bwd"]),
+    or None. It is removed; whoever pops it launches it, fused or on its own."""
+    boundary = pair.get("boundary") if pair is not None else None
+    entry = boundary.pop("bwd", None) if boundary is not None else None
+    if entry is not None:
+        entry["chain"]["deferred"] = None
+    return entry
+
+
+def _is_deferred_dx(d, entry):
+    """d is the very tensor the deferred head backward returned unwritten: same memory, shape, strides and version."""
+    dx = entry["dx"]
+    return (d.data_ptr() == dx.data_ptr() and d.shape == dx.shape and d.stride() == dx.stride() and d.dtype == dx.dtype
+            and d._version == entry["version"])
+
+
+def _launch_deferred_head(entry):
+    """The deferred launch on its own, as _GPTBlockHead.backward would have run it: writes entry["dx"]."""
+    x, lnw, lnb, wq, wkv, dqkv, gx = entry["head"]
+    ws, (n, c, L) = entry["ws"], entry["geometry"]
+    _lib.check(_lib.load().pg_gpt_block_head_bwd_partial(x.data_ptr(), lnw.data_ptr(), lnb.data_ptr(), wq.data_ptr(),
+                                                         wkv.data_ptr(), dqkv.data_ptr(), gx.data_ptr(), entry["dx"].data_ptr(),
+                                                         n, c, L, entry["eps"], ws.data_ptr(), ws.numel(), _stream()),
+               "pg_gpt_block_head_bwd_partial")
+
+
 class _GPTBlockHead(torch.autograd.Function):
     """(qkv, x) = ([W_q; W_kv] LN1(x) + b, x). The second output aliases x: whatever gradient reaches it
     (the residual routes of the block) is added to LN1's input gradient inside the backward kernel."""
@@ -186,6 +219,9 @@ class _GPTBlockHead(torch.autograd.Function):
         x = _chk(x, "gpt_block_head.x")
         n, c, h, w = x.shape
         qkv = _take_boundary_qkv(pair, x, (lnw, lnb, wq, bq, wkv, bkv), eps)
+        # the backward may leave its launch to the previous block's tail only where that tail ran this head in its forward launch and
+        # the caller vouches that x has no other consumer (pair["defer_bwd"], set by ImageGPT.forward)
+        ctx.defer = qkv is not None and bool(pair.get("defer_bwd"))
         if qkv is None:
             qkv = torch.empty((n, 3 * c, h, w), device=x.device, dtype=torch.float32)
             _lib.check(
@@ -232,9 +268,18 @@ class _GPTBlockHead(torch.autograd.Function):
         # waits for the LAST backward of the model, which adds the rows of every block with one launch per 8 blocks; otherwise
         # it is reduced at once, one launch for the block
         t_ws, t = pending  # t order: wp, bp, lnw, lnb, w1, b1, w2, b2
-        _lib.check(lib.pg_gpt_block_head_bwd_partial(*head_args, *geometry), "pg_gpt_block_head_bwd_partial")
         # 14 destinations in the C-ABI's order: head lnw, lnb, wq, bq, wkv, bkv | tail w1, b1, w2, b2, wp, bp, lnw, lnb
         job = (ws, t_ws, [g.data_ptr() for g in tgt + t[4:] + t[:4]], (tgt, t))
+        if queue and not flusher and ctx.defer:
+            # The launch is left to the previous block's tail backward, which receives dx as its d x_new and runs both chains in one
+            # kernel (pg_gpt_block_head_tail_bwd_partial): dx is returned unwritten and is never read if that happens. The job is
+            # queued now, as always; its head rows are written before the model's last backward reduces them.
+            entry = {"dx": dx, "version": dx._version, "head": (x, lnw, lnb, wq, wkv, dqkv, gx), "ws": ws,
+                     "geometry": (n, c, h * w), "eps": ctx.eps, "chain": chain}
+            ctx.pair["boundary"]["bwd"] = chain["deferred"] = entry
+            chain["jobs"].append(job)
+            return (dx, *ret, None, None, None)
+        _lib.check(lib.pg_gpt_block_head_bwd_partial(*head_args, *geometry), "pg_gpt_block_head_bwd_partial")
         if not queue:
             reduce_rows([job], n, c, h * w)
         else:
@@ -288,13 +333,33 @@ class _GPTBlockTail(torch.autograd.Function):
     def backward(ctx, d):
         lib = _lib.load()
         o, x, wp, bp, lnw, lnb, w1, b1, w2 = ctx.saved_tensors
-        d = _chk(d, "gpt_block_tail.dx_new")
         n, c, h, w = x.shape
-        d_o, gx = torch.empty_like(o), torch.empty_like(x)
         tgt, ret = _grad_targets(ctx.params)  # order: wp, bp, lnw, lnb, w1, b1, w2, b2
+        parks = ctx.pair is not None and all(r is None for r in ret)
+        # the next block's head backward may have left its launch to this one: taken only if d is the tensor it returned unwritten
+        # and this kernel parks its rows as well; otherwise that launch runs first, on its own, and d is then what it wrote
+        deferred = _pop_deferred_head(ctx.pair)
+        fuse = (deferred is not None and parks and _is_deferred_dx(d, deferred) and deferred["eps"] == ctx.eps
+                and deferred["geometry"] == (n, c, h * w))
+        if deferred is not None and not fuse:
+            _launch_deferred_head(deferred)
+        d = _chk(d, "gpt_block_tail.dx_new")
+        d_o, gx = torch.empty_like(o), torch.empty_like(x)
         ws_n = lib.pg_gpt_block_tail_bwd_workspace_floats(n, h * w)
         ws = torch.empty(ws_n, device=x.device, dtype=torch.float32)
-        if ctx.pair is not None and all(r is None for r in ret):
+        if fuse:
+            hws = deferred["ws"]
+            _lib.check(
+                lib.pg_gpt_block_head_tail_bwd_partial(*(t.data_ptr() for t in deferred["head"]), o.data_ptr(), x.data_ptr(),
+                                                       wp.data_ptr(), bp.data_ptr(), lnw.data_ptr(), lnb.data_ptr(),
+                                                       w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), d_o.data_ptr(), gx.data_ptr(),
+                                                       n, c, w1.shape[0], h * w, ctx.eps, hws.data_ptr(), hws.numel(),
+                                                       ws.data_ptr(), ws_n, _stream()),
+                "pg_gpt_block_head_tail_bwd_partial",
+            )
+            ctx.pair["tail"] = (ws, tgt)
+            return (d_o, gx, *ret, None, None, None)
+        if parks:
             # every gradient goes into a sink (FlatAdam): leave the partial rows for the head's backward of the
             # same block, which reduces both kernels' rows in one launch or queues them for the model's
             _lib.check(

@@ -1,5 +1,5 @@
-"""A few launches of the GPT-block kernels (csrc/gpt_block.hip: head / tail forward and backward, and the fused tail + next head
-forward) at the bench's batch, through the C-ABI, for rocprofv3 counter
+"""A few launches of the GPT-block kernels (csrc/gpt_block.hip: head / tail forward and backward, the fused tail + next head
+forward and the fused next head + tail backward) at the bench's batch, through the C-ABI, for rocprofv3 counter
 passes (--pmc alone, never combined with a trace domain) and for a library A/B (PG_HIP_LIB=<other build>):
 
     python tools/exp/block_launch.py [launches] [batch]
@@ -28,6 +28,7 @@ r = lambda *s: torch.randn(*s, device=dev)  # noqa: E731
 x, o, d, gx, dqkv = r(n, 16, L), r(n, 16, L), r(n, 16, L), r(n, 16, L), r(n, 48, L)
 qkv, xnew, d_o, gxo, dx = (torch.empty(n, c, L, device=dev) for c in (48, 16, 16, 16, 16))
 qkv2, xnew2 = torch.empty(n, 48, L, device=dev), torch.empty(n, 16, L, device=dev)  # the fused launch's own outputs
+d_o2, gxo2 = torch.empty(n, 16, L, device=dev), torch.empty(n, 16, L, device=dev)
 g1, be1, wq, bq, wkv, bkv = r(16), r(16), r(16, 16) * .2, r(16), r(32, 16) * .2, r(32)
 wp, bp, g2, be2, w1, b1, w2, b2 = r(16, 16) * .2, r(16), r(16), r(16), r(64, 16) * .2, r(64), r(16, 64) * .1, r(16)
 G = {k: torch.zeros_like(v) for k, v in dict(g1=g1, be1=be1, wq=wq, bq=bq, wkv=wkv, bkv=bkv, wp=wp, bp=bp, g2=g2, be2=be2, w1=w1,
@@ -49,6 +50,15 @@ calls = {
                                                   p(G["b2"]), n, 16, 64, L, eps, p(tws), tn, st),
     "head_bwd": lambda: lib.pg_gpt_block_head_bwd(p(x), p(g1), p(be1), p(wq), p(wkv), p(dqkv), p(gx), p(dx), p(G["g1"]), p(G["be1"]),
                                                   p(G["wq"]), p(G["bq"]), p(G["wkv"]), p(G["bkv"]), n, 16, L, eps, p(hws), hn, st),
+    # the backward boundary without any reduce launch: the two kernels on their own, then both chains in one launch (x and the
+    # head's parameters stand in for the next block's; d_o2 / gxo2 are the fused launch's own outputs)
+    "tail_bwd_partial": lambda: lib.pg_gpt_block_tail_bwd_partial(p(o), p(x), p(wp), p(bp), p(g2), p(be2), p(w1), p(b1), p(w2), p(d),
+                                                                  p(d_o), p(gxo), n, 16, 64, L, eps, p(tws), tn, st),
+    "head_bwd_partial": lambda: lib.pg_gpt_block_head_bwd_partial(p(x), p(g1), p(be1), p(wq), p(wkv), p(dqkv), p(gx), p(dx), n, 16, L,
+                                                                  eps, p(hws), hn, st),
+    "head_tail_bwd_partial": lambda: lib.pg_gpt_block_head_tail_bwd_partial(
+        p(x), p(g1), p(be1), p(wq), p(wkv), p(dqkv), p(gx), p(o), p(x), p(wp), p(bp), p(g2), p(be2), p(w1), p(b1), p(w2), p(d_o2),
+        p(gxo2), n, 16, 64, L, eps, p(hws), hn, p(tws), tn, st),
 }
 out = {"launches": launches, "batch": n, "lib": os.path.basename(_lib.LIB_PATH)}
 for name, fn in calls.items():
