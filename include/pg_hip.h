@@ -327,6 +327,32 @@ int pg_masked_linear_mask(float* mask, const int* deg_in, const int* deg_out, in
                           void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Sampling a one-hidden-layer MADE in one launch on cached hidden sums (csrc/made_sample.hip; the reference's sampler,
+ * made.py:125-141, runs one full forward per dimension). All tensors dense row-major fp32; w1 (H, D) and w2 (D, H) are the
+ * layers' weights ALREADY masked (exact zeros where the mask is 0: the kernels evaluate no mask).
+ * Per sample n, a[h] = b1[h]; then for i = order[0], order[1], ..., order[D - 1]:
+ *   l = b2[i] + sum_h max(a[h], 0) * w2[i][h];  p = 1 / (1 + exp(-l));
+ *   x = canvas[n][i] if that is >= 0 (any float, not only 0 and 1), else (uniforms[n][i] < p ? 1 : 0);
+ *   canvas[n][i] = x;  logits_out[n][i] = l (logits_out may be NULL);  a[h] += x * w1[h][i] for every h.
+ * order: int32 (D), a permutation of 0..D-1 (an entry outside [0, D) is clamped into it); canvas, uniforms, logits_out: (N, D),
+ * uniforms indexed by dimension, not by step. All arithmetic fp32; no float atomics, the sum over h in a fixed order that
+ * depends on H alone: a sample's rows of canvas and logits_out are bit-identical from run to run and for any N.
+ * pg_made_sample_plan (host only, no device call) is the one function that decides the domain and the geometry; the pack and
+ * the launch call it too. It fills out[0 .. PG_MADE_SAMPLE_PLAN_INTS): samples per workgroup, threads per workgroup, hidden
+ * units per thread, LDS bytes per workgroup, pack floats, floats of a padded weight row (threads * units), workgroups, the
+ * largest H. Any D, N >= 1 and H in 1..8192 with a pack below 2^31 floats (PG_ESHAPE otherwise, from the plan, the pack and
+ * the launch alike, nothing launched); PG_EINVAL for a null pointer, a short array, a non-positive dimension or a pack that
+ * is not 16-byte aligned.
+ *   pg_made_sample_pack: pack (D, 2, row floats) = [w2[i][:] | w1[:][i]] per dimension i, zeros from H on: what a step reads,
+ *   contiguous. Made once per call from the masked weights.
+ * ------------------------------------------------------------------------------------- */
+#define PG_MADE_SAMPLE_PLAN_INTS 8
+int pg_made_sample_plan(int D, int H, int N, int* out, int out_len);
+int pg_made_sample_pack(const float* w1, const float* w2, float* pack, int D, int H, void* stream);
+int pg_made_sample(const float* pack, const float* b1, const float* b2, const int* order, float* canvas,
+                   const float* uniforms, float* logits_out, int N, int D, int H, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Density estimators (models/mixture_models.py, models/kde.py) on streaming log-density kernels (density.hip):
  * the pairwise log-density c[n][k] = sum_d f(x[n][d], theta[k][d]) is one or two fp32-MFMA GEMMs plus a per-column
  * constant, reduced by a running logsumexp over column tiles; nothing of size N x K (x F) is written to memory.

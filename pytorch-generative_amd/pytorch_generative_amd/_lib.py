@@ -126,6 +126,9 @@ SIGNATURES = {
     "pg_masked_linear_dgrad": (c_i, [c_f] * 4 + [c_i, c_f, c_f] + [c_i] * 3 + [c_f, c_z, c_s]),
     "pg_masked_linear_wgrad": (c_i, [c_f] * 4 + [c_i] * 3 + [c_s]),
     "pg_masked_linear_mask": (c_i, [c_f] * 3 + [c_i] * 3 + [c_s]),
+    "pg_made_sample_plan": (c_i, [c_i] * 3 + [c_ip, c_i]),
+    "pg_made_sample_pack": (c_i, [c_f] * 3 + [c_i] * 2 + [c_s]),
+    "pg_made_sample": (c_i, [c_f] * 7 + [c_i] * 3 + [c_s]),
     "pg_mixture_workspace_floats": (c_z, [c_i] * 5),
     "pg_mixture_fwd": (c_i, [c_i] + [c_f] * 6 + [c_i] * 3 + [c_f, c_z, c_s]),
     "pg_mixture_bwd": (c_i, [c_i] + [c_f] * 9 + [c_i] * 3 + [c_f, c_z, c_s]),

@@ -12,6 +12,14 @@ numpy's RandomState(mask_seed % n_masks) in `_sample_masks()`; what differs is w
 * forward is one autograd Function over the whole network (ops.masked_mlp): masked GEMMs with the ReLU fused into
   the epilogues, `weight.data *= mask` done by the forward kernel, the reference's UNMASKED weight gradient.
 
+Sampling: the reference (made.py:125-141) runs one full masked forward per dimension and uses one logit of it. With exactly one
+hidden layer the work per dimension collapses to what NADE does: the hidden pre-activation a = b1 + W1m x changes by the rank-1
+update a += x_i W1m[:, i] when dimension i is fixed, and the one logit needed is b2[i] + relu(a) . W2m[i, :]. sample() then
+draws the whole batch in ONE launch (ops.made_sample_chain, csrc/made_sample.hip; route "chain"), from uniforms drawn once
+per call: x_i = (u_i < sigmoid(l_i)). Same distribution as Bernoulli(logits=l_i), another random stream. Every other case —
+`incremental=False`, a user `sample_fn`, no or several hidden layers, a shape the kernel's plan refuses — runs the reference's
+procedure (route "full"); `_sample_route` tells which one the last call took.
+
 hipGraph capture: with n_masks == 1 the mask never changes and the training step captures and replays
 (graph.GraphedTrainStep, trainer.Trainer). With n_masks > 1 a captured step would freeze one mask, so forward RAISES
 while a capture is open; `graph_capture_refusal()` tells the Trainer before it starts its warm-up steps, and it
@@ -82,6 +90,8 @@ class MADE(base.AutoregressiveModel):
         self._net = nn.Sequential(*layers[:-1])
         self._conn = {}      # mask index -> connectivity (host numpy)
         self._degrees = {}   # (mask index, device) -> int32 device vector conn[0] | conn[1] | ... | conn[-2]
+        self._orders = {}    # (mask index, device) -> int32 device vector argsort(conn[-1]): the dimension drawn at each step
+        self._sample_route = None  # "chain" or "full": what the last sample() call ran
         self._mask_index = None  # mask index whose masks the `mask` buffers hold
         self._mask_versions = None  # the buffers' version counters right after that write
 
@@ -157,12 +167,67 @@ class MADE(base.AutoregressiveModel):
         """x: (n, input_dim) vectors or (n, 1, h, w) images with h * w = input_dim; returns logits of x's shape."""
         return self._forward(x.contiguous(), self._next_mask_index())
 
+    def _start_canvas(self, n_samples, conditioned_on):
+        """As the base class; a model that has seen no image batch (no recorded shape) starts from (n_samples, input_dim)."""
+        if conditioned_on is None and n_samples is not None and getattr(self, "_c", None) is None:
+            return torch.full((n_samples, self._input_dim), -1.0, device=self.device)
+        return super()._start_canvas(n_samples, conditioned_on)
+
+    def _route(self, n, incremental):
+        """"chain" when the one-launch sampler applies: asked for, exactly one hidden layer, the base class's Bernoulli draw
+        (a user `sample_fn` sees every logit vector, so it keeps the reference's procedure) and a shape the plan accepts."""
+        if (incremental and len(self._dims) == 3 and self._sample_fn is base._bernoulli_from_logits
+                and ops.made_sample_plan(self._input_dim, self._dims[1], n) is not None):
+            return "chain"
+        return "full"
+
     @torch.no_grad()
-    def sample(self, n_samples=None, conditioned_on=None):
-        """Fills the entries of `conditioned_on` that are < 0 (made.py:125-141): one mask draw, then one full forward
-        per dimension in the order argsort(ordering)."""
-        conditioned_on = self._start_canvas(n_samples, conditioned_on)
-        return self._sample(conditioned_on)
+    def sample(self, n_samples=None, conditioned_on=None, *, incremental=True, return_logits=False, generator=None):
+        """Fills the entries of `conditioned_on` that are < 0 (made.py:125-141): one mask draw, then the dimensions in the
+        order argsort(ordering), each from the logit its predecessors give it. `conditioned_on` is not modified.
+
+        incremental (extension): a network with one hidden layer and the default Bernoulli `sample_fn` is drawn in one launch
+        on cached hidden sums (ops.made_sample_chain) instead of one full forward per dimension. That route draws
+        x_i = (u_i < sigmoid(l_i)) from uniforms u = torch.rand((n, D), generator=generator) made once per call: the same
+        distribution as the reference's Bernoulli(logits), but another random stream, so a seeded run differs from
+        incremental=False (as with the other incremental samplers). Mask rotation, the `mask` buffers and the in-place masking
+        of both weights are what one forward would leave. `_sample_route` is "chain" or "full" afterwards.
+        return_logits (extension, "chain" only): also returns logits shaped like the sample, logits[n, i] being the logit
+        dimension i was decided from (for a given entry: the one it would have been drawn from).
+        generator (extension): the torch.Generator of the uniforms (one of the model's device); the "full" route draws through
+        `sample_fn` and ignores it."""
+        canvas = self._start_canvas(n_samples, conditioned_on)
+        self._sample_route = self._route(canvas.shape[0], incremental)
+        if self._sample_route == "chain":
+            return self._sample_chain(canvas, return_logits, generator)
+        if return_logits:
+            raise ValueError("MADE.sample: return_logits needs the one-launch route (one hidden layer, the default sample_fn, "
+                             "incremental=True)")
+        return self._sample(canvas)
+
+    def _order(self, index, device):
+        key = (index, str(device))
+        order = self._orders.get(key)
+        if order is None:
+            order = torch.from_numpy(np.argsort(self._connectivity(index)[-1]).astype(np.int32)).to(device)
+            self._orders[key] = order
+        return order
+
+    def _sample_chain(self, canvas, return_logits, generator):
+        index = self._next_mask_index()
+        self._no_input_codes()
+        shape = canvas.shape
+        x = canvas.contiguous().view(shape[0], -1)
+        self._layer_specs(index, x.device)  # the `mask` buffers of this index
+        hidden, out = self._masked_layers()
+        for layer in (hidden, out):  # weight.data *= mask, as the forward leaves it: the kernel evaluates no mask
+            ops.mul_mask_(layer.weight, layer.mask)
+        uniforms = torch.rand(x.shape, device=x.device, generator=generator)
+        got = ops.made_sample_chain(x, hidden.weight.data, hidden.bias.data, out.weight.data, out.bias.data,
+                                    self._order(index, x.device), uniforms, return_logits=return_logits)
+        if return_logits:
+            return got[0].view(shape), got[1].view(shape)
+        return got.view(shape)
 
     @base.auto_reshape
     def _sample(self, x):

@@ -151,6 +151,10 @@ from pytorch_generative_amd.ops.masked_linear import (  # noqa: F401
     masked_mlp,
     mul_mask_,
 )
+from pytorch_generative_amd.ops.made_sample import (  # noqa: F401
+    made_sample_plan,
+    made_sample_chain,
+)
 from pytorch_generative_amd.ops.density import (  # noqa: F401
     _MixtureLogProb,
     MIXTURE_BERNOULLI,
