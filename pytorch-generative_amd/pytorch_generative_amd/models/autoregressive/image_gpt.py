@@ -7,6 +7,8 @@ NCHW LayerNorm, 1x1 convs (residual adds fused into the projection / MLP-out ker
 GELU, and the fused causal attention core.
 """
 
+import itertools
+
 import torch
 from torch import nn
 
@@ -38,29 +40,10 @@ class TransformerBlock(nn.Module):
         return ops.gpt_block_supported(x, self._ln1, self._attn._q, self._attn._kv, self._attn._proj,
                                        self._ln2, self._out[0], self._out[2])
 
-    def forward_plus_input(self, x, chain=None, flush=False, boundary=None, next_block=None, defer_bwd=False):
+    def forward_plus_input(self, x):
         """x + self(x) — what the model loop computes (reference image_gpt.py:107) — on the fused
-        head / attention / tail kernels (gpt_block.hip) when the block has the BASELINE shape.
-        chain / flush: a queue shared by all blocks of the model, flushed by the block whose backward runs last —
-        the weight-gradient rows of all blocks are then reduced by ONE launch (ops.gpt_block_head).
-        boundary / next_block: a dict shared by the blocks of one forward and the block that runs next (fused shape as well) —
-        this block's tail launch then also computes that block's LN1 and q/kv projection (ops.gpt_block_tail).
-        defer_bwd: x is the output of the previous block's forward_plus_input(..., next_block=self) and NOTHING else consumes it —
-        this block's head backward may then leave its launch to that block's tail backward (pg_gpt_block_head_tail_bwd_partial)."""
-        if not self._fused_ok(x):
-            return ops.add(x, self.forward(x))
-        attn = self._attn
-        pair = {}  # lets the block's two backward kernels share one weight-gradient reduction launch
-        if chain is not None:
-            pair["chain"], pair["flush"] = chain, flush
-        if boundary is not None:
-            pair["boundary"] = boundary
-            pair["defer_bwd"] = defer_bwd and chain is not None
-        nxt = None if next_block is None else (next_block._ln1, next_block._attn._q, next_block._attn._kv)
-        qkv, xs = ops.gpt_block_head(x, self._ln1, attn._q, attn._kv, pair)
-        o = ops.causal_attention_qkv(qkv, attn._n_heads, attn._embed_channels, attn._out_channels,
-                                     attn._mask_center)
-        return ops.gpt_block_tail(o, xs, attn._proj, self._ln2, self._out[0], self._out[2], pair, nxt)
+        head / attention / tail kernels (gpt_block.hip, ops.gpt_blocks) when the block has the BASELINE shape."""
+        return ops.gpt_blocks(x, [self]) if self._fused_ok(x) else ops.add(x, self.forward(x))
 
     def forward(self, x):
         # skip=True: the residual branch's gradient is added inside the LayerNorm backward kernel
@@ -267,17 +250,15 @@ class ImageGPT(base.AutoregressiveModel):
             chain = ops.new_block_chain()
         if fuse_stem:
             x = self._input(img, pos=self._pos, chain=chain if stem_flushes else None)
-        # block boundaries: tail(i) + head(i+1) in one launch where both blocks take the fused kernels; PG_FUSE_BOUNDARY=0 = two
-        fused = [b._fused_ok(probe) for b in blocks] if ops.gpt_block.FUSE_BOUNDARY else [False] * len(blocks)
-        boundary = {} if any(fused) else None
-        # backward: head(i+1) + tail(i) in one launch at the boundaries fused above (x_new of block i feeds block i+1 and nothing
-        # else here); PG_FUSE_BOUNDARY_BWD=0 = two
-        defer, after_fused = grad and ops.gpt_block.FUSE_BOUNDARY_BWD, False
-        for i, block in enumerate(blocks):
-            nxt = blocks[i + 1] if i + 1 < len(blocks) and fused[i] and fused[i + 1] else None
-            x = block.forward_plus_input(x, chain, flush=(i == 0 and not stem_flushes), boundary=boundary, next_block=nxt,
-                                         defer_bwd=defer and after_fused)
-            after_fused = nxt is not None
+        # every maximal run of blocks that take the fused kernels (all of them or none, in practice) is one autograd node, which
+        # runs each boundary inside it — tail(i) + head(i+1), and head(i+1) + tail(i) backward — as one launch (ops.gpt_blocks)
+        for ok, run in itertools.groupby(blocks, key=lambda b: b._fused_ok(probe)):
+            run = list(run)
+            if ok:
+                x = ops.gpt_blocks(x, run, chain, flush=run[0] is blocks[0] and not stem_flushes)
+            else:
+                for block in run:
+                    x = block.forward_plus_input(x)
         # defer_head: the head runs inside the loss (ops.DeferredLogits) and reduces its own rows: it does not join the chain
         return self._logits(x, self._out, pre_ln=self._ln, chain=chain if stem_flushes else None)
 

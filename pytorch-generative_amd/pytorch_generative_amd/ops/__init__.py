@@ -29,6 +29,7 @@ from pytorch_generative_amd.ops._common import (  # noqa: F401
     zeros,
     zeros_like,
     _sink,
+    _grad_targets,
     CONV_FMT_F32,
     CONV_FMT_B3,
     CONV_FMT_B3_GATE,
@@ -93,7 +94,6 @@ from pytorch_generative_amd.ops.gpt_block import (  # noqa: F401
     _MlpGelu,
     mlp_gelu,
     FUSE_BLOCK,
-    _grad_targets,
     new_block_chain,
     assert_no_pending_block_reductions,
     reduce_rows,
@@ -102,6 +102,7 @@ from pytorch_generative_amd.ops.gpt_block import (  # noqa: F401
     gpt_block_supported,
     gpt_block_head,
     gpt_block_tail,
+    gpt_blocks,
     _NCHWLayerNorm,
     nchw_layernorm,
     nchw_layernorm_skip,

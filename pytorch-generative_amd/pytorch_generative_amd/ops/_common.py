@@ -128,6 +128,22 @@ def _sink(param):
     return getattr(param, "_pg_grad", None) if param is not None else None
 
 
+def _grad_targets(params):
+    """Per parameter: (tensor the kernel adds into, value to return to autograd): the direct sink if
+    the parameter has one (then autograd gets None), else a fresh zero tensor."""
+    tgt, ret = [], []
+    for p in params:
+        sink = _sink(p)
+        if sink is not None:
+            tgt.append(sink)
+            ret.append(None)
+        else:
+            z = zeros_like(p)
+            tgt.append(z)
+            ret.append(z)
+    return tgt, ret
+
+
 CONV_FMT_F32, CONV_FMT_B3, CONV_FMT_B3_GATE = 1, 2, 3  # include/pg_hip.h PG_CONV_FMT_*
 FUSE_SKIP = os.environ.get("PG_FUSE_SKIP", "1") != "0"  # A/B: 0 = plain fan-out, autograd sums the gradients
 

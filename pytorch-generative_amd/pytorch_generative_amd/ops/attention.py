@@ -64,56 +64,61 @@ class _CausalAttention(torch.autograd.Function):
         return dq, dkv, None, None, None, None
 
 
+def attention_qkv_fwd(qkv, n_heads, embed, vdim, strict):
+    """The causal core on ONE contiguous (N, embed + embed + vdim, H, W) tensor [q | k | v], head dims the kernels take as they
+    are: (o, lse2). A plain launch, for the Functions that own the tensors (_CausalAttentionQKV, ops.gpt_blocks)."""
+    n, ch, h, w = qkv.shape
+    if ch != 2 * embed + vdim:
+        raise ValueError("attention: qkv channel count != 2 * embed + value dims")
+    if embed % n_heads or vdim % n_heads:
+        raise ValueError("attention: channels not divisible by n_heads")
+    L = h * w
+    o = torch.empty((n, vdim, h, w), device=qkv.device, dtype=torch.float32)
+    lse2 = torch.empty((n, n_heads, L), device=qkv.device, dtype=torch.float32)
+    base, bs = qkv.data_ptr(), ch * L
+    _lib.check(
+        _lib.load().pg_causal_attn_fwd(base, base + 4 * embed * L, base + 8 * embed * L, o.data_ptr(), lse2.data_ptr(), n,
+                                       n_heads, L, embed // n_heads, vdim // n_heads, bs, bs, bs, vdim * L, int(strict),
+                                       _stream()),
+        "pg_causal_attn_fwd",
+    )
+    return o, lse2
+
+
+def attention_qkv_bwd(qkv, o, lse2, d_o, n_heads, embed, vdim, strict):
+    """d qkv of attention_qkv_fwd, one tensor of qkv's layout."""
+    d_o = _chk(d_o, "attention.d_o")
+    n, ch, h, w = qkv.shape
+    L = h * w
+    dqkv = torch.empty_like(qkv)
+    delta = torch.empty_like(lse2)
+    base, gbase, bs = qkv.data_ptr(), dqkv.data_ptr(), ch * L
+    _lib.check(
+        _lib.load().pg_causal_attn_bwd(
+            base, base + 4 * embed * L, base + 8 * embed * L, o.data_ptr(), d_o.data_ptr(), lse2.data_ptr(),
+            delta.data_ptr(), gbase, gbase + 4 * embed * L, gbase + 8 * embed * L, n, n_heads, L, embed // n_heads,
+            vdim // n_heads, bs, bs, bs, vdim * L, vdim * L, bs, bs, bs, int(strict), _stream(),
+        ),
+        "pg_causal_attn_bwd",
+    )
+    return dqkv
+
+
 class _CausalAttentionQKV(torch.autograd.Function):
     """Same core on ONE (N, embed + embed + vdim, H, W) tensor [q | k | v] — the output of the merged
     q/kv projection (conv2d_pair); its gradient is produced as one tensor of the same layout."""
 
     @staticmethod
     def forward(ctx, qkv, n_heads, embed, vdim, strict):
-        lib = _lib.load()
         qkv = _chk(qkv, "attention.qkv")
-        n, ch, h, w = qkv.shape
-        if ch != 2 * embed + vdim:
-            raise ValueError("attention: qkv channel count != 2 * embed + value dims")
-        if embed % n_heads or vdim % n_heads:
-            raise ValueError("attention: channels not divisible by n_heads")
-        L = h * w
-        dk, dv = embed // n_heads, vdim // n_heads
-        o = torch.empty((n, vdim, h, w), device=qkv.device, dtype=torch.float32)
-        lse2 = torch.empty((n, n_heads, L), device=qkv.device, dtype=torch.float32)
-        base, bs = qkv.data_ptr(), ch * L
-        _lib.check(
-            lib.pg_causal_attn_fwd(base, base + 4 * embed * L, base + 8 * embed * L, o.data_ptr(),
-                                   lse2.data_ptr(), n, n_heads, L, dk, dv, bs, bs, bs, vdim * L,
-                                   int(strict), _stream()),
-            "pg_causal_attn_fwd",
-        )
+        o, lse2 = attention_qkv_fwd(qkv, n_heads, embed, vdim, strict)
         ctx.save_for_backward(qkv, o, lse2)
         ctx.cfg = (n_heads, embed, vdim, int(strict))
         return o
 
     @staticmethod
     def backward(ctx, d_o):
-        lib = _lib.load()
-        qkv, o, lse2 = ctx.saved_tensors
-        n_heads, embed, vdim, strict = ctx.cfg
-        d_o = _chk(d_o, "attention.d_o")
-        n, ch, h, w = qkv.shape
-        L = h * w
-        dk, dv = embed // n_heads, vdim // n_heads
-        dqkv = torch.empty_like(qkv)
-        delta = torch.empty_like(lse2)
-        base, gbase, bs = qkv.data_ptr(), dqkv.data_ptr(), ch * L
-        _lib.check(
-            lib.pg_causal_attn_bwd(
-                base, base + 4 * embed * L, base + 8 * embed * L, o.data_ptr(), d_o.data_ptr(),
-                lse2.data_ptr(), delta.data_ptr(), gbase, gbase + 4 * embed * L,
-                gbase + 8 * embed * L, n, n_heads, L, dk, dv, bs, bs, bs, vdim * L, vdim * L, bs, bs,
-                bs, strict, _stream(),
-            ),
-            "pg_causal_attn_bwd",
-        )
-        return dqkv, None, None, None, None
+        return attention_qkv_bwd(*ctx.saved_tensors, d_o, *ctx.cfg), None, None, None, None
 
 
 class _MergeQKVWeight(torch.autograd.Function):

@@ -10,16 +10,11 @@ import os
 import torch
 
 from pytorch_generative_amd import _lib
-from pytorch_generative_amd.ops._common import RowDecode, _chk, _stream
-from pytorch_generative_amd.ops.gpt_block import _grad_targets, reduce_rows
+from pytorch_generative_amd.ops._common import RowDecode, _chk, _grad_targets, _stream
+from pytorch_generative_amd.ops.gpt_block import reduce_rows
 
 FUSE_ENDS = os.environ.get("PG_FUSE_ENDS", "1") != "0"  # A/B: 0 = the generic operators (add, mask, conv_taps, LayerNorm, 1x1)
 MAX_OUT_CHANNELS = 4  # csrc/gpt_ends.h MAX_COUT
-
-
-def _flush(chain, n, c, L, stem=None):
-    """Empties `chain`: the queued blocks, the output head's rows if its backward parked them, and the caller's stem rows."""
-    reduce_rows(chain["jobs"], n, c, L, out=chain.pop("out", None), stem=stem)
 
 
 # --------------------------------------------------------------------------------------------
@@ -75,10 +70,10 @@ class _GPTStem(torch.autograd.Function):
             stem = (ws, rows.value, slices.value, h, w, [tgt[1], tgt[2], tgt[0]])
         except BaseException:
             if chain is not None:  # whatever was queued still reaches its destinations
-                _flush(chain, n, 16, h * w)
+                chain.flush(n, 16, h * w)
             raise
         if chain is not None:
-            _flush(chain, n, 16, h * w, stem=stem)
+            chain.flush(n, 16, h * w, stem=stem)
         else:
             reduce_rows([], n, 16, h * w, stem=stem)
         return None, ret[0], ret[1], ret[2], None, None, None
@@ -137,7 +132,7 @@ class _GPTOutHead(torch.autograd.Function):
                                            ws.data_ptr(), ws_n, _stream()), "pg_gpt_out_head_bwd")
         out = (ws, rows, cout, tgt)
         if ctx.chain is not None and all(r is None for r in ret):
-            ctx.chain["out"] = out  # the stem's backward adds these rows in the step's one reduce launch
+            ctx.chain.out = out  # the stem's backward adds these rows in the step's one reduce launch
         else:
             reduce_rows([], n, c, L, out=out)
         return dx, ret[0], ret[1], ret[2], ret[3], None, None, None, None

@@ -12,8 +12,7 @@ import ctypes
 import torch
 
 from pytorch_generative_amd import _lib
-from pytorch_generative_amd.ops._common import RowDecode, _chk, _p, _stream, zeros
-from pytorch_generative_amd.ops.gpt_block import _grad_targets
+from pytorch_generative_amd.ops._common import RowDecode, _chk, _grad_targets, _p, _stream, zeros
 from pytorch_generative_amd.ops.gpt_ends import gpt_out_head_supported
 
 TRANSFORM_NONE, TRANSFORM_RELU, TRANSFORM_LN = 0, 1, 2  # include/pg_hip.h PG_LC_*

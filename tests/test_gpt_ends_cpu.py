@@ -51,10 +51,10 @@ def test_parked_output_head_rows_count_as_pending():
 
     chain = ops.new_block_chain()
     ops.assert_no_pending_block_reductions()
-    chain["out"] = ("workspace", 1, 1, [])
+    chain.out = ("workspace", 1, 1, [])
     with pytest.raises(RuntimeError, match="never flushed"):
         ops.assert_no_pending_block_reductions()
-    chain.pop("out")
+    chain.out = None
     ops.assert_no_pending_block_reductions()
 
 

@@ -194,9 +194,7 @@ def _first_block_flushes(m):
         with torch.no_grad():
             x = m._input(img, pos=m._pos)
         x.requires_grad_(True)
-        chain = ops.new_block_chain()
-        for i, block in enumerate(m._transformer):
-            x = block.forward_plus_input(x, chain, flush=(i == 0))
+        x = ops.gpt_blocks(x, list(m._transformer), ops.new_block_chain(), flush=True)
         return m._out(x, pre_ln=m._ln)
 
     return forward
@@ -210,7 +208,7 @@ def test_model_routes_agree_bitwise_and_launch_as_counted(dev, lib, monkeypatch)
                  not flush: the output head, then the first block flushes both                              [0, 2]
       no_sinks   plain .grad: every block kernel reduces its own rows; the output head, then the stem        [0, 0]
     ImageGPT.forward declines the chain when the first block's input needs no gradient, so a frozen stem selects own_rows and
-    not first; first is therefore driven through TransformerBlock.forward_plus_input."""
+    not first; first is therefore driven through ops.gpt_blocks."""
     from pytorch_generative_amd import ops
 
     for name in REMOVED:

@@ -717,8 +717,8 @@ def test_deferred_block_reductions_must_be_flushed_before_a_step():
 
     chain = ops.new_block_chain()
     ops.assert_no_pending_block_reductions()
-    chain["jobs"].append(("head_ws", "tail_ws", [0] * 14, None))
+    chain.jobs.append(("head_ws", "tail_ws", [0] * 14, None))
     with pytest.raises(RuntimeError, match="never flushed"):
         ops.assert_no_pending_block_reductions()
-    chain["jobs"].clear()
+    chain.jobs.clear()
     ops.assert_no_pending_block_reductions()
