@@ -916,6 +916,39 @@ int pg_sample_embed_codes(const float* canvas, const float* w, const float* b, c
                           void* stream);
 int pg_vq_lookup(const float* levels, const float* embedding, float* out, int N, int D, int L, int K, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Upsampling lookup over an image of code indices, code_up.hip: F.conv_transpose2d(one_hot(codes), w, stride = f) with
+ * kernel = stride = f as a table lookup with a phase — how an autoregressive prior over the bottom codes of a two-level
+ * VQ-VAE takes the top codes as context (nn.CodeUpsample, ImageGPT.set_condition). levels (N, 1, h, w) dense: a code image
+ * as above (a NEGATIVE level adds nothing); w (K, Cout, f, f), the nn.ConvTranspose2d layout; the output image is
+ * (N, Cout, h f, w f).
+ *   fwd:    out[n, co, i f + a, j f + b] = base[n, co, i f + a, j f + b] + w[code(n, i, j), co, a, b]. base may be NULL (the
+ *           lookup alone) and out may BE base (the conditioned stem in one pass: every element is read and written by one
+ *           thread, once). The weight is packed once per call into (f f, K, Cout) rows in `ws`
+ *           (pg_code_up_fwd_workspace_floats floats). One fp32 addition per element: bit-reproducible.
+ *   wgrad:  dw[k, co, a, b] (+)= sum of dy[n, co, i f + a, j f + b] over the top positions with code(n, i, j) = k.
+ *           Store-and-sum as pg_code_conv_wgrad, over the inverted index of the N h w TOP positions: one wave sums a chunk
+ *           of at most 512 list entries for a group of channels (lanes = channel x phase), a code's chunks are added in
+ *           chunk order. No float atomics, no host synchronisation, capturable; bit-reproducible. Codes that never occur
+ *           receive exact zeros. accumulate != 0 adds the finished sum to dw (a flat-gradient sink) with one fp32 addition
+ *           per element. ws: pg_code_up_wgrad_workspace_floats floats.
+ *   plan:   host only. max_chunks = ceil(N h w / 512), items = K + N h w / 512, as pg_code_conv_wgrad_plan.
+ * pg_sample_cond_codes: the decode-time half. x[co * ld + n] += w[code(n, r / f, c / f), co, r % f, c % f] on the
+ *   (Cout, ld) plane pg_sample_embed_codes writes, for raster position (r, c) of the (h f, w f) image (pos_dev != NULL:
+ *   the position is read from the device and clamped to the image).
+ * K in 2..4096, f in 1..4, any Cout >= 1 (pg_sample_cond_codes: at most 65535), positions and weights below 2^31 (PG_ESHAPE
+ * otherwise); PG_EINVAL for a null operand, a pixel outside the image or a short workspace. No device call before these
+ * checks; the queries return 0 for shapes the launch refuses. */
+size_t pg_code_up_fwd_workspace_floats(int K, int Cout, int f);
+int pg_code_up_fwd(const float* levels, const float* w, const float* base, float* out, int N, int K, int h, int wd, int Cout,
+                   int f, float* ws, size_t ws_floats, void* stream);
+int pg_code_up_plan(int N, int K, int h, int wd, int* max_chunks, int* items);
+size_t pg_code_up_wgrad_workspace_floats(int N, int K, int h, int wd, int Cout, int f);
+int pg_code_up_wgrad(const float* levels, const float* dy, float* dw, int accumulate, int N, int K, int h, int wd, int Cout,
+                     int f, float* ws, size_t ws_floats, void* stream);
+int pg_sample_cond_codes(const float* cond_levels, const float* w, float* x, int N, int K, int h, int wd, int Cout, int f,
+                         int r, int c, int ld, const int* pos_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

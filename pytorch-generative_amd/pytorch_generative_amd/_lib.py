@@ -198,7 +198,13 @@ SIGNATURES = {
     "pg_code_conv_wgrad": (c_i, [c_f] * 4 + [c_i] * 12 + [c_f, c_z, c_s]),
     "pg_sample_embed_codes": (c_i, [c_f] * 5 + [c_i] * 10 + [c_f, c_s]),
     "pg_vq_lookup": (c_i, [c_f] * 3 + [c_i] * 4 + [c_s]),
-    "pg_col_subsample2": (c_i, [c_f, c_f, c_l, c_i, c_s]),
+    "pg_code_up_fwd_workspace_floats": (c_z, [c_i] * 3),
+    "pg_code_up_fwd": (c_i, [c_f] * 4 + [c_i] * 6 + [c_f, c_z, c_s]),
+    "pg_code_up_plan": (c_i, [c_i] * 4 + [c_ip, c_ip]),
+    "pg_code_up_wgrad_workspace_floats": (c_z, [c_i] * 6),
+    "pg_code_up_wgrad": (c_i, [c_f] * 3 + [c_i] * 7 + [c_f, c_z, c_s]),
+    "pg_sample_cond_codes": (c_i, [c_f] * 3 + [c_i] * 9 + [c_f, c_s]),
+    "pg_col_subsample2":(c_i, [c_f, c_f, c_l, c_i, c_s]),
     "pg_col_zero_insert2": (c_i, [c_f, c_f, c_l, c_i, c_s]),
     "pg_copy_rows": (c_i, [c_f, c_f, c_l, c_l, c_l, c_l, c_i, c_s]),
     "pg_comm_unique_id": (c_i, [ctypes.c_char_p]),

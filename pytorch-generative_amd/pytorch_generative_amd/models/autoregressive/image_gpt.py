@@ -87,6 +87,25 @@ class ImageGPT(base.AutoregressiveModel):
             in_channels=n_embedding_channels, out_channels=out_channels, kernel_size=1
         )
 
+    _accepts_condition = True  # AutoregressiveModel.set_condition: a coarser code image as context (nn.CodeUpsample)
+
+    def _check_cond(self, cond, hw):
+        """The condition module for `cond` (None for neither); a ValueError when only one of the two is there or when the
+        sizes do not match the (H, W) image."""
+        mod = getattr(self, "_cond", None)
+        if cond is None and mod is None:
+            return None
+        if mod is None:
+            raise ValueError("ImageGPT: `cond` given, but the model has no condition module (set_condition)")
+        if cond is None:
+            raise ValueError("ImageGPT: the model has a condition module and needs `cond`")
+        if self.input_codes is None:
+            raise ValueError("ImageGPT: a condition module needs input_codes")
+        f = mod.factor
+        if cond.dim() != 4 or cond.shape[1] != 1 or (cond.shape[2] * f, cond.shape[3] * f) != tuple(hw):
+            raise ValueError(f"ImageGPT: cond {tuple(cond.shape)} times the factor {f} is not the image size {tuple(hw)}")
+        return mod
+
     # ---- code-index input (AutoregressiveModel.input_codes) ------------------------------------
     def _position_term(self):
         """W * _pos without the bias, (1, C, H, W): the data-independent half of _input(onehot + _pos) (the convolution is
@@ -95,10 +114,17 @@ class ImageGPT(base.AutoregressiveModel):
         conv = self._input
         return ops.conv2d_taps(self._pos, conv.weight, None, conv._conv_spec(), weight_param=conv.weight)
 
-    def _stem_codes(self, levels):
-        """_input(one_hot(codes) + _pos) for a code image (N, 1, H, W): lookup with the bias + the position term."""
+    def _stem_codes(self, levels, cond=None):
+        """_input(one_hot(codes) + _pos) for a code image (N, 1, H, W): lookup with the bias + the position term; with a
+        condition module, + its lookup of `cond` in the same pass that copies the stem (ops.code_upsample)."""
+        mod = self._check_cond(cond, levels.shape[2:])
         x = self._input.forward_codes(levels, self.input_codes)  # masks the weight in place first
-        return ops.add_broadcast_batch(x, self._position_term())
+        x = ops.add_broadcast_batch(x, self._position_term())
+        if mod is None:
+            return x
+        if torch.is_grad_enabled():
+            return mod(cond, base=x)
+        return ops.code_upsample_(x, cond, mod.weight, mod.factor)  # x is this call's own tensor: added in place
 
     # ---- incremental sampling (SURVEY §8 f2) -------------------------------------------------
     def _decode_route(self, n):
@@ -118,7 +144,7 @@ class ImageGPT(base.AutoregressiveModel):
 
     @base.dense_head
     @torch.no_grad()
-    def sample(self, n_samples=None, conditioned_on=None, *, incremental=True, return_logits=False, route=None):
+    def sample(self, n_samples=None, conditioned_on=None, *, cond=None, incremental=True, return_logits=False, route=None):
         """Same contract as the reference's AutoregressiveModel.sample (models/base.py:97-120: raster
         order, only entries < 0 are drawn, `_sample_fn` called once per pixel on (n, c) logits) — but
         each step evaluates ONLY the current position: the model is causal, so the activations of
@@ -129,11 +155,20 @@ class ImageGPT(base.AutoregressiveModel):
         position carries every sample through all blocks (ops.gpt_decode_step, `_decode_route`). The
         reference (and `incremental=False`) instead runs one full forward per pixel: H*W times the work.
 
+        cond (extension): the coarser code image (n, 1, H / f, W / f) of a model with a condition module (set_condition); n
+        comes from it when neither n_samples nor conditioned_on is given. Every route honours it.
         return_logits (extension): also returns the (H*W, n, c) logits the draws were made from.
         route (measurement aid, tools/gpt_decode_bench.py): "step" runs the one-launch step kernel on a model that would
         take the block kernels. The route that ran is left in `_sample_route` ("blocks", "step" or "full")."""
+        if n_samples is None and conditioned_on is None and cond is not None:
+            n_samples = cond.shape[0]
         canvas = self._start_canvas(n_samples, conditioned_on)
         n, c, h, w = canvas.shape
+        cond_mod = self._check_cond(cond, (h, w))
+        if cond_mod is not None:
+            if cond.shape[0] != n:
+                raise ValueError(f"sample: cond holds {cond.shape[0]} images, the canvas {n}")
+            cond = cond.to(canvas.device).contiguous()
         decode = self._decode_route(n) if incremental else None
         if route is not None and decode is not None:
             if route not in ("blocks", "step") or (route == "blocks" and decode != "blocks"):
@@ -145,7 +180,12 @@ class ImageGPT(base.AutoregressiveModel):
         if decode is None:
             if return_logits:
                 raise ValueError("return_logits needs the incremental sampler")
-            return super().sample(conditioned_on=canvas)
+            if cond_mod is None:
+                return super().sample(conditioned_on=canvas)
+            for row in range(h):  # the reference's loop (models/base.py:97-120) with the context passed to every forward
+                for col in range(w):
+                    self._draw_into(canvas, row, col, self.forward(canvas, cond)[:, :, row, col])
+            return canvas
         lib = _lib.load()
         dev, L = canvas.device, h * w
         canvas = canvas.contiguous()
@@ -181,6 +221,8 @@ class ImageGPT(base.AutoregressiveModel):
                                                conv.weight.data_ptr(), conv.bias.data_ptr(), x.data_ptr(),
                                                n, c, h, w, emb, kh, kw, 0, 0, ld, pos_dev.data_ptr(), st),
                            "pg_sample_embed")
+            if cond_mod is not None:
+                cond_mod.add_position_(x, cond, pos_dev, ld)
             if decode == "step":  # every block of the position in one launch, in place
                 cur = ops.gpt_decode_step(x, pack, k_cache, v_cache, pos_dev, heads=attn0._n_heads,
                                           strict=int(attn0._mask_center), eps=blocks[0]._ln1.eps)
@@ -224,10 +266,12 @@ class ImageGPT(base.AutoregressiveModel):
             return canvas, torch.stack(all_logits)
         return canvas
 
-    def forward(self, x):
+    def forward(self, x, cond=None):
         img, blocks, grad = x, list(self._transformer), torch.is_grad_enabled()
         # the two ends on their own kernels (gpt_ends.hip) where the model has the BASELINE shape; PG_FUSE_ENDS=0 = generic operators
         codes = self.input_codes is not None  # the stem as a table lookup: the fused stem is not taken
+        if not codes:
+            self._check_cond(cond, img.shape[2:])  # a cond or a condition module without input_codes raises
         fuse_stem = not codes and ops.gpt_stem_supported(img, self._pos, self._input)
         # The stem's backward runs last: a trainable fused stem flushes the chain on its only path, whichever blocks queued rows
         stem_flushes = fuse_stem and grad and any(p.requires_grad for p in (self._pos, self._input.weight, self._input.bias))
@@ -235,7 +279,7 @@ class ImageGPT(base.AutoregressiveModel):
             x0_grad = stem_flushes
             probe = torch.empty(1, self._input.weight.shape[0], img.shape[2], img.shape[3], device="meta")
         elif codes:
-            x = probe = self._stem_codes(img)
+            x = probe = self._stem_codes(img, cond)
             x0_grad = x.requires_grad
         else:
             x = probe = self._input(ops.add_broadcast_batch(img, self._pos))

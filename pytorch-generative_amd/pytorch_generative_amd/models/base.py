@@ -107,6 +107,24 @@ class AutoregressiveModel(GenerativeModel):
         if self.input_codes is not None:
             raise ValueError(f"{type(self).__name__} does not support input_codes (ImageGPT and PixelCNN do)")
 
+    # A condition module (extension; nn.CodeUpsample): forward(x, cond=...) and sample(cond=...) take a second, coarser code
+    # image as context. It is the submodule `_cond`, so state_dict gains `_cond.weight` — only then: a model that never calls
+    # set_condition keeps the reference's keys, signatures and bits. ImageGPT with `input_codes` takes it; the others raise.
+    _accepts_condition = False
+
+    def set_condition(self, module):
+        """Registers `module` as the condition module `_cond` (before the optimizer is built: its weight is a parameter);
+        None removes it."""
+        if module is None:
+            if "_cond" in self._modules:
+                del self._modules["_cond"]
+            return
+        if not self._accepts_condition:
+            raise ValueError(f"{type(self).__name__} does not support a condition module (ImageGPT with input_codes does)")
+        if self.input_codes is None:
+            raise ValueError(f"{type(self).__name__}: a condition module needs input_codes (set it first)")
+        self.add_module("_cond", module)
+
     def _logits(self, features, conv, *, in_act=None, pre_ln=None, **dense_kw):
         """The model's last 1x1 convolution: deferred when `defer_head` is set and no RowDecode is open, else as always."""
         from pytorch_generative_amd import ops

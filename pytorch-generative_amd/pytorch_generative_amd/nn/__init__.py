@@ -3,6 +3,7 @@
 from pytorch_generative_amd.nn.attention import CausalAttention, LinearCausalAttention, image_positional_encoding
 from pytorch_generative_amd.nn.convolution import (
     CausalConv2d,
+    CodeUpsample,
     Conv2d,
     ConvTranspose2d,
     GatedActivation,
@@ -17,6 +18,7 @@ __all__ = [
     "image_positional_encoding",
     "CausalConv2d",
     "Conv2d",
+    "CodeUpsample",
     "ConvTranspose2d",
     "GatedActivation",
     "GatedConv",

@@ -425,3 +425,32 @@ class NCHWLayerNorm(nn.LayerNorm):
         if skip:
             return ops.nchw_layernorm_skip(x, self.weight, self.bias, self.eps)
         return ops.nchw_layernorm(x, self.weight, self.bias, self.eps)
+
+
+class CodeUpsample(nn.Module):
+    """A coarser code image as context for an autoregressive model over a finer one: for codes (N, 1, h, w) at the levels
+    j / (n_codes - 1), base + F.conv_transpose2d(one_hot(codes), weight, stride=factor) with kernel = stride = factor — one
+    learned (out_channels, factor, factor) patch per code — as a table lookup (ops.code_upsample). The weight starts at
+    zero, as ImageGPT's `_pos` does: a fresh conditional model computes what the unconditional one computes. No bias: the
+    stem it is added to has one."""
+
+    def __init__(self, n_codes, out_channels, factor):
+        super().__init__()
+        n_codes, out_channels, factor = int(n_codes), int(out_channels), int(factor)
+        if not 2 <= n_codes <= ops.CODE_MAX_CODES:
+            raise ValueError(f"CodeUpsample: n_codes = {n_codes} outside 2..{ops.CODE_MAX_CODES}")
+        if not 1 <= factor <= ops.CODE_UP_MAX_FACTOR or out_channels < 1:
+            raise ValueError(f"CodeUpsample: factor = {factor} outside 1..{ops.CODE_UP_MAX_FACTOR} or no output channels")
+        self.n_codes, self.out_channels, self.factor = n_codes, out_channels, factor
+        self.weight = nn.Parameter(torch.zeros(n_codes, out_channels, factor, factor))
+
+    def extra_repr(self):
+        return f"n_codes={self.n_codes}, out_channels={self.out_channels}, factor={self.factor}"
+
+    def forward(self, levels, base=None):
+        return ops.code_upsample(levels, self.weight, self.factor, base=base, weight_param=self.weight)
+
+    def add_position_(self, x_plane, levels, pos_dev, ld):
+        """The decode call: adds the current raster position's column (position in the int32 device scalar `pos_dev`) to the
+        (out_channels, ld) plane of the incremental sampler, in place."""
+        return ops.sample_cond_codes_(x_plane, levels, self.weight, self.factor, ld=ld, pos_dev=pos_dev)

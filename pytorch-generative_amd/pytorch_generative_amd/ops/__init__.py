@@ -88,6 +88,13 @@ from pytorch_generative_amd.ops.code_conv import (  # noqa: F401
     vq_lookup,
     codes_to_levels,
 )
+from pytorch_generative_amd.ops.code_up import (  # noqa: F401
+    CODE_UP_MAX_FACTOR,
+    code_upsample,
+    code_upsample_,
+    code_up_plan,
+    sample_cond_codes_,
+)
 from pytorch_generative_amd.ops.gpt_block import (  # noqa: F401
     FUSE_MLP,
     mlp_gelu_supported,

@@ -46,9 +46,10 @@ def _device(n_gpus, device_id):
 
 
 def run(build_model, *, loaders, loss_fn, lr, lr_decay=1.0, n_epochs, batch_size, log_dir, n_gpus,
-        device_id, debug_loader, defer_head=False):
+        device_id, debug_loader, defer_head=False, trainer_cls=None):
     """Builds everything a recipe names and trains for `n_epochs`; returns the Trainer. defer_head=True sets the attribute
-    of that name on the model (autoregressive models with a categorical head: the head runs inside the loss kernels)."""
+    of that name on the model (autoregressive models with a categorical head: the head runs inside the loss kernels).
+    trainer_cls: a Trainer subclass with the same constructor (trainer.ConditionalTrainer), default trainer.Trainer."""
     device = _device(n_gpus, device_id)
     if debug_loader is not None:
         train_loader = test_loader = debug_loader
@@ -58,8 +59,8 @@ def run(build_model, *, loaders, loss_fn, lr, lr_decay=1.0, n_epochs, batch_size
     if defer_head:
         model.defer_head = True
     optimizer = optim.FlatAdam(model.parameters(), lr=lr, lr_decay=lr_decay)
-    t = trainer.Trainer(model=model, loss_fn=loss_fn, optimizer=optimizer, train_loader=train_loader,
-                        eval_loader=test_loader, log_dir=log_dir, n_gpus=n_gpus, device_id=device_id)
+    t = (trainer_cls or trainer.Trainer)(model=model, loss_fn=loss_fn, optimizer=optimizer, train_loader=train_loader,
+                                         eval_loader=test_loader, log_dir=log_dir, n_gpus=n_gpus, device_id=device_id)
     t.interleaved_train_and_eval(n_epochs)
     return t
 
@@ -122,3 +123,34 @@ def code_loaders(vqvae, loaders):
     VQ-VAE in eval mode on its device — code images (N, 1, h, w) at the levels j / (n_embeddings - 1), the input of a model
     with `input_codes` and the target of `categorical_loss`."""
     return tuple(_CodeLoader(vqvae, loader) for loader in loaders)
+
+
+class _CodeLoader2:
+    """A loader whose (x, y) batches become a level of vqvae2.encode_codes(x): "top" -> (top, y), "bottom" -> (bottom, top),
+    the training data of the two priors of a VQ-VAE-2 (the second is trained by trainer.ConditionalTrainer)."""
+
+    def __init__(self, vqvae2, loader, level):
+        if level not in ("top", "bottom"):
+            raise ValueError(f"code_loaders_2: level {level!r} is neither 'top' nor 'bottom'")
+        self._vqvae, self._loader, self._level = vqvae2, loader, level
+
+    def __len__(self):
+        return len(self._loader)
+
+    def __iter__(self):
+        vqvae = self._vqvae
+        device = vqvae.device
+        for x, y in self._loader:
+            was_training = vqvae.training
+            vqvae.eval()  # frozen
+            try:
+                top, bottom = vqvae.encode_codes(x.to(device))
+            finally:
+                vqvae.train(was_training)
+            yield (top, y) if self._level == "top" else (bottom, top)
+
+
+def code_loaders_2(vqvae2, loaders, level):
+    """code_loaders for a two-level VQ-VAE: level "top" yields (top codes, y), level "bottom" yields (bottom codes, top
+    codes) — the input and the context of the conditional prior."""
+    return tuple(_CodeLoader2(vqvae2, loader, level) for loader in loaders)

@@ -393,3 +393,18 @@ class Trainer:
             if self._epoch % self.sample_epochs == 0:
                 self.sample_one_batch()
         self._log.close()
+
+
+class ConditionalTrainer(Trainer):
+    """Trains a model that takes the batch's second element as context: model(x, cond=y) (ImageGPT.set_condition; recipes.
+    code_loaders_2 yields (bottom codes, top codes)). `y` travels to the device and into the captured step's static buffers
+    like any label, and the hooks hold no host logic, so the step is captured as in Trainer (graph=True means "force")."""
+
+    def __init__(self, *args, graph=True, **kwargs):
+        super().__init__(*args, graph="force" if graph is True else graph, **kwargs)
+
+    def train_one_batch(self, x, y):
+        return self.loss_fn(x, y, self.model(x, cond=y))
+
+    def eval_one_batch(self, x, y):
+        return self.loss_fn(x, y, self.model(x, cond=y))
