@@ -224,13 +224,15 @@ int pg_nchw_layernorm_bwd_res(const float* x, const float* gamma, const float* m
  * CausalAttention accepts any embed / head split: the Python host (ops.causal_attention) zero-pads other head dims
  * and sequence lengths to the next instantiated size — exact, see its docstring.
  * pg_causal_attn_bwd: dk = 4 with dv in {4, 16, 32} runs ONE fused kernel whose dq is summed with fp32 atomics
- * (run-to-run last-bit differences); pg_attn_fused_bwd(0) selects the bit-reproducible two-kernel backward.
+ * (run-to-run last-bit differences) while that kernel takes the shape: dv = 4 up to L = 1792 (its LDS planes), dv = 16 / 32 for
+ * L % 16 == 0 with 16-byte aligned planes; otherwise, and after pg_attn_fused_bwd(0), the bit-reproducible two-kernel backward
+ * runs. pg_attn_route tells which.
  * ------------------------------------------------------------------------------------- */
 int pg_causal_attn_fwd(const float* q, const float* k, const float* v, float* o, float* lse2,
                        int N, int heads, int L, int dk, int dv, long q_bs, long k_bs, long v_bs,
                        long o_bs, int strict, void* stream);
-/* dq/dk/dv written (not accumulated). delta: (N, heads, L) workspace. For d_k = d_v = 4 this is ONE
- * fused launch (attention_mfma.hip attn_bwd_m44_kernel: S, dP and exp2 evaluated once per pair; delta
+/* dq/dk/dv written (not accumulated). delta: (N, heads, L) workspace. For d_k = d_v = 4 up to L = 1792 this
+ * is ONE fused launch (attention_mfma.hip attn_bwd_m44_kernel: S, dP and exp2 evaluated once per pair; delta
  * is then not written); otherwise the two launches below. */
 int pg_causal_attn_bwd(const float* q, const float* k, const float* v, const float* o,
                        const float* d_o, const float* lse2, float* delta, float* dq, float* dk,
@@ -266,6 +268,46 @@ int pg_attn_fused_bwd(int enable);
  * shape to the VALU kernels), PG_EINVAL for bad arguments. */
 int pg_attn_block_plan(int which, int L, int waves, int* out_blk, int* out_q0, int* out_ngrp, int* out_wave,
                        int* out_cost);
+
+/* Host only, launches nothing: which kernel family a pg_causal_attn_* launch of this problem takes and how it is laid out — the
+ * answer of the one route function the launches themselves read (csrc/attention.hip: attn_route, which asks attention_mfma.hip and
+ * attention_k4.hip in the launch's order). which: 0 forward, 1 dQ, 2 dK/dV, 3 the fused-backward request pg_causal_attn_bwd makes
+ * first. flags: PG_ATTN_R_*, what the launch reads from its pointers and strides (a plane = the first image's first channel of the
+ * tensor; a batch stride counts floats). The fused-backward switch (pg_attn_fused_bwd) is read, never changed. Fills
+ * out[0 .. PG_ATTN_ROUTE_INTS):
+ *   [0] family: PG_ATTN_FAM_VALU (attention.hip row-owner kernels), PG_ATTN_FAM_M44 (attention_mfma.hip, d_k = d_v = 4),
+ *       PG_ATTN_FAM_K4 (attention_k4.hip); for which = 3 also PG_ATTN_FAM_DECLINED: no fused kernel takes it, the dQ and dK/dV
+ *       launches follow (route them with which = 1, 2)
+ *   [1] the fused-backward switch as found (0 / 1)
+ *   [2] [3] [4] template instantiation: VALU Cfg<DK, DV> (head dims padded up), 0; k4 <DKT, DVT, QB> (d_k 4 -> DKT 1, else d_k / 4;
+ *       DVT = d_v / 16; QB = 16-row groups per block, the fused k4 backward: key groups per block); M44 4, 4, 0
+ *   [5] [6] [7] grid x, y, z   [8] block size   [9] dynamic LDS bytes
+ *   [10] VALU: 64-row blocks per workgroup (<= 16)   [11] VALU: rows per LDS tile, kt (which 0, 1) resp. kt2 (which 2)
+ *   [12] VALU: LDS tiles a sequence of L rows spans, ceil(L / [11])
+ *   [13] waves per workgroup   [14] M44: LDS plane stride lp in floats   [15] M44: float4 stores (L % 4 == 0, planes aligned)
+ *   [16] M44 variant: which 2: 1 = bf16x3 score tile; which 3: the kernel's compile-time plane stride (848, 1040, or 0 = any)
+ * Fields that do not apply to the family are 0. d_k = d_v = 4 stays on the matrix cores only while the kernel's LDS planes fit 160 KB,
+ * kernel by kernel: fused backward L <= 1792, dQ L <= 1984, dK/dV L <= 2240, forward L <= 3392 (L rounded up to 64); beyond, that
+ * kernel alone runs on the VALU family, so one forward / backward may mix the two (they share lse2 and delta).
+ * Returns 0, or the status the launch would return (PG_ESHAPE: no kernel instantiates the head dims at this L; out holds
+ * [0] = PG_ATTN_FAM_NONE, [1] and zeros; head dims above 64: out untouched); PG_EINVAL for a null pointer, a short array, a bad `which` or a non-positive dimension. */
+#define PG_ATTN_R_QKV_MISALIGNED 1     /* q, k or v is not 16-byte aligned */
+#define PG_ATTN_R_O_MISALIGNED 2       /* the forward's o is not 16-byte aligned */
+#define PG_ATTN_R_GRADIN_MISALIGNED 4  /* d_o, lse2 or delta of a backward launch is not 16-byte aligned */
+#define PG_ATTN_R_DQ_MISALIGNED 8      /* dq is not 16-byte aligned */
+#define PG_ATTN_R_DKV_MISALIGNED 16    /* dk or dv is not 16-byte aligned */
+#define PG_ATTN_R_QKV_STRIDE 32        /* q_bs, k_bs or v_bs is not a multiple of 4 */
+#define PG_ATTN_R_O_STRIDE 64          /* o_bs is not a multiple of 4 */
+#define PG_ATTN_R_DO_STRIDE 128        /* do_bs is not a multiple of 4 */
+#define PG_ATTN_R_DQ_STRIDE 256        /* dq_bs is not a multiple of 4 */
+#define PG_ATTN_R_DKV_STRIDE 512       /* dk_bs or dv_bs is not a multiple of 4 */
+#define PG_ATTN_FAM_VALU 0
+#define PG_ATTN_FAM_M44 1
+#define PG_ATTN_FAM_K4 2
+#define PG_ATTN_FAM_DECLINED (-1)
+#define PG_ATTN_FAM_NONE (-2)
+#define PG_ATTN_ROUTE_INTS 17
+int pg_attn_route(int which, int N, int heads, int L, int dk, int dv, int flags, int* out, int n_out);
 
 /* ---------------------------------------------------------------------------------------
  * Linear causal attention (O(L) memory).  nn/attention.py:168-195 (_UnnormalizedLinearCausalAttention

@@ -492,21 +492,26 @@ __global__ void __launch_bounds__(512) attn_bwd_dkv_kernel(const AttnArgs a) {
 enum { K_FWD = PG_ATTN_FWD, K_DQ = PG_ATTN_DQ, K_DKV = PG_ATTN_DKV };
 
 template <int DK, int DV>
-void launch_one(int which, const AttnArgs& a, dim3 grid, dim3 block, hipStream_t st) {
-  using C = Cfg<DK, DV>;
-  // tile rows: everything the workgroup streams if it fits ~64 KB of LDS, else 64-row multiples
-  AttnArgs b = a;
-  const int rows = ((b.L + 63) / 64) * 64;
-  const int budget = 16384;  // floats
-  int kt = (budget / C::RS / 64) * 64, kt2 = (budget / C::RS2 / 64) * 64;
-  b.kt = kt < 64 ? 64 : (kt > rows ? rows : kt);
-  b.kt2 = kt2 < 64 ? 64 : (kt2 > rows ? rows : kt2);
+void launch_one(int which, const AttnArgs& a, dim3 grid, dim3 block, size_t lds, hipStream_t st) {
   if (which == K_FWD)
-    hipLaunchKernelGGL((attn_fwd_kernel<DK, DV>), grid, block, (size_t)b.kt * C::RS * sizeof(float), st, b);
+    hipLaunchKernelGGL((attn_fwd_kernel<DK, DV>), grid, block, lds, st, a);
   else if (which == K_DQ)
-    hipLaunchKernelGGL((attn_bwd_dq_kernel<DK, DV>), grid, block, (size_t)b.kt * C::RS * sizeof(float), st, b);
+    hipLaunchKernelGGL((attn_bwd_dq_kernel<DK, DV>), grid, block, lds, st, a);
   else
-    hipLaunchKernelGGL((attn_bwd_dkv_kernel<DK, DV>), grid, block, (size_t)b.kt2 * C::RS2 * sizeof(float), st, b);
+    hipLaunchKernelGGL((attn_bwd_dkv_kernel<DK, DV>), grid, block, lds, st, a);
+}
+
+// tile rows: everything the workgroup streams if it fits ~64 KB of LDS, else 64-row multiples
+template <int DK, int DV>
+void valu_tiles(int which, int L, PgAttnRoute& r) {
+  using C = Cfg<DK, DV>;
+  const int rows = ((L + 63) / 64) * 64;
+  const int budget = 16384;  // floats
+  const int kt = (budget / C::RS / 64) * 64, kt2 = (budget / C::RS2 / 64) * 64;
+  r.DK = DK; r.DV = DV;
+  r.kt = kt < 64 ? 64 : (kt > rows ? rows : kt);
+  r.kt2 = kt2 < 64 ? 64 : (kt2 > rows ? rows : kt2);
+  r.lds = (int)(which == K_DKV ? (size_t)r.kt2 * C::RS2 * sizeof(float) : (size_t)r.kt * C::RS * sizeof(float));
 }
 
 // Instantiated head dims of these VALU kernels (padded up): d_k <= 4 with d_v <= 32, d_k <= 16 with d_v <= 16 — the
@@ -514,29 +519,49 @@ void launch_one(int which, const AttnArgs& a, dim3 grid, dim3 block, hipStream_t
 // lane, which beyond these sizes no longer fits the register file (round 3 shipped <64, 64> with 1 755 spilled
 // registers). Larger head dims run on the matrix-core kernels of attention_k4.hip (multiples of 16, L % 16 == 0);
 // ops.causal_attention zero-pads other shapes to the next such size.
-template <int DK>
-int launch_dv(int which, const AttnArgs& a, dim3 grid, dim3 block, hipStream_t st) {
-  const int dv = a.dv_dim;
-  if (dv <= 4) launch_one<DK, 4>(which, a, grid, block, st);
-  else if (dv <= 16) launch_one<DK, 16>(which, a, grid, block, st);
-  else if (DK == 4 && dv <= 32) launch_one<4, 32>(which, a, grid, block, st);
-  else return PG_ESHAPE;
+// Returns 0 with r filled in, PG_ESHAPE (r untouched) for head dims beyond these.
+int valu_route(int which, int N, int heads, int L, int dk, int dv, PgAttnRoute& r) {
+  if (dk <= 4) {
+    if (dv <= 4) valu_tiles<4, 4>(which, L, r);
+    else if (dv <= 16) valu_tiles<4, 16>(which, L, r);
+    else if (dv <= 32) valu_tiles<4, 32>(which, L, r);
+    else return PG_ESHAPE;
+  } else if (dk <= 16) {
+    if (dv <= 4) valu_tiles<16, 4>(which, L, r);
+    else if (dv <= 16) valu_tiles<16, 16>(which, L, r);
+    else return PG_ESHAPE;
+  } else {
+    return PG_ESHAPE;
+  }
+  // a workgroup owns up to 16 consecutive 64-row blocks, handed to its waves in balanced pairs;
+  // small L -> one workgroup per (n, head)
+  const int NB = (L + 63) / 64;
+  const int bpw = NB < 16 ? NB : 16;
+  r.family = PG_ATTN_FAM_VALU;
+  r.QB = 0;
+  r.bpw = bpw;
+  r.waves = (bpw + 1) / 2;
+  r.grid[0] = (NB + bpw - 1) / bpw; r.grid[1] = heads; r.grid[2] = N;
+  r.block = 64 * r.waves;
   return 0;
 }
 
-int launch_attn(int which, AttnArgs& a, hipStream_t st) {
-  // a workgroup owns up to 16 consecutive 64-row blocks, handed to its waves in balanced pairs;
-  // small L -> one workgroup per (n, head)
-  const int NB = (a.L + 63) / 64;
-  const int bpw = NB < 16 ? NB : 16;
-  a.blocks_per_wg = bpw;
-  const int nwaves = (bpw + 1) / 2;
-  dim3 grid((unsigned)((NB + bpw - 1) / bpw), (unsigned)a.heads, (unsigned)a.N);
-  dim3 block((unsigned)(64 * nwaves));
-  const int dk = a.dk_dim;
-  if (dk <= 4) return launch_dv<4>(which, a, grid, block, st);
-  if (dk <= 16) return launch_dv<16>(which, a, grid, block, st);
-  return PG_ESHAPE;
+void launch_attn(int which, const AttnArgs& a0, const PgAttnRoute& r, hipStream_t st) {
+  AttnArgs a = a0;
+  a.blocks_per_wg = r.bpw;
+  a.kt = r.kt;
+  a.kt2 = r.kt2;
+  const dim3 grid((unsigned)r.grid[0], (unsigned)r.grid[1], (unsigned)r.grid[2]);
+  const dim3 block((unsigned)r.block);
+  const size_t lds = (size_t)r.lds;
+  if (r.DK == 4) {
+    if (r.DV == 4) launch_one<4, 4>(which, a, grid, block, lds, st);
+    else if (r.DV == 16) launch_one<4, 16>(which, a, grid, block, lds, st);
+    else launch_one<4, 32>(which, a, grid, block, lds, st);
+  } else {
+    if (r.DV == 4) launch_one<16, 4>(which, a, grid, block, lds, st);
+    else launch_one<16, 16>(which, a, grid, block, lds, st);
+  }
 }
 
 int check_dims(const char* who, int N, int heads, int L, int dk, int dv, int strict) {
@@ -556,13 +581,54 @@ static bool use_mfma_attention() {
   return on;
 }
 
-// launch `which` on whichever kernel family covers the shape
-static int launch_any(int which, AttnArgs& a, hipStream_t st) {
+// THE route: which kernel family takes `which` for this shape and these pointer / stride properties, and its launch geometry.
+// which = PG_ATTN_BWD is the fused-backward request: family PG_ATTN_FAM_DECLINED means the dQ and dK/dV launches follow.
+// Returns 0, or PG_ESHAPE when no family instantiates the head dims at this L (r.family = PG_ATTN_FAM_NONE).
+static int attn_route(int which, int N, int heads, int L, int dk, int dv, int flags, PgAttnRoute& r) {
+  r = PgAttnRoute{};
+  r.fused_on = pg_attn_fused_bwd(-1);
+  if (which == PG_ATTN_BWD) {
+    if (use_mfma_attention() && pg_attn_mfma_route(which, N, heads, L, dk, dv, flags, r) == 1) return 0;
+    r.family = PG_ATTN_FAM_DECLINED;
+    return 0;
+  }
   // ab library: PG_ATTN_MFMA_MASK = bit mask of the kernels allowed on the matrix-core family (1 forward, 2 dQ, 4 dK/dV)
   static const int mask = PG_AB_INT("PG_ATTN_MFMA_MASK", 7);
   const int bit = which == K_FWD ? 1 : (which == K_DQ ? 2 : 4);
-  if (use_mfma_attention() && (mask & bit) && pg_attn_mfma_launch(which, a, st) == 1) return 0;
-  return launch_attn(which, a, st);
+  if (use_mfma_attention() && (mask & bit) && pg_attn_mfma_route(which, N, heads, L, dk, dv, flags, r) == 1) return 0;
+  const int rc = valu_route(which, N, heads, L, dk, dv, r);
+  if (rc) r.family = PG_ATTN_FAM_NONE;
+  return rc;
+}
+
+static void launch_route(int which, const AttnArgs& a, const PgAttnRoute& r, hipStream_t st) {
+  if (r.family == PG_ATTN_FAM_M44) pg_attn_mfma_launch(which, a, r, st);
+  else if (r.family == PG_ATTN_FAM_K4) pg_attn_k4_launch(which, a, r, st);
+  else launch_attn(which, a, r, st);
+}
+
+// launch `which` on whichever kernel family the route names
+static int launch_any(int which, const AttnArgs& a, hipStream_t st) {
+  PgAttnRoute r;
+  const int rc = attn_route(which, a.N, a.heads, a.L, a.dk_dim, a.dv_dim, pg_attn_route_flags(a), r);
+  if (rc) return rc;
+  launch_route(which, a, r, st);
+  return 0;
+}
+
+PG_EXPORT int pg_attn_route(int which, int N, int heads, int L, int dk, int dv, int flags, int* out, int n_out) {
+  PG_REQUIRE(out && n_out >= PG_ATTN_ROUTE_INTS, PG_EINVAL, "pg_attn_route: null or short output array");
+  PG_REQUIRE(which >= PG_ATTN_FWD && which <= PG_ATTN_BWD, PG_EINVAL, "pg_attn_route: which must be 0..3");
+  int rc = check_dims("pg_attn_route", N, heads, L, dk, dv, 0);
+  if (rc) return rc;
+  PgAttnRoute r;
+  rc = attn_route(which, N, heads, L, dk, dv, flags, r);
+  const int tile = r.family == PG_ATTN_FAM_VALU ? (which == K_DKV ? r.kt2 : r.kt) : 0;
+  const int vals[PG_ATTN_ROUTE_INTS] = {r.family, r.fused_on, r.DK, r.DV, r.QB, r.grid[0], r.grid[1], r.grid[2], r.block,
+                                        r.lds, r.bpw, tile, tile ? (L + tile - 1) / tile : 0, r.waves, r.lp, r.vec, r.variant};
+  for (int i = 0; i < PG_ATTN_ROUTE_INTS; ++i) out[i] = vals[i];
+  PG_REQUIRE(rc == 0, rc, "pg_attn_route: head dims (%d, %d) at L = %d are not instantiated: pad them to multiples of 16 and L to a multiple of 16 (ops.causal_attention does)", dk, dv, L);
+  return 0;
 }
 
 PG_EXPORT int pg_causal_attn_fwd(const float* q, const float* k, const float* v, float* o,
@@ -600,9 +666,14 @@ int attn_bwd_impl(int which_mask, const float* q, const float* k, const float* v
   a.dq_bs = dq_bs; a.dk_bs = dk_bs; a.dv_bs = dv_bs;
   a.scale = 1.f / sqrtf((float)dk_dim);
   a.scale2 = a.scale * 1.44269504088896340736f;
-  if (which_mask == 3 && use_mfma_attention() && pg_attn_mfma_launch(PG_ATTN_BWD, a, (hipStream_t)stream) == 1) {
-    PG_LAUNCH_CHECK("pg_causal_attn_bwd(fused)");  // dQ, dK, dV in one pass (attention_mfma.hip)
-    return 0;
+  if (which_mask == 3) {
+    PgAttnRoute r;
+    attn_route(PG_ATTN_BWD, N, heads, L, dk_dim, dv_dim, pg_attn_route_flags(a), r);
+    if (r.family != PG_ATTN_FAM_DECLINED) {
+      launch_route(PG_ATTN_BWD, a, r, (hipStream_t)stream);
+      PG_LAUNCH_CHECK("pg_causal_attn_bwd(fused)");  // dQ, dK, dV in one pass (attention_mfma.hip / attention_k4.hip)
+      return 0;
+    }
   }
   if (which_mask & 1) {
     rc = launch_any(K_DQ, a, (hipStream_t)stream);

@@ -697,40 +697,42 @@ void k4_launch(int which, const PgAttnArgs& a, dim3 grid, hipStream_t st) {
     hipLaunchKernelGGL((attn_dkv_k4_kernel<DKT, DVT, QB>), grid, dim3(64), 0, st, a);
 }
 
-bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 }  // namespace
 
-// Returns 1 if these kernels took the launch: d_k = 4 with d_v in {16, 32, 64}, or d_k in {16, 32, 64} with d_v in
-// {16, 32, 64}; L % 16 == 0; 16-byte aligned planes; else 0. (Round 4: everything beyond (4, 16 / 32) and (32, 32)
-// — the shapes that used to run on VALU kernels spilling up to 1 755 registers.)
-int pg_attn_k4_launch(int which, const PgAttnArgs& a, hipStream_t st) {
-  const int dk = a.dk_dim, dv = a.dv_dim;
+// The shapes these kernels take: d_k = 4 with d_v in {16, 32, 64}, or d_k in {16, 32, 64} with d_v in {16, 32, 64}; L % 16 == 0;
+// 16-byte aligned planes and batch strides that are multiples of 4 floats. (Round 4: everything beyond (4, 16 / 32) and (32, 32)
+// — the shapes that used to run on VALU kernels spilling up to 1 755 registers.) Returns 1 with the instantiation and the grid
+// in r, else 0.
+int pg_attn_k4_route(int which, int N, int heads, int L, int dk, int dv, int flags, PgAttnRoute& r) {
   const bool dv_ok = dv == 16 || dv == 32 || dv == 64;
   const bool small_k = dk == 4 && dv_ok;
   const bool big_k = (dk == 16 || dk == 32 || dk == 64) && dv_ok;
-  if (!(small_k || big_k) || (a.L % 16) != 0 || a.L < 16) return 0;
+  if (!(small_k || big_k) || (L % 16) != 0 || L < 16) return 0;
   if (which == PG_ATTN_BWD && !(small_k && dv <= 32)) return 0;  // the fused backward exists for d_k = 4, d_v = 16 / 32
   if (which > PG_ATTN_BWD) return 0;
-  if ((a.q_bs | a.k_bs | a.v_bs | a.o_bs) % 4 != 0) return 0;
-  if (!al16(a.k) || !al16(a.v) || !al16(a.q)) return 0;
+  if (flags & (PG_ATTN_R_QKV_STRIDE | PG_ATTN_R_O_STRIDE)) return 0;
+  if (flags & PG_ATTN_R_QKV_MISALIGNED) return 0;
   if (which != PG_ATTN_FWD) {
-    if ((a.do_bs | a.dq_bs | a.dk_bs | a.dv_bs) % 4 != 0) return 0;
-    if (!al16(a.d_o) || !al16(a.lse2_in) || !al16(a.delta)) return 0;
+    if (flags & (PG_ATTN_R_DO_STRIDE | PG_ATTN_R_DQ_STRIDE | PG_ATTN_R_DKV_STRIDE)) return 0;
+    if (flags & PG_ATTN_R_GRADIN_MISALIGNED) return 0;
   }
-  const int units = a.N * a.heads;
+  const int units = N * heads;
+  PgAttnRoute t = r;
+  t.family = PG_ATTN_FAM_K4;
+  t.DK = dk == 4 ? 1 : dk / 4;
+  t.DV = dv / 16;
+  t.grid[1] = t.grid[2] = 1;
+  t.block = 64;
+  t.waves = 1;
   if (which == PG_ATTN_BWD) {
     // delta pre-pass (which also zeroes dq: the fused kernel deposits with atomics), then the fused kernel on 32-key blocks
-    if ((a.dq_bs % 4) != 0 || (reinterpret_cast<uintptr_t>(a.dq) & 15) != 0) return 0;
-    const dim3 dgrid((unsigned)((a.L + 255) / 256), (unsigned)units);
-    if (dv == 32) hipLaunchKernelGGL((attn_delta_k4_kernel<2>), dgrid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((attn_delta_k4_kernel<1>), dgrid, dim3(256), 0, st, a);
+    if (flags & PG_ATTN_R_DQ_MISALIGNED) return 0;
     constexpr int FQB = 2;
-    const int NBf = (a.L + 16 * FQB - 1) / (16 * FQB);
+    const int NBf = (L + 16 * FQB - 1) / (16 * FQB);
     const int npf = (NBf + 1) / 2;
-    const dim3 fgrid((unsigned)(((units + 63) / 64) * 64 * npf));
-    if (dv == 32) hipLaunchKernelGGL((attn_bwd_k4_kernel<2, FQB>), fgrid, dim3(64), 0, st, a);
-    else hipLaunchKernelGGL((attn_bwd_k4_kernel<1, FQB>), fgrid, dim3(64), 0, st, a);
+    t.QB = FQB;
+    t.grid[0] = ((units + 63) / 64) * 64 * npf;
+    r = t;
     return 1;
   }
   // A lone wave keeps its SIMD's matrix pipe ~50 % busy (score -> exp -> P.V is one dependent chain
@@ -741,34 +743,49 @@ int pg_attn_k4_launch(int which, const PgAttnArgs& a, hipStream_t st) {
   static const int force_qb = PG_AB_INT("PG_ATTN_K4_QB", 0);
   int qb;
   if (small_k && dv <= 32) {
-    qb = ((long)units * (((a.L + 63) / 64 + 1) / 2) >= 3 * 1024) ? 4 : 2;
+    qb = ((long)units * (((L + 63) / 64 + 1) / 2) >= 3 * 1024) ? 4 : 2;
     if (force_qb == 2 || force_qb == 4) qb = force_qb;
   } else if (small_k) {
     qb = 2;
   } else {
     qb = (dk == 64 || dv == 64) ? 1 : 2;
   }
-  const int NB = (a.L + 16 * qb - 1) / (16 * qb);
+  const int NB = (L + 16 * qb - 1) / (16 * qb);
   const int npair = (NB + 1) / 2;
   // units in groups of 64 (8 per XCD); every group has 8 * 8 * npair workgroups
   const int groups = (units + 63) / 64;
-  dim3 grid((unsigned)(groups * 64 * npair));
-  if (small_k) {
-    if (dv == 64) k4_launch<1, 4, 2>(which, a, grid, st);
-    else if (dv == 32) { if (qb == 4) k4_launch<1, 2, 4>(which, a, grid, st); else k4_launch<1, 2, 2>(which, a, grid, st); }
-    else { if (qb == 4) k4_launch<1, 1, 4>(which, a, grid, st); else k4_launch<1, 1, 2>(which, a, grid, st); }
-  } else if (dk == 16) {
-    if (dv == 16) k4_launch<4, 1, 2>(which, a, grid, st);
-    else if (dv == 32) k4_launch<4, 2, 2>(which, a, grid, st);
-    else k4_launch<4, 4, 1>(which, a, grid, st);
-  } else if (dk == 32) {
-    if (dv == 16) k4_launch<8, 1, 2>(which, a, grid, st);
-    else if (dv == 32) k4_launch<8, 2, 2>(which, a, grid, st);
-    else k4_launch<8, 4, 1>(which, a, grid, st);
-  } else {
-    if (dv == 16) k4_launch<16, 1, 1>(which, a, grid, st);
-    else if (dv == 32) k4_launch<16, 2, 1>(which, a, grid, st);
-    else k4_launch<16, 4, 1>(which, a, grid, st);
-  }
+  t.QB = qb;
+  t.grid[0] = groups * 64 * npair;
+  r = t;
   return 1;
+}
+
+void pg_attn_k4_launch(int which, const PgAttnArgs& a, const PgAttnRoute& r, hipStream_t st) {
+  const dim3 grid((unsigned)r.grid[0]);
+  if (which == PG_ATTN_BWD) {
+    const dim3 dgrid((unsigned)((a.L + 255) / 256), (unsigned)(a.N * a.heads));
+    if (r.DV == 2) hipLaunchKernelGGL((attn_delta_k4_kernel<2>), dgrid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((attn_delta_k4_kernel<1>), dgrid, dim3(256), 0, st, a);
+    if (r.DV == 2) hipLaunchKernelGGL((attn_bwd_k4_kernel<2, 2>), grid, dim3(64), 0, st, a);
+    else hipLaunchKernelGGL((attn_bwd_k4_kernel<1, 2>), grid, dim3(64), 0, st, a);
+    return;
+  }
+  const int key = r.DK * 100 + r.DV * 10 + r.QB;  // <DKT, DVT, QB>
+  switch (key) {
+    case 142: k4_launch<1, 4, 2>(which, a, grid, st); break;
+    case 124: k4_launch<1, 2, 4>(which, a, grid, st); break;
+    case 122: k4_launch<1, 2, 2>(which, a, grid, st); break;
+    case 114: k4_launch<1, 1, 4>(which, a, grid, st); break;
+    case 112: k4_launch<1, 1, 2>(which, a, grid, st); break;
+    case 412: k4_launch<4, 1, 2>(which, a, grid, st); break;
+    case 422: k4_launch<4, 2, 2>(which, a, grid, st); break;
+    case 441: k4_launch<4, 4, 1>(which, a, grid, st); break;
+    case 812: k4_launch<8, 1, 2>(which, a, grid, st); break;
+    case 822: k4_launch<8, 2, 2>(which, a, grid, st); break;
+    case 841: k4_launch<8, 4, 1>(which, a, grid, st); break;
+    case 1611: k4_launch<16, 1, 1>(which, a, grid, st); break;
+    case 1621: k4_launch<16, 2, 1>(which, a, grid, st); break;
+    case 1641: k4_launch<16, 4, 1>(which, a, grid, st); break;
+    default: abort();  // pg_attn_k4_route names instantiated kernels only
+  }
 }

@@ -993,8 +993,6 @@ __global__ void __launch_bounds__(512, 4) attn_bwd_m44_kernel(const PgAttnArgs a
     for (int m = threadIdx.x; m < L; m += blockDim.x) dqp[(size_t)dd * L + m] = dqa[dd * Lp + m] * a.scale;
 }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 }  // namespace
 
 // waves per workgroup: forward / dK,dV use 4 (a multiple of the 4 SIMDs; 3-4 workgroups per CU),
@@ -1014,8 +1012,6 @@ static void attn_waves(int* w) {
   }();
   w[0] = cfg.w[0]; w[1] = cfg.w[1]; w[2] = cfg.w[2];
 }
-
-int pg_attn_k4_launch(int which, const PgAttnArgs& a, hipStream_t st);  // attention_k4.hip
 
 // process-wide switch of the fused backward (default: on, or PG_ATTN_FUSED_BWD=0/1 at load time);
 // pg_attn_fused_bwd(0) selects the two-kernel backward, whose results are bit-reproducible
@@ -1199,22 +1195,24 @@ PG_EXPORT int pg_attn_block_plan(int which, int L, int waves, int* out_blk, int*
   return n;
 }
 
-int pg_attn_mfma_launch(int which, const PgAttnArgs& a0, hipStream_t st) {
+// The d_k = d_v = 4 kernels take a launch while their LDS planes fit 160 KB and a wave's block list holds its share; every other
+// head dim is attention_k4.hip's to decide. Returns 1 with r filled in, else 0 (the caller uses the VALU kernels; for the fused
+// request: the two-kernel backward).
+int pg_attn_mfma_route(int which, int N, int heads, int L, int dk, int dv, int flags, PgAttnRoute& r) {
   if (which == PG_ATTN_BWD) {
     // fused backward: d_k = d_v = 4 only; PG_ATTN_FUSED_BWD=0 keeps the two-kernel backward (A/B, and
     // bit-reproducible dQ: the fused kernel sums dQ over key blocks with fp32 LDS atomics)
     if (!pg_attn_fused_bwd_enabled()) return 0;
-    if (a0.dk_dim != 4 || a0.dv_dim != 4) {
+    if (dk != 4 || dv != 4) {
       // d_k = 4, d_v = 16 / 32 (PixelSNAIL): attn_bwd_k4_kernel (round 4); PG_ATTN_FUSED_BWD_K4=0 for A/B
       static const bool k4_fused = PG_AB_ON("PG_ATTN_FUSED_BWD_K4");
-      return k4_fused ? pg_attn_k4_launch(which, a0, st) : 0;
+      return k4_fused ? pg_attn_k4_route(which, N, heads, L, dk, dv, flags, r) : 0;
     }
   }
   // everything but d_k = d_v = 4: attention_k4.hip decides (d_k in {4, 16, 32, 64} x d_v in {16, 32, 64}, L % 16 == 0)
-  if (a0.dk_dim != 4 || a0.dv_dim != 4) return pg_attn_k4_launch(which, a0, st);
-  PgAttnArgs a = a0;
-  const int NB = (a.L + 63) / 64;
-  a.lp = 64 * NB + 16;  // plane stride == 16 (mod 64): conflict-free b32 and b128 fragment reads
+  if (dk != 4 || dv != 4) return pg_attn_k4_route(which, N, heads, L, dk, dv, flags, r);
+  const int NB = (L + 63) / 64;
+  const int lp = 64 * NB + 16;  // plane stride == 16 (mod 64): conflict-free b32 and b128 fragment reads
   // in 4-byte units per row — fwd: K chunks (2 x 16 B) + V^T planes; dQ: K and V chunks + K^T planes;
   // dK/dV: 10 planes; plus the ones chunk
   // dK/dV score tile on the bf16x3 MFMA (default; PG_ATTN_DKV_BF16=0 selects the all-fp32 variant:
@@ -1228,30 +1226,47 @@ int pg_attn_mfma_launch(int which, const PgAttnArgs& a0, hipStream_t st) {
   const int bwd_waves = bwd_waves_env >= 1 && bwd_waves_env <= 8 ? bwd_waves_env : 8;
   int W = which == PG_ATTN_BWD ? bwd_waves : wcfg[which];
   // fused backward: + 1 KB of transposition scratch per wave
-  const size_t shmem = planes * (size_t)a.lp * sizeof(float) + (which == PG_ATTN_BWD ? 8 * 1024 : 16);
+  const size_t shmem = planes * (size_t)lp * sizeof(float) + (which == PG_ATTN_BWD ? 8 * 1024 : 16);
   if (shmem > 160 * 1024) return 0;
   if (which == PG_ATTN_DKV && dkv_bf16 && !PG_AB_ENV("PG_ATTN_WAVES")) W = 8;
   // few (n, head) units (the reference's default batch 64 x 4 heads = one workgroup per CU): the launch
   // lasts as long as its most loaded wave, so the forward kernel also spreads its 13 query blocks over
   // 8 waves (longest list 78 -> 47.5 tile steps; with many units per CU 4-wave workgroups pack better)
-  if (which == PG_ATTN_FWD && (long)a.N * a.heads <= 512 && !PG_AB_ENV("PG_ATTN_WAVES")) W = 8;
-  const AttnPlan* plan = attn_plan(which, a.L, W);
+  if (which == PG_ATTN_FWD && (long)N * heads <= 512 && !PG_AB_ENV("PG_ATTN_WAVES")) W = 8;
+  const AttnPlan* plan = attn_plan(which, L, W);
   if (!plan->nb) return 0;  // block lists hold 16 entries per wave
-  W = plan->waves;
+  r.family = PG_ATTN_FAM_M44;
+  r.DK = r.DV = 4;
+  r.QB = 0;
+  r.grid[0] = 1; r.grid[1] = heads; r.grid[2] = N;
+  r.waves = plan->waves;
+  r.block = 64 * plan->waves;
+  r.lds = (int)shmem;
+  r.lp = lp;
+  r.plan = plan;
+  const bool out_ok = which == PG_ATTN_FWD  ? !(flags & (PG_ATTN_R_O_MISALIGNED | PG_ATTN_R_O_STRIDE))
+                      : which == PG_ATTN_DQ ? !(flags & (PG_ATTN_R_DQ_MISALIGNED | PG_ATTN_R_DQ_STRIDE))
+                                            // dK/dV and the fused backward (whose dQ planes are written with scalar stores)
+                                            : !(flags & (PG_ATTN_R_DKV_MISALIGNED | PG_ATTN_R_DKV_STRIDE));
+  r.vec = (L % 4 == 0 && out_ok) ? 1 : 0;
+  r.variant = which == PG_ATTN_BWD ? (lp == 848 || lp == 1040 ? lp : 0) : (which == PG_ATTN_DKV && dkv_bf16 ? 1 : 0);
+  return 1;
+}
+
+void pg_attn_mfma_launch(int which, const PgAttnArgs& a0, const PgAttnRoute& r, hipStream_t st) {
+  PgAttnArgs a = a0;
+  a.lp = r.lp;
+  const AttnPlan* plan = static_cast<const AttnPlan*>(r.plan);
   for (int w = 0; w < 8; ++w) {
     a.bcount[w] = plan->bcount[w];
     for (int i = 0; i < 16; ++i) a.blist[w][i] = plan->blist[w][i];
   }
   a.qshift = plan->qshift;
-  a.vec = a.L % 4 == 0 ? 1 : 0;
-  if (which == PG_ATTN_FWD)
-    a.vec = a.vec && aligned16(a.o_out) && a.o_bs % 4 == 0;
-  else if (which == PG_ATTN_DQ)
-    a.vec = a.vec && aligned16(a.dq) && a.dq_bs % 4 == 0;
-  else  // dK/dV and the fused backward (whose dQ planes are written with scalar stores)
-    a.vec = a.vec && aligned16(a.dk) && aligned16(a.dv) && a.dk_bs % 4 == 0 && a.dv_bs % 4 == 0;
-  dim3 grid(1u, (unsigned)a.heads, (unsigned)a.N);
-  dim3 block((unsigned)(64 * W));
+  a.vec = r.vec;
+  const size_t shmem = (size_t)r.lds;
+  const bool dkv_bf16 = r.variant == 1;
+  dim3 grid((unsigned)r.grid[0], (unsigned)r.grid[1], (unsigned)r.grid[2]);
+  dim3 block((unsigned)r.block);
   const void* fn = which == PG_ATTN_FWD  ? reinterpret_cast<const void*>(attn_fwd_m44_kernel)
                    : which == PG_ATTN_BWD ? (a.lp == 848 ? reinterpret_cast<const void*>(attn_bwd_m44_kernel<848>)
                                              : a.lp == 1040 ? reinterpret_cast<const void*>(attn_bwd_m44_kernel<1040>)
@@ -1274,5 +1289,4 @@ int pg_attn_mfma_launch(int which, const PgAttnArgs& a0, hipStream_t st) {
     hipLaunchKernelGGL(attn_dkv_m44_kernel<true>, grid, block, shmem, st, a);
   else
     hipLaunchKernelGGL(attn_dkv_m44_kernel<false>, grid, block, shmem, st, a);
-  return 1;
 }

@@ -178,6 +178,7 @@ SIGNATURES = {
     "pg_adam_step": (c_i, [c_f, c_f, c_f, c_f, c_z, c_f, c_flt, c_flt, c_flt, c_s]),
     "pg_attn_fused_bwd": (c_i, [c_i]),
     "pg_attn_block_plan": (c_i, [c_i, c_i, c_i, c_ip, c_ip, c_ip, c_ip, c_ip]),
+    "pg_attn_route": (c_i, [c_i] * 7 + [c_ip, c_i]),
     "pg_concat_elu_fwd": (c_i, [c_f, c_f, c_i, c_l, c_s]),
     "pg_concat_elu_bwd": (c_i, [c_f, c_f, c_f, c_i, c_l, c_s]),
     "pg_dmol_fwd": (c_i, [c_f, c_f, c_f, c_i, c_i, c_i, c_s]),

@@ -143,6 +143,8 @@ from pytorch_generative_amd.ops.attention import (  # noqa: F401
     set_deterministic,
     causal_attention_qkv,
     attention_dims_native,
+    attention_route,
+    attention_layout_flags,
     _pad16,
     causal_attention,
 )

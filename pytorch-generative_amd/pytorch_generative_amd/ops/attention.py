@@ -202,6 +202,50 @@ def attention_dims_native(dk, dv, L):
     return dk in (4, 16, 32, 64) and dv in (16, 32, 64) and L % 16 == 0 and L >= 16
 
 
+ATTN_FWD, ATTN_DQ, ATTN_DKV, ATTN_BWD = 0, 1, 2, 3
+ATTN_FAMILIES = {0: "valu", 1: "m44", 2: "k4", -1: "declined", -2: "none"}
+# pg_attn_route's flags (include/pg_hip.h PG_ATTN_R_*)
+ATTN_R_QKV_MISALIGNED, ATTN_R_O_MISALIGNED, ATTN_R_GRADIN_MISALIGNED, ATTN_R_DQ_MISALIGNED, ATTN_R_DKV_MISALIGNED = 1, 2, 4, 8, 16
+ATTN_R_QKV_STRIDE, ATTN_R_O_STRIDE, ATTN_R_DO_STRIDE, ATTN_R_DQ_STRIDE, ATTN_R_DKV_STRIDE = 32, 64, 128, 256, 512
+ATTN_ROUTE_FIELDS = ("family", "fused_on", "t0", "t1", "qb", "grid_x", "grid_y", "grid_z", "block", "lds", "blocks_per_wg",
+                     "kt", "tiles", "waves", "lp", "vec", "variant")
+
+
+def attention_route(which, n, heads, L, dk, dv, flags=0):
+    """pg_attn_route: the kernel family and launch geometry pg_causal_attn_fwd (which = ATTN_FWD), the dQ / dK/dV launches
+    (ATTN_DQ, ATTN_DKV) or the fused-backward request (ATTN_BWD) take for this problem, as a dict of ATTN_ROUTE_FIELDS with
+    "family" by name (ATTN_FAMILIES) and "status" (0, or the launch's own: -2 = not instantiated). Host only, no GPU needed.
+    t0 / t1: the template's head dims (include/pg_hip.h); flags: ATTN_R_*, 0 = aligned planes and strides."""
+    out = _lib.int_array([0] * len(ATTN_ROUTE_FIELDS))
+    rc = _lib.load().pg_attn_route(which, n, heads, L, dk, dv, flags, out, len(ATTN_ROUTE_FIELDS))
+    if rc not in (0, -2):
+        _lib.check(rc, "pg_attn_route")
+    r = dict(zip(ATTN_ROUTE_FIELDS, out))
+    r["family"] = ATTN_FAMILIES[r["family"]]
+    r["status"] = rc
+    return r
+
+
+def attention_layout_flags(n_heads, embed, vdim, L, merged):
+    """The ATTN_R_* flags of the launches causal_attention (merged = False: q its own tensor, k / v views into kv, gradients
+    likewise) resp. causal_attention_qkv (merged = True: q / k / v views into one tensor) make, given 16-byte aligned
+    tensors: a view that starts a multiple of embed * L floats into its tensor is aligned when that is a multiple of 4,
+    and a batch stride is the channel count of the tensor it walks times L."""
+    f = 0
+    if (embed * L) % 4:  # k (merged) and v, dk and dv start embed * L resp. 2 * embed * L floats in
+        f |= ATTN_R_QKV_MISALIGNED | ATTN_R_DKV_MISALIGNED
+    ch = (2 * embed + vdim) if merged else (embed + vdim)
+    if (ch * L) % 4 or (not merged and (embed * L) % 4):
+        f |= ATTN_R_QKV_STRIDE
+    if (ch * L) % 4:
+        f |= ATTN_R_DKV_STRIDE
+    if ((ch if merged else embed) * L) % 4:
+        f |= ATTN_R_DQ_STRIDE
+    if (vdim * L) % 4:
+        f |= ATTN_R_O_STRIDE | ATTN_R_DO_STRIDE
+    return f
+
+
 def _pad16(d):
     for v in (16, 32, 64):
         if d <= v:

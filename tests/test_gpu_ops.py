@@ -315,14 +315,14 @@ ATTN_CASES = [
     (2, 2, 32, 32, 28, 28, False),  # ... at the reproduce() image size, L = 784 (49 query groups: ragged last block)
     (1, 1, 32, 32, 20, 20, True),   # ... strict mask, L = 400
     (2, 2, 2, 2, 7, 7, False),     # reference MultipleChannelsTests (L=49, ragged chunks)
-    (1, 1, 4, 4, 5, 5, True),      # L < 64, strict, L % 8 != 0
-    (2, 3, 8, 16, 9, 7, True),     # odd everything
-    (1, 2, 48, 40, 8, 8, False),   # padded head dims (64-template)
-    (1, 1, 4, 4, 18, 18, True),    # L = 324: more than one 256-query block
+    (1, 1, 4, 4, 5, 5, True),      # matrix-core path (d_k = d_v = 4), L < 64, strict, L % 8 != 0
+    (2, 3, 8, 16, 9, 7, True),     # odd everything: VALU row-owner kernels, L = 63
+    (1, 2, 48, 40, 8, 8, False),   # head dims zero-padded to 64 / 64 (attention_k4.hip)
+    (1, 1, 4, 4, 18, 18, True),    # matrix-core path, L = 324: six query blocks, the short one first
     (3, 2, 4, 4, 28, 28, True),    # matrix-core path (d_k = d_v = 4), strict mask
     (1, 3, 4, 4, 7, 9, False),     # matrix-core path, L = 63: scalar staging, ragged last group
     (1, 1, 4, 4, 32, 32, False),   # matrix-core path, L = 1024: 16 blocks = 8 waves
-    (1, 2, 4, 4, 36, 36, True),    # matrix-core path, L = 1296: two workgroups per (n, head)
+    (1, 2, 4, 4, 36, 36, True),    # matrix-core path, L = 1296: 21 blocks on the 8 waves of ONE workgroup per (n, head)
     # round 4: head dims beyond (4, <= 32) / (<= 16, <= 16) on the matrix-core kernels of attention_k4.hip
     # (instantiated for d_k in {4, 16, 32, 64} x d_v in {16, 32, 64}), other sizes zero-padded by ops.causal_attention
     (2, 1, 64, 64, 16, 16, False),  # 64 / 64: 16-row blocks
@@ -347,7 +347,7 @@ ALLOWED_SET_CASES = [
     (1, 4, 32, 32, 32, True),   # PixelSNAIL (configs[3]): attention_k4.hip, L = 1024, strict
     (1, 4, 32, 32, 32, False),
     (2, 32, 32, 28, 28, False),  # ImageGPT reproduce() head dims, ragged last 32-row block
-    (1, 4, 4, 36, 36, True),    # L = 1296: two workgroups per (n, head)
+    (1, 4, 4, 36, 36, True),    # attention_mfma.hip, L = 1296: 21 blocks on the 8 waves of one workgroup
     (2, 2, 2, 7, 7, False),     # VALU row-owner kernels, L = 49
 ]
 
