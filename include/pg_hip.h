@@ -185,6 +185,30 @@ int pg_conv2d_wgrad(const float* x, const float* dy, float* dw, float* db, int N
                     int in_act, float* workspace, size_t workspace_floats, void* stream);
 /* floats of scratch pg_conv2d_wgrad needs for a (Cout, Cin, T) problem */
 size_t pg_conv2d_wgrad_workspace_floats(int Cout, int Cin, int T);
+/* Host only (no device call): which kernel a pg_conv2d_wgrad call of this problem launches and how it is laid out — the answer of the
+ * one route function the launch itself reads (csrc/conv_wgrad.hip: wgrad_route). flags: PG_WGR_* (db given; x / dy not 16-byte
+ * aligned). Fills out[0 .. PG_WGR_ROUTE_INTS):
+ *   [0]     family: 0 x-copy bf16x3 (conv_wgrad_b3_kernel), 1 row ring (conv_wgrad_b3r_kernel), 2 shifted dy (conv_wgrad_b3s_kernel),
+ *           3 fp32 1x1 (conv_wgrad_pw_kernel), 4 input layer (conv_wgrad_small_kernel), 5 generic fp32 (conv_wgrad_kernel)
+ *   [1..4]  that family's template integers: x-copy T, MR, waves, CIT | ring T, WM, WN | shifted dy NR, NC | 1x1 NCOT, NCIT, ACT |
+ *           input layer none | generic NT (taps per pass), NC, prefetch; unused ones 0
+ *   [5..9]  grid x, y, z, block size, dynamic LDS bytes
+ *   [10]    G, the partial rows the kernel writes and the reduction reads (= grid x)
+ *   [11..13] TR (rows per tile; ring 1), tiles per image, total tiles (ring: (image, segment) units; 1x1: 16-pixel groups)
+ *   [14..16] nseg, seg_rows (ring: row segments per image, rows per segment), PBR (bf16x3: 8-pixel blocks per row)
+ *   [17..18] vec_dy, vec_x (float4 staging of dy / x)
+ *   [19]    grid of wgrad_reduce_kernel (64 slots per workgroup)
+ *   [20..22] row halo of the tap list, copies (x copies of x-copy / ring, dy copies of shifted dy), tap passes (generic)
+ *   [23]    partial rows the workspace of pg_conv2d_wgrad_workspace_floats holds
+ * The ablation / experiment switches (PG_AB_*, read by the variant libraries only) are honoured: the route is what THIS process would
+ * launch. Returns 0, or the status the launch would return (PG_ESHAPE) with the same message; PG_EINVAL for a null pointer, a short
+ * array or a bad dimension. */
+#define PG_WGR_HAS_BIAS 1
+#define PG_WGR_X_MISALIGNED 2
+#define PG_WGR_DY_MISALIGNED 4
+#define PG_WGR_ROUTE_INTS 24
+int pg_conv2d_wgrad_route(int N, int Cin, int IH, int IW, int Cout, int OH, int OW, int KH, int KW, int T, const int* tap_dr,
+                          const int* tap_dc, int in_act, int flags, int* out, int n_out);
 
 /* w *= mask in place: nn/convolution.py:42 `self.weight.data *= self.mask`. */
 int pg_mul_inplace(float* w, const float* mask, size_t n, void* stream);

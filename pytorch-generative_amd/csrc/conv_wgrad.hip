@@ -18,8 +18,9 @@
 // dy / x tiles (x with halo, zero filled) are staged in LDS with channel strides == 2 (mod 32)
 // so both fragment reads are bank-conflict free. Each workgroup walks many pixel tiles and
 // flushes once with fp32 atomics (caller zeroes dw/db once per step).
-#include "common.h"
+#include "conv_wgrad_route.h"
 #include <stdlib.h>
+#include <string.h>
 
 namespace {
 
@@ -31,24 +32,6 @@ constexpr int CI_CHUNK = 32;  // x channels staged per block (2 MFMA column tile
 constexpr int DS = 4;    // float4 staging slots per thread per tile: dy
 constexpr int XSW = 6;   // ... and x
 constexpr int LDS_BUDGET_FLOATS = 18000;  // ~72 KB -> two workgroups per CU: one stages while the other runs MFMAs (measured best of 36k/18k/9.5k)
-
-struct WgArgs {
-  const float* x; const float* dy; float* dw; float* db;
-  float* part;        // [gridDim.x][part_stride] per-block partial sums (no atomics: see below)
-  long part_stride;   // = Cout*Cin*T + Cout
-  int N, Cin, IH, IW, Cout, OH, OW, KH, KW, T;
-  int TR, tiles_per_img, total_tiles, SW, xh, min_dr, min_dc;
-  int S_dy, S_x, npos, in_act;
-  int swp_shift, rpi;       // lanes per staged row = 1<<swp_shift, rows per wave iteration
-  int dump;                 // LDS float index of the dump word (past every tile / scratch area)
-  int vec_dy, vec_x, qshift_dy, qshift_x;  // float4 staging when rows are 16-byte aligned
-  float inv_TR, inv_xh;
-  int prefetch;             // float4 slot staging with register prefetch (both tensors 16-byte aligned rows)
-  int Qd, Qx, dslots, xslots;  // quads per row and slots per tile (dy / x)
-  int tapoff[PG_MAX_TAPS];
-  int tap_u[PG_MAX_TAPS];
-  int tap_v[PG_MAX_TAPS];
-};
 
 template <int NT, int NCIT, bool PF>
 __global__ void __launch_bounds__(WG_THREADS, NT <= 4 ? 2 : 1) conv_wgrad_kernel(const WgArgs a) {
@@ -334,14 +317,6 @@ __global__ void __launch_bounds__(WG_THREADS, NT <= 4 ? 2 : 1) conv_wgrad_kernel
 // of "its" channel lane&15, pixel quad lane>>4) per 16-channel tile; MFMA #j of a 16-pixel group
 // contracts element j of every lane's float4, i.e. pixels {4k + j : k = lane>>4} — A and B use
 // the same pixel<->(lane, j) bijection, so no cross-lane movement is needed.
-struct PwWgArgs {
-  const float* x; const float* dy; float* dw; float* db;
-  float* part;        // [gridDim.x][Cout*Cin + Cout]
-  long part_stride;
-  int N, Cin, Cout, L, G16, in_act;
-  long total_groups;
-};
-
 template <int NCOT, int NCIT, int ACT>
 __global__ void __launch_bounds__(WG_THREADS) conv_wgrad_pw_kernel(const PwWgArgs a) {
   // U pixel groups are loaded per iteration before any MFMA, so >= 2*U*(tiles) 16-byte loads are
@@ -471,7 +446,7 @@ void launch_pw_wgrad_act(const PwWgArgs& a, dim3 grid, hipStream_t st) {
 
 template <int NCOT>
 void launch_pw_wgrad(const PwWgArgs& a, int ncit, dim3 grid, hipStream_t st) {
-  if (ncit <= 1) launch_pw_wgrad_act<NCOT, 1>(a, grid, st);
+  if (ncit == 1) launch_pw_wgrad_act<NCOT, 1>(a, grid, st);
   else if (ncit == 2) launch_pw_wgrad_act<NCOT, 2>(a, grid, st);
   else launch_pw_wgrad_act<NCOT, 4>(a, grid, st);
 }
@@ -536,24 +511,193 @@ inline int pad_stride(int s) {  // smallest s' >= s with s' % 32 == 2
   return r <= 2 ? s + (2 - r) : s + (34 - r);
 }
 
-}  // namespace
+// ---- the route: ONE function decides which kernel family takes a problem and how it is laid out --------------------------------------
+// wgrad_route(problem) -> route is pure host arithmetic (no HIP call): the launch (pg_conv2d_wgrad) and the host-only export
+// pg_conv2d_wgrad_route read the same answer. The bf16x3 and input-layer families plan themselves (conv_wgrad_route.h).
 
-// conv_wgrad_small.hip: input layers (<= 4 input channels, many taps); same return convention
-int pg_wgrad_small_launch(const float* x, const float* dy, float* part, long part_stride, long max_rows,
-                          int has_bias, int N, int Cin, int IH, int IW, int Cout, int OH, int OW, int T,
-                          const int* tap_dr, const int* tap_dc, int in_act, hipStream_t st);
+void wg_clear(WgRoute& r) { memset(&r, 0, sizeof(r)); }
 
-// conv_wgrad_b3.hip: the bf16x3 kernel for the shapes it takes (returns the partial rows it wrote)
-int pg_wgrad_b3_launch(const float* x, const float* dy, float* part, long part_stride, long max_rows,
-                       int has_bias, int N, int Cin, int IH, int IW, int Cout, int OH, int OW, int T,
-                       const int* tap_dr, const int* tap_dc, int in_act, hipStream_t st);
+bool wg_is_1x1(const WgProblem& p) {
+  return p.T == 1 && p.KH == 1 && p.KW == 1 && p.tap_dr[0] == 0 && p.tap_dc[0] == 0 && p.IH == p.OH && p.IW == p.OW;
+}
 
-// ... and its "shifted dy" variant (32 output channels per workgroup, full tap grids, W % 4 == 0)
-int pg_wgrad_b3s_launch(const float* x, const float* dy, float* part, long part_stride, long max_rows,
-                        int has_bias, int N, int Cin, int IH, int IW, int Cout, int OH, int OW, int T,
-                        const int* tap_dr, const int* tap_dc, int in_act, hipStream_t st);
+// fp32 1x1 kernel (conv_wgrad_pw_kernel): fragments straight from global memory
+int wg_plan_pw(const WgProblem& p, WgRoute& r) {
+  if (!(wg_is_1x1(p) && ((p.OH * p.OW) % 4 == 0) && p.x_al16 && p.dy_al16)) return 0;
+  PwWgArgs& a = r.pw;
+  a.x = nullptr; a.dy = nullptr; a.dw = nullptr; a.db = nullptr; a.part = nullptr; a.part_stride = p.stride;
+  a.N = p.N; a.Cin = p.Cin; a.Cout = p.Cout; a.L = p.OH * p.OW; a.in_act = p.in_act;
+  a.G16 = (a.L + 15) / 16;
+  a.total_groups = (long)p.N * a.G16;
+  const int co_chunks = (p.Cout + 63) / 64, ci_chunks = (p.Cin + 63) / 64;
+  const int ncot = ((p.Cout < 64 ? p.Cout : 64) + 15) / 16, ncit = ((p.Cin < 64 ? p.Cin : 64) + 15) / 16;
+  long gx = (a.total_groups + 15) / 16;
+  if (gx > p.max_rows) gx = p.max_rows;
+  r.family = WGF_PW;
+  r.t[0] = ncot;                                // 3 = 48 output channels: the merged q|k|v projection
+  r.t[1] = ncit <= 1 ? 1 : ncit == 2 ? 2 : 4;
+  r.t[2] = p.in_act;
+  r.gx = (int)gx; r.gy = co_chunks; r.gz = ci_chunks; r.block = WG_THREADS;
+  r.shmem = (size_t)3 * (r.t[0] * r.t[1] + r.t[0]) * 256 * sizeof(float);
+  r.G = (int)gx; r.total = a.total_groups; r.vec_dy = r.vec_x = 1;
+  return 1;
+}
 
-static long wgrad_max_rows(int Cout, int Cin, int T) {
+void wg_run_pw(const WgRoute& r, const float* x, const float* dy, float* dw, float* db, float* part, hipStream_t st) {
+  PwWgArgs a = r.pw;
+  a.x = x; a.dy = dy; a.dw = dw; a.db = db; a.part = part;
+  const dim3 grid((unsigned)r.gx, (unsigned)r.gy, (unsigned)r.gz);
+  switch (r.t[0]) {
+    case 1: launch_pw_wgrad<1>(a, r.t[1], grid, st); break;
+    case 2: launch_pw_wgrad<2>(a, r.t[1], grid, st); break;
+    case 3: launch_pw_wgrad<3>(a, r.t[1], grid, st); break;
+    default: launch_pw_wgrad<4>(a, r.t[1], grid, st); break;
+  }
+}
+
+#define WG_ROUTE_REQUIRE(cond, code, ...)              \
+  do {                                                 \
+    if (!(cond)) {                                     \
+      snprintf(r.msg, sizeof(r.msg), __VA_ARGS__);     \
+      return (code);                                   \
+    }                                                  \
+  } while (0)
+
+// generic fp32 kernel (conv_wgrad_kernel): takes everything its LDS holds; 0 or the launch's status
+int wg_plan_generic(const WgProblem& p, WgRoute& r) {
+  const int N = p.N, Cin = p.Cin, IH = p.IH, IW = p.IW, Cout = p.Cout, OH = p.OH, OW = p.OW, T = p.T;
+  WgArgs& a = r.wg;
+  a.x = nullptr; a.dy = nullptr; a.dw = nullptr; a.db = nullptr;
+  a.N = N; a.Cin = Cin; a.IH = IH; a.IW = IW; a.Cout = Cout; a.OH = OH; a.OW = OW;
+  a.KH = p.KH; a.KW = p.KW; a.T = T; a.in_act = p.in_act;
+  a.part = nullptr; a.part_stride = p.stride;
+  int min_dr, min_dc, hr, hc;
+  pg_tap_extent(T, p.tap_dr, p.tap_dc, min_dr, hr, min_dc, hc);
+  a.min_dr = min_dr; a.min_dc = min_dc;
+  a.SW = OW + hc;
+  const int nco = Cout < CO_CHUNK ? ((Cout + 15) / 16) * 16 : CO_CHUNK;
+  const int nco_alloc = nco == 48 ? 64 : nco;
+  const int nci = Cin < CI_CHUNK ? ((Cin + 15) / 16) * 16 : CI_CHUNK;
+  // per-row cost in floats: (nco+nci)*SW ; fixed: nci*(hr*SW + hc + 48) + nco*48
+  const int fixed = nci * (hr * a.SW + hc + 48) + nco_alloc * 48;
+  int TR = (LDS_BUDGET_FLOATS - fixed) / ((nco_alloc + nci) * a.SW);
+  WG_ROUTE_REQUIRE(TR >= 1, PG_ESHAPE, "pg_conv2d_wgrad: row of %d (+%d halo) too wide for LDS", OW, hc);
+  if (TR > OH) TR = OH;
+  // register-prefetch staging: rows of both tensors 16-byte aligned in global memory
+  static const bool pf_on = PG_AB_ON("PG_WGRAD_PREFETCH");
+  a.prefetch = pf_on && (OW % 4 == 0) && (IW % 4 == 0) && p.x_al16 && p.dy_al16;
+  a.Qd = OW / 4;
+  a.Qx = IW / 4;
+  if (a.prefetch) {
+    while (TR > 1 && ((long)nco * TR * a.Qd > (long)DS * WG_THREADS ||
+                      (long)nci * (TR + hr) * a.Qx > (long)XSW * WG_THREADS))
+      --TR;
+    if ((long)nco * TR * a.Qd > (long)DS * WG_THREADS ||
+        (long)nci * (TR + hr) * a.Qx > (long)XSW * WG_THREADS || TR + hr >= 2048)
+      a.prefetch = 0;
+  }
+  a.TR = TR;
+  a.xh = TR + hr;
+  a.tiles_per_img = (OH + TR - 1) / TR;
+  a.total_tiles = N * a.tiles_per_img;
+  const int kq = 16;  // npos multiple of 4*ks for every ks in {1,2,4}
+  a.npos = ((TR * a.SW + kq - 1) / kq) * kq;
+  a.S_dy = pad_stride(a.npos);
+  a.dslots = nco * a.TR * a.Qd;
+  a.xslots = nci * a.xh * a.Qx;
+  a.S_x = pad_stride(a.npos + hr * a.SW + hc + 4);
+  for (int t = 0; t < T; ++t) a.tapoff[t] = (p.tap_dr[t] - min_dr) * a.SW + (p.tap_dc[t] - min_dc);
+  int shift = 0;
+  while ((1 << shift) < a.SW && shift < 6) ++shift;
+  a.swp_shift = shift;
+  a.rpi = 64 >> shift;
+  a.inv_TR = 1.0f / (float)a.TR;
+  a.inv_xh = 1.0f / (float)a.xh;
+  a.vec_dy = (OW % 4 == 0) && p.dy_al16 && (OW / 4 <= 64);
+  a.vec_x = (IW % 4 == 0) && p.x_al16 && (IW / 4 <= 64);
+  a.qshift_dy = a.qshift_x = 0;
+  while ((1 << a.qshift_dy) < OW / 4 && a.qshift_dy < 6) ++a.qshift_dy;
+  while ((1 << a.qshift_x) < IW / 4 && a.qshift_x < 6) ++a.qshift_x;
+  const int co_chunks = (Cout + CO_CHUNK - 1) / CO_CHUNK;
+  const int ci_chunks = (Cin + CI_CHUNK - 1) / CI_CHUNK;
+  int G = 512 / (co_chunks * ci_chunks);
+  if (G < 64) G = 64;
+  if (G > a.total_tiles) G = a.total_tiles;
+  if (G > p.max_rows) G = (int)p.max_rows;
+  size_t shmem = ((size_t)nco_alloc * a.S_dy + (size_t)nci * a.S_x) * sizeof(float);
+  const int ncit_h = (nci + 15) / 16;
+  const int NTsel = T >= 9 ? 9 : (T >= 4 ? 4 : T);  // taps per pass: 1, 2, 3, 4 or 9
+  const size_t red_bytes = (size_t)3 * (ncit_h * NTsel + 1) * 256 * sizeof(float);  // cross-wave reduction scratch
+  if (shmem < red_bytes) shmem = red_bytes;
+  a.dump = (int)(shmem / sizeof(float));
+  shmem += 16;
+  WG_ROUTE_REQUIRE(shmem <= 160 * 1024, PG_ESHAPE, "pg_conv2d_wgrad: LDS %zu B over budget", shmem);
+  r.family = WGF_GENERIC;
+  r.t[0] = NTsel; r.t[1] = ncit_h <= 1 ? 1 : 2; r.t[2] = a.prefetch;
+  r.gx = G; r.gy = co_chunks; r.gz = ci_chunks; r.block = WG_THREADS; r.shmem = shmem; r.G = G;
+  r.TR = TR; r.tiles_per_img = a.tiles_per_img; r.total = a.total_tiles;
+  r.vec_dy = a.vec_dy; r.vec_x = a.vec_x; r.hr = hr; r.passes = (T + NTsel - 1) / NTsel;
+  return 0;
+}
+
+void wg_run_generic(const WgRoute& r, const float* x, const float* dy, float* dw, float* db, float* part, const int* tap_u,
+                    const int* tap_v, hipStream_t st) {
+  WgArgs a = r.wg;
+  a.x = x; a.dy = dy; a.dw = dw; a.db = db; a.part = part;
+  for (int t = 0; t < a.T; ++t) {
+    a.tap_u[t] = tap_u[t];
+    a.tap_v[t] = tap_v[t];
+  }
+  const dim3 grid((unsigned)r.gx, (unsigned)r.gy, (unsigned)r.gz);
+  const size_t shmem = r.shmem;
+#define PG_WG(NT, NC)                                                                              \
+  {                                                                                               \
+    if (a.prefetch) hipLaunchKernelGGL((conv_wgrad_kernel<NT, NC, true>), grid, dim3(WG_THREADS), shmem, st, a);  \
+    else hipLaunchKernelGGL((conv_wgrad_kernel<NT, NC, false>), grid, dim3(WG_THREADS), shmem, st, a);            \
+  }
+  if (r.t[1] == 1) {
+    switch (r.t[0]) { case 1: PG_WG(1, 1); break; case 2: PG_WG(2, 1); break; case 3: PG_WG(3, 1); break;
+                      case 4: PG_WG(4, 1); break; default: PG_WG(9, 1); break; }
+  } else {
+    switch (r.t[0]) { case 1: PG_WG(1, 2); break; case 2: PG_WG(2, 2); break; case 3: PG_WG(3, 2); break;
+                      case 4: PG_WG(4, 2); break; default: PG_WG(9, 2); break; }
+  }
+#undef PG_WG
+}
+
+// The order in which the families are asked (each plan function declines what it does not take):
+//   1. a 1x1 convolution: the bf16x3 kernels (x-copy big tiles, or the ring's 128 x 128 tile), then the fp32 direct-fragment kernel;
+//   2. the input-layer kernel;
+//   3. x-copy / ring, shifted-dy, x-copy again for the shapes that prefer the shifted-dy kernel (below);
+//   4. the generic fp32 kernel, which takes whatever its LDS holds.
+// Returns 0 with the route, or the status the launch returns with r.msg.
+int wgrad_route(const WgProblem& p, WgRoute& r) {
+  wg_clear(r);
+  // 1x1 convolutions whose shape the bf16x3 kernel takes (Cout % 64 == 0, Cin % 32 == 0, W % 8 == 0) go there
+  // first (PG_WGRAD_B3_PW=0: the fp32 direct-fragment kernel below, for A/B)
+  static const bool b3_pw = PG_AB_ON("PG_WGRAD_B3_PW");
+  if (b3_pw && wg_is_1x1(p) && pg_wgrad_b3_plan(p, r)) return 0;
+  wg_clear(r);
+  if (wg_plan_pw(p, r)) return 0;
+  wg_clear(r);
+  if (pg_wgrad_small_plan(p, r)) return 0;
+  // 64 output channels per workgroup where the shape divides that way (the kernel PixelSNAIL / GatedPixelCNN were
+  // tuned on), else — or when its x copies do not fit LDS (3x3 on 64-wide rows) — the shifted-dy variant
+  // (measured, PG_WGRAD_B3S=2 prefers the shifted-dy kernel everywhere: PixelSNAIL 12.43 -> 12.31 k img/s,
+  // GatedPixelCNN 5.26 -> 5.06 k, beta-VAE 38.1 -> 38.5 k: only the 3x3 grids gain, so those go there first)
+  static const bool s_all = PG_AB_OFF("PG_WGRAD_B3S", '2');
+  const bool s_first = s_all || p.T == 9;
+  wg_clear(r);
+  if (p.Cout % 64 == 0 && !s_first && pg_wgrad_b3_plan(p, r)) return 0;
+  wg_clear(r);
+  if (pg_wgrad_b3s_plan(p, r)) return 0;
+  wg_clear(r);
+  if ((p.Cout % 64 != 0 || s_first) && pg_wgrad_b3_plan(p, r)) return 0;
+  wg_clear(r);
+  return wg_plan_generic(p, r);
+}
+
+long wgrad_max_rows(int Cout, int Cin, int T) {
   const long chunks = (long)((Cout + 63) / 64) * ((Cin + 63) / 64);
   // one tap with Cout % 128 == 0 and Cin % 64 == 0: conv_wgrad_b3's 128 x 64 tiles — half as many (co, ci) chunks, so
   // twice the partial rows for the same number of workgroups
@@ -562,6 +706,21 @@ static long wgrad_max_rows(int Cout, int Cin, int T) {
   const long g = ((T == 1 && Cout % 128 == 0 && Cin % 128 == 0) ? 2048 : (Cout % 128 == 0 && Cin % 64 == 0) ? 1024 : 512) / chunks;  // (any tap count: the ring's 128 x 64 tiles)
   return g > 64 ? g : 64;
 }
+
+WgProblem wg_problem(int N, int Cin, int IH, int IW, int Cout, int OH, int OW, int KH, int KW, int T, const int* tap_dr,
+                     const int* tap_dc, int in_act, bool has_bias, bool x_al16, bool dy_al16) {
+  WgProblem p;
+  p.N = N; p.Cin = Cin; p.IH = IH; p.IW = IW; p.Cout = Cout; p.OH = OH; p.OW = OW; p.KH = KH; p.KW = KW; p.T = T;
+  p.tap_dr = tap_dr; p.tap_dc = tap_dc; p.in_act = in_act;
+  p.has_bias = has_bias; p.x_al16 = x_al16; p.dy_al16 = dy_al16;
+  p.stride = (long)Cout * Cin * T + Cout;
+  p.max_rows = wgrad_max_rows(Cout, Cin, T);
+  return p;
+}
+
+unsigned reduce_grid(const WgProblem& p) { return (unsigned)(((long)p.Cout * p.Cin * p.T + (p.has_bias ? p.Cout : 0) + 63) / 64); }
+
+}  // namespace
 
 PG_EXPORT size_t pg_conv2d_wgrad_workspace_floats(int Cout, int Cin, int T) {
   return (size_t)wgrad_max_rows(Cout, Cin, T) * ((size_t)Cout * Cin * T + Cout);
@@ -586,161 +745,60 @@ PG_EXPORT int pg_conv2d_wgrad(const float* x, const float* dy, float* dw, float*
     PG_REQUIRE(tap_u[t] >= 0 && tap_u[t] < KH && tap_v[t] >= 0 && tap_v[t] < KW, PG_EINVAL,
                "pg_conv2d_wgrad: tap %d outside the %dx%d filter", t, KH, KW);
   hipStream_t st = (hipStream_t)stream;
-  const long stride = (long)Cout * Cin * T + Cout;
-  const long max_rows = wgrad_max_rows(Cout, Cin, T);
-  // 1x1 convolutions whose shape the bf16x3 kernel takes (Cout % 64 == 0, Cin % 32 == 0, W % 8 == 0) go there
-  // first (PG_WGRAD_B3_PW=0: the fp32 direct-fragment kernel below, for A/B)
-  static const bool b3_pw = PG_AB_ON("PG_WGRAD_B3_PW");
-  if (b3_pw && T == 1 && KH == 1 && KW == 1 && tap_dr[0] == 0 && tap_dc[0] == 0 && IH == OH && IW == OW) {
-    const int g = pg_wgrad_b3_launch(x, dy, workspace, stride, max_rows, db != nullptr, N, Cin, IH, IW,
-                                     Cout, OH, OW, T, tap_dr, tap_dc, in_act, st);
-    PG_REQUIRE(g >= 0, PG_EINVAL, "pg_conv2d_wgrad(bf16x3, 1x1): launch failed");
-    if (g > 0) {
-      launch_reduce(workspace, stride, g, dw, db, Cout, Cin, KH, KW, T, tap_u, tap_v, st);
-      PG_LAUNCH_CHECK("pg_conv2d_wgrad(reduce)");
-      return 0;
-    }
+  const WgProblem p = wg_problem(N, Cin, IH, IW, Cout, OH, OW, KH, KW, T, tap_dr, tap_dc, in_act, db != nullptr,
+                                 ((uintptr_t)x & 15) == 0, ((uintptr_t)dy & 15) == 0);
+  WgRoute r;
+  const int rc = wgrad_route(p, r);
+  if (rc) {
+    pg_set_error("%s", r.msg);
+    return rc;
   }
-  if (T == 1 && KH == 1 && KW == 1 && tap_dr[0] == 0 && tap_dc[0] == 0 && IH == OH && IW == OW &&
-      ((OH * OW) % 4 == 0) && (((uintptr_t)x | (uintptr_t)dy) & 15) == 0) {
-    PwWgArgs p;
-    p.x = x; p.dy = dy; p.dw = dw; p.db = db; p.part = workspace; p.part_stride = stride;
-    p.N = N; p.Cin = Cin; p.Cout = Cout; p.L = OH * OW; p.in_act = in_act;
-    p.G16 = (p.L + 15) / 16;
-    p.total_groups = (long)N * p.G16;
-    const int co_chunks = (Cout + 63) / 64, ci_chunks = (Cin + 63) / 64;
-    const int ncot = ((Cout < 64 ? Cout : 64) + 15) / 16, ncit = ((Cin < 64 ? Cin : 64) + 15) / 16;
-    long gx = (p.total_groups + 15) / 16;
-    if (gx > max_rows) gx = max_rows;
-    dim3 grid((unsigned)gx, (unsigned)co_chunks, (unsigned)ci_chunks);
-    if (ncot <= 1) launch_pw_wgrad<1>(p, ncit, grid, st);
-    else if (ncot == 2) launch_pw_wgrad<2>(p, ncit, grid, st);
-    else if (ncot == 3) launch_pw_wgrad<3>(p, ncit, grid, st);  // 48 = the merged q|k|v projection
-    else launch_pw_wgrad<4>(p, ncit, grid, st);
-    PG_LAUNCH_CHECK("pg_conv2d_wgrad(1x1)");
-    launch_reduce(workspace, stride, (int)gx, dw, db, Cout, Cin, KH, KW, T, tap_u, tap_v, st);
-    PG_LAUNCH_CHECK("pg_conv2d_wgrad(reduce)");
-    return 0;
+  switch (r.family) {
+    case WGF_XCOPY:
+    case WGF_RING:
+      PG_REQUIRE(pg_wgrad_b3_run(r, x, dy, workspace, st) == 0, PG_EINVAL, "pg_conv2d_wgrad(bf16x3%s): launch failed",
+                 wg_is_1x1(p) ? ", 1x1" : "");
+      break;
+    case WGF_SHIFTED:
+      PG_REQUIRE(pg_wgrad_b3s_run(r, x, dy, workspace, st) == 0, PG_EINVAL, "pg_conv2d_wgrad(bf16x3): launch failed");
+      break;
+    case WGF_SMALL:
+      PG_REQUIRE(pg_wgrad_small_run(r, x, dy, workspace, st) == 0, PG_EINVAL, "pg_conv2d_wgrad(input layer): launch failed");
+      break;
+    case WGF_PW:
+      wg_run_pw(r, x, dy, dw, db, workspace, st);
+      PG_LAUNCH_CHECK("pg_conv2d_wgrad(1x1)");
+      break;
+    default:
+      wg_run_generic(r, x, dy, dw, db, workspace, tap_u, tap_v, st);
+      PG_LAUNCH_CHECK("pg_conv2d_wgrad");
+      break;
   }
-  {
-    const int g = pg_wgrad_small_launch(x, dy, workspace, stride, max_rows, db != nullptr, N, Cin, IH, IW,
-                                        Cout, OH, OW, T, tap_dr, tap_dc, in_act, st);
-    PG_REQUIRE(g >= 0, PG_EINVAL, "pg_conv2d_wgrad(input layer): launch failed");
-    if (g > 0) {
-      launch_reduce(workspace, stride, g, dw, db, Cout, Cin, KH, KW, T, tap_u, tap_v, st);
-      PG_LAUNCH_CHECK("pg_conv2d_wgrad(reduce)");
-      return 0;
-    }
-  }
-  {
-    // 64 output channels per workgroup where the shape divides that way (the kernel PixelSNAIL / GatedPixelCNN were
-    // tuned on), else — or when its x copies do not fit LDS (3x3 on 64-wide rows) — the shifted-dy variant
-    // (measured, PG_WGRAD_B3S=2 prefers the shifted-dy kernel everywhere: PixelSNAIL 12.43 -> 12.31 k img/s,
-    // GatedPixelCNN 5.26 -> 5.06 k, beta-VAE 38.1 -> 38.5 k: only the 3x3 grids gain, so those go there first)
-    static const bool s_all = PG_AB_OFF("PG_WGRAD_B3S", '2');
-    const bool s_first = s_all || T == 9;
-    int g = (Cout % 64 == 0 && !s_first) ? pg_wgrad_b3_launch(x, dy, workspace, stride, max_rows, db != nullptr, N, Cin, IH, IW,
-                                                Cout, OH, OW, T, tap_dr, tap_dc, in_act, st)
-                           : 0;
-    if (g == 0)
-      g = pg_wgrad_b3s_launch(x, dy, workspace, stride, max_rows, db != nullptr, N, Cin, IH, IW, Cout, OH, OW, T,
-                              tap_dr, tap_dc, in_act, st);
-    if (g == 0 && (Cout % 64 != 0 || s_first))
-      g = pg_wgrad_b3_launch(x, dy, workspace, stride, max_rows, db != nullptr, N, Cin, IH, IW, Cout, OH, OW, T,
-                             tap_dr, tap_dc, in_act, st);
-    PG_REQUIRE(g >= 0, PG_EINVAL, "pg_conv2d_wgrad(bf16x3): launch failed");
-    if (g > 0) {
-      launch_reduce(workspace, stride, g, dw, db, Cout, Cin, KH, KW, T, tap_u, tap_v, st);
-      PG_LAUNCH_CHECK("pg_conv2d_wgrad(reduce)");
-      return 0;
-    }
-  }
-  WgArgs a;
-  a.x = x; a.dy = dy; a.dw = dw; a.db = db;
-  a.N = N; a.Cin = Cin; a.IH = IH; a.IW = IW; a.Cout = Cout; a.OH = OH; a.OW = OW;
-  a.KH = KH; a.KW = KW; a.T = T; a.in_act = in_act;
-  a.part = workspace; a.part_stride = stride;
-  int min_dr, min_dc, hr, hc;
-  pg_tap_extent(T, tap_dr, tap_dc, min_dr, hr, min_dc, hc);
-  a.min_dr = min_dr; a.min_dc = min_dc;
-  a.SW = OW + hc;
-  const int nco = Cout < CO_CHUNK ? ((Cout + 15) / 16) * 16 : CO_CHUNK;
-  const int nco_alloc = nco == 48 ? 64 : nco;
-  const int nci = Cin < CI_CHUNK ? ((Cin + 15) / 16) * 16 : CI_CHUNK;
-  // per-row cost in floats: (nco+nci)*SW ; fixed: nci*(hr*SW + hc + 48) + nco*48
-  const int fixed = nci * (hr * a.SW + hc + 48) + nco_alloc * 48;
-  int TR = (LDS_BUDGET_FLOATS - fixed) / ((nco_alloc + nci) * a.SW);
-  PG_REQUIRE(TR >= 1, PG_ESHAPE, "pg_conv2d_wgrad: row of %d (+%d halo) too wide for LDS", OW, hc);
-  if (TR > OH) TR = OH;
-  // register-prefetch staging: rows of both tensors 16-byte aligned in global memory
-  static const bool pf_on = PG_AB_ON("PG_WGRAD_PREFETCH");
-  a.prefetch = pf_on && (OW % 4 == 0) && (IW % 4 == 0) && ((((uintptr_t)x | (uintptr_t)dy) & 15) == 0);
-  a.Qd = OW / 4;
-  a.Qx = IW / 4;
-  if (a.prefetch) {
-    while (TR > 1 && ((long)nco * TR * a.Qd > (long)DS * WG_THREADS ||
-                      (long)nci * (TR + hr) * a.Qx > (long)XSW * WG_THREADS))
-      --TR;
-    if ((long)nco * TR * a.Qd > (long)DS * WG_THREADS ||
-        (long)nci * (TR + hr) * a.Qx > (long)XSW * WG_THREADS || TR + hr >= 2048)
-      a.prefetch = 0;
-  }
-  a.TR = TR;
-  a.xh = TR + hr;
-  a.tiles_per_img = (OH + TR - 1) / TR;
-  a.total_tiles = N * a.tiles_per_img;
-  const int kq = 16;  // npos multiple of 4*ks for every ks in {1,2,4}
-  a.npos = ((TR * a.SW + kq - 1) / kq) * kq;
-  a.S_dy = pad_stride(a.npos);
-  a.dslots = nco * a.TR * a.Qd;
-  a.xslots = nci * a.xh * a.Qx;
-  a.S_x = pad_stride(a.npos + hr * a.SW + hc + 4);
-  for (int t = 0; t < T; ++t) {
-    a.tapoff[t] = (tap_dr[t] - min_dr) * a.SW + (tap_dc[t] - min_dc);
-    a.tap_u[t] = tap_u[t];
-    a.tap_v[t] = tap_v[t];
-  }
-  int shift = 0;
-  while ((1 << shift) < a.SW && shift < 6) ++shift;
-  a.swp_shift = shift;
-  a.rpi = 64 >> shift;
-  a.inv_TR = 1.0f / (float)a.TR;
-  a.inv_xh = 1.0f / (float)a.xh;
-  a.vec_dy = (OW % 4 == 0) && (((uintptr_t)dy & 15) == 0) && (OW / 4 <= 64);
-  a.vec_x = (IW % 4 == 0) && (((uintptr_t)x & 15) == 0) && (IW / 4 <= 64);
-  a.qshift_dy = a.qshift_x = 0;
-  while ((1 << a.qshift_dy) < OW / 4 && a.qshift_dy < 6) ++a.qshift_dy;
-  while ((1 << a.qshift_x) < IW / 4 && a.qshift_x < 6) ++a.qshift_x;
-  const int co_chunks = (Cout + CO_CHUNK - 1) / CO_CHUNK;
-  const int ci_chunks = (Cin + CI_CHUNK - 1) / CI_CHUNK;
-  int G = 512 / (co_chunks * ci_chunks);
-  if (G < 64) G = 64;
-  if (G > a.total_tiles) G = a.total_tiles;
-  if (G > max_rows) G = (int)max_rows;
-  size_t shmem = ((size_t)nco_alloc * a.S_dy + (size_t)nci * a.S_x) * sizeof(float);
-  const int ncit_h = (nci + 15) / 16;
-  const int NTsel = T >= 9 ? 9 : (T >= 4 ? 4 : T);  // taps per pass: 1, 2, 3, 4 or 9
-  const size_t red_bytes = (size_t)3 * (ncit_h * NTsel + 1) * 256 * sizeof(float);  // cross-wave reduction scratch
-  if (shmem < red_bytes) shmem = red_bytes;
-  a.dump = (int)(shmem / sizeof(float));
-  shmem += 16;
-  PG_REQUIRE(shmem <= 160 * 1024, PG_ESHAPE, "pg_conv2d_wgrad: LDS %zu B over budget", shmem);
-  dim3 grid((unsigned)G, (unsigned)co_chunks, (unsigned)ci_chunks);
-#define PG_WG(NT, NC)                                                                              \
-  {                                                                                               \
-    if (a.prefetch) hipLaunchKernelGGL((conv_wgrad_kernel<NT, NC, true>), grid, dim3(WG_THREADS), shmem, st, a);  \
-    else hipLaunchKernelGGL((conv_wgrad_kernel<NT, NC, false>), grid, dim3(WG_THREADS), shmem, st, a);            \
-  }
-  if (ncit_h <= 1) {
-    switch (NTsel) { case 1: PG_WG(1, 1); break; case 2: PG_WG(2, 1); break; case 3: PG_WG(3, 1); break;
-                     case 4: PG_WG(4, 1); break; default: PG_WG(9, 1); break; }
-  } else {
-    switch (NTsel) { case 1: PG_WG(1, 2); break; case 2: PG_WG(2, 2); break; case 3: PG_WG(3, 2); break;
-                     case 4: PG_WG(4, 2); break; default: PG_WG(9, 2); break; }
-  }
-#undef PG_WG
-  PG_LAUNCH_CHECK("pg_conv2d_wgrad");
-  launch_reduce(workspace, stride, G, dw, db, Cout, Cin, KH, KW, T, tap_u, tap_v, st);
+  launch_reduce(workspace, p.stride, r.G, dw, db, Cout, Cin, KH, KW, T, tap_u, tap_v, st);
   PG_LAUNCH_CHECK("pg_conv2d_wgrad(reduce)");
+  return 0;
+}
+
+// Host only, no device call: the route of a problem given as integers (include/pg_hip.h). flags: PG_WGR_*.
+PG_EXPORT int pg_conv2d_wgrad_route(int N, int Cin, int IH, int IW, int Cout, int OH, int OW, int KH, int KW, int T,
+                                    const int* tap_dr, const int* tap_dc, int in_act, int flags, int* out, int n_out) {
+  PG_REQUIRE(tap_dr && tap_dc && out && n_out >= PG_WGR_ROUTE_INTS, PG_EINVAL, "pg_conv2d_wgrad_route: null pointer or short output array");
+  PG_REQUIRE(N > 0 && Cin > 0 && Cout > 0 && IH > 0 && IW > 0 && OH > 0 && OW > 0 && KH > 0 && KW > 0, PG_EINVAL,
+             "pg_conv2d_wgrad_route: non-positive dimension");
+  PG_REQUIRE(T >= 1 && T <= PG_MAX_TAPS, PG_ESHAPE, "pg_conv2d_wgrad_route: T=%d not in [1,%d]", T, PG_MAX_TAPS);
+  PG_REQUIRE(in_act >= PG_ACT_NONE && in_act <= PG_ACT_GELU, PG_EINVAL, "pg_conv2d_wgrad_route: bad in_act");
+  const WgProblem p = wg_problem(N, Cin, IH, IW, Cout, OH, OW, KH, KW, T, tap_dr, tap_dc, in_act, (flags & PG_WGR_HAS_BIAS) != 0,
+                                 !(flags & PG_WGR_X_MISALIGNED), !(flags & PG_WGR_DY_MISALIGNED));
+  WgRoute r;
+  const int rc = wgrad_route(p, r);
+  if (rc) {
+    pg_set_error("%s", r.msg);
+    return rc;
+  }
+  const int v[PG_WGR_ROUTE_INTS] = {
+      r.family, r.t[0], r.t[1], r.t[2], r.t[3], r.gx, r.gy, r.gz, r.block, (int)r.shmem,
+      r.G, r.TR, r.tiles_per_img, (int)r.total, r.nseg, r.seg_rows, r.PBR, r.vec_dy, r.vec_x, (int)reduce_grid(p),
+      r.hr, r.copies, r.passes, (int)p.max_rows};
+  for (int i = 0; i < PG_WGR_ROUTE_INTS; ++i) out[i] = v[i];
   return 0;
 }

@@ -24,7 +24,7 @@
 // the fp32-MFMA kernel; phase ablation with PG_WB_DBG and the variants that were tried and dropped
 // (producer / consumer waves, two half-workgroups in opposite phases): profiles/README.md, round 2,
 // items 11-13, sources under tools/exp/rejected/.
-#include "common.h"
+#include "conv_wgrad_route.h"
 #include <stdlib.h>
 
 namespace {
@@ -38,22 +38,7 @@ constexpr int WB_CO = 64;   // dy channels per workgroup (4 MFMA row tiles: 2 pe
 constexpr int WB_CI = 32;   // x channels per workgroup (2 MFMA column tiles: 1 per wave)
 constexpr int WB_DS = 3;    // staging slots (8 pixels each) per thread per tile: dy
 constexpr int WB_XS = 3;    // ... and x
-constexpr int WB_MAXT = 9;
 constexpr int WB_LDS_BUDGET = 76 * 1024;  // two workgroups per CU
-
-struct WbArgs {
-  const float* x; const float* dy; float* part;
-  long part_stride;
-  int N, Cin, Cout, H, W, T;
-  int TR, xh, tiles_per_img, total_tiles, min_dr;
-  int PBR, dpb, xpb, ksteps;   // pixel blocks per row / per dy tile / per x tile; K steps per tile
-  int dslots, xslots;
-  int ndc, dcs[3];             // distinct column shifts (copies)
-  int x_off16;                 // first 16-byte entry of the x area
-  int in_act, has_bias;
-  int dbg;                     // ablation switches (PG_WB_DBG: 1 no loads, 2 no commit, 4 no MFMA), 0 in production
-  int tap_base[WB_MAXT];       // entry offset of tap t inside the x area: copy plane + row-shift blocks
-};
 
 // 8 fp32 -> three bf16x8 (h, m, l pieces), element 2i in the low half of dword i.
 // The pieces are TRUNCATIONS (h = top 16 bits of x, m = top 16 bits of x - h, l = x - h - m, whose
@@ -396,20 +381,6 @@ __global__ void __launch_bounds__(64 * WV, WV / 2) conv_wgrad_b3_kernel(const Wb
 // the rows above it are still in the ring (hr + 1 rows; a segment starts with hr x-only steps). 512 threads: waves 0-3 stage
 // the dy row, waves 4-7 the x row (one 8-pixel slot per thread); every wave owns one 16-channel dy tile x two ci tiles x T taps.
 // LDS: dy 12 KB + x copies * (hr + 1) * 12 KB (2x2: 60 KB, two workgroups per CU).
-struct WrArgs {
-  const float* x; const float* dy; float* part;
-  long part_stride;
-  int N, Cin, Cout, H, W, T;
-  int nseg, seg_rows, units;   // row segments per image, rows per segment, N * nseg work units (strided over blockIdx.x)
-  int P, RB;                   // x-only steps in front of a segment (= hr), ring rows (= hr + 1)
-  int max_dr;
-  int ndc, dcs[3];             // distinct column shifts (copies)
-  int x_off16;                 // first 16-byte entry of the x area
-  int in_act, has_bias;
-  int dbg;                     // ablation switches (PG_WB_DBG: 1 no loads, 2 no commit, 4 no MFMA, 8 no fragment reads either), 0 in production
-  int copy_of[6], q_of[6];     // per tap: its x copy; rows back from the newest ring row (max_dr - dr)
-};
-
 // staging slot kind of slot index k (slots e = tid + 512 k; the dy slots come first): 0 dy, 1 x, 2 none for EVERY thread, or -1 mixed
 // (decided per wave at run time) — compile-time kinds keep the unrolled commit code to the branches that can occur
 constexpr int wr_kind(int k, int dslots, int xslots) {
@@ -664,20 +635,6 @@ __global__ void __launch_bounds__(512, (WM == 1 || (WM == 2 && WN == 4) || (WM =
 // are zero in both operands.
 // Per K step a wave holds the A fragments of all NC copies (NC x 3 pieces) and walks the NR row shifts with one
 // set of B fragments each: NC * 3 + NR * 3 LDS reads for NR * NC * 6 MFMAs.
-struct WsArgs {
-  const float* x; const float* dy; float* part;
-  long part_stride;
-  int N, Cin, Cout, H, W, T;
-  int TR, xh, tiles_per_img, total_tiles, min_dr, min_dc;
-  int PBR, dpb, xpb, ksteps;
-  int dslots, xslots;
-  int x_off16;                 // first 16-byte entry of the x area (behind NC dy copies x 3 pieces)
-  int v0;                      // dy copy with dc == 0 (bias sums)
-  int wpart;                   // W % 8 != 0: the last pixel block of a row holds 4 pixels
-  int in_act, has_bias;
-  int tap_of[9];               // caller's tap index of grid position (ri, ci): ri * NC + ci
-};
-
 template <int NR, int NC>
 __global__ void __launch_bounds__(WB_THREADS, 2) conv_wgrad_b3s_kernel(const WsArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -906,21 +863,21 @@ __global__ void __launch_bounds__(WB_THREADS, 2) conv_wgrad_b3s_kernel(const WsA
 
 }  // namespace
 
-// Launches the bf16x3 kernel when it takes the problem; returns the number of partial rows written
-// (the caller runs the reduction over them), 0 when the shape stays on the fp32 kernels, < 0 on a
-// launch error. Called by pg_conv2d_wgrad (conv_wgrad.hip) only.
-int pg_wgrad_b3_launch(const float* x, const float* dy, float* part, long part_stride, long max_rows,
-                       int has_bias, int N, int Cin, int IH, int IW, int Cout, int OH, int OW, int T,
-                       const int* tap_dr, const int* tap_dc, int in_act, hipStream_t st) {
+// The plan of the x-copy and row-ring kernels (host only, no HIP call): 1 and the route when one of them takes the problem — r.family
+// says which —, 0 when the shape stays on the other kernels. Read by wgrad_route (conv_wgrad.hip) only.
+int pg_wgrad_b3_plan(const WgProblem& p, WgRoute& r) {
   static const bool on = PG_AB_ON("PG_WGRAD_B3");
   if (!on) return 0;
-  if (IH != OH || IW != OW || OW % 4 != 0 || Cout % 32 != 0 || Cin % WB_CI != 0) return 0;
+  const int N = p.N, Cin = p.Cin, Cout = p.Cout, OH = p.OH, OW = p.OW, T = p.T;
+  const int* tap_dr = p.tap_dr;
+  const int* tap_dc = p.tap_dc;
+  if (p.IH != OH || p.IW != OW || OW % 4 != 0 || Cout % 32 != 0 || Cin % WB_CI != 0) return 0;
   int MR = Cout % WB_CO == 0 ? 2 : 1;  // 64 or 32 dy channels per workgroup
   if (MR == 1 && T == 1) return 0;  // 1x1 with 32 output channels: too little MFMA work per staged tile (measured on
                                     // PixelCNN's 64 -> 32 layers: 70.9 vs 70.6 k img/s against the fp32 direct-fragment kernel)
   if (!(T == 1 || T == 2 || T == 3 || T == 4 || T == 6 || T == 9)) return 0;
-  if ((((uintptr_t)x | (uintptr_t)dy) & 15) != 0) return 0;
-  WbArgs a;
+  if (!(p.x_al16 && p.dy_al16)) return 0;
+  WbArgs& a = r.wb;
   int min_dr = tap_dr[0], max_dr = tap_dr[0];
   a.ndc = 0;
   int copy_of[WB_MAXT];
@@ -936,6 +893,7 @@ int pg_wgrad_b3_launch(const float* x, const float* dy, float* part, long part_s
   for (int v = a.ndc; v < 3; ++v) a.dcs[v] = 0;
   const int hr = max_dr - min_dr;
   const int PBR = (OW + 7) / 8;  // W % 8 == 4: the last pixel block of a row is half full
+  r.hr = hr; r.copies = a.ndc; r.PBR = PBR; r.vec_dy = r.vec_x = 1;
   // row-ring kernel (round 6; PG_WGRAD_B3_RING=0 for A/B): 32-pixel rows; wave tiles (WM x WN 16-channel tiles) by shape:
   //   (1, 2) = 64 x 64 per workgroup, two workgroups per CU: the shapes with a row halo or three taps;
   //   (2, 2) = 128 x 64 when Cout % 128 == 0: dy AND x of a 64 -> 128 layer staged once;
@@ -960,26 +918,26 @@ int pg_wgrad_b3_launch(const float* x, const float* dy, float* part, long part_s
     const bool cfg_ok = (WM == 1 && WN == 2) || (WM == 2 && WN == 2 && T <= 4) || (WM == 4 && WN == 4 && T == 1) || (WM == 4 && WN == 2 && T <= 2) ||
                         (WM == 2 && WN == 4 && T == 1);
     const bool shape_ok = cfg_ok && Cout % (64 * WM) == 0 && Cin % (32 * WN) == 0;
-    WrArgs r;
-    r.ndc = a.ndc;
-    for (int v = 0; v < 3; ++v) r.dcs[v] = a.dcs[v];
-    r.RB = hr + 1; r.P = hr; r.max_dr = max_dr;
-    const int dplane = 4 * WM * 64, xplane = 2 * WN * r.RB * 64;
-    const size_t shmem = ((size_t)3 * dplane + (size_t)r.ndc * 3 * xplane) * 16;
+    WrArgs& w = r.wr;
+    w.ndc = a.ndc;
+    for (int v = 0; v < 3; ++v) w.dcs[v] = a.dcs[v];
+    w.RB = hr + 1; w.P = hr; w.max_dr = max_dr;
+    const int dplane = 4 * WM * 64, xplane = 2 * WN * w.RB * 64;
+    const size_t shmem = ((size_t)3 * dplane + (size_t)w.ndc * 3 * xplane) * 16;
     const bool one_wg = (WM > 1 && !(WM == 2 && WN == 4) && !(WM == 2 && WN == 2 && T <= 2)) || shmem > (size_t)WB_LDS_BUDGET;   // the kernel's launch bounds / an LDS footprint above half a CU: two waves per SIMD (one 8-wave workgroup per CU)
     if (shape_ok && shmem <= (one_wg ? (size_t)150 * 1024 : (size_t)WB_LDS_BUDGET)) {
-      r.x = x; r.dy = dy; r.part = part; r.part_stride = part_stride;
-      r.N = N; r.Cin = Cin; r.Cout = Cout; r.H = OH; r.W = OW; r.T = T;
-      r.x_off16 = 3 * dplane;
-      r.in_act = in_act; r.has_bias = has_bias;
+      w.x = nullptr; w.dy = nullptr; w.part = nullptr; w.part_stride = p.stride;
+      w.N = N; w.Cin = Cin; w.Cout = Cout; w.H = OH; w.W = OW; w.T = T;
+      w.x_off16 = 3 * dplane;
+      w.in_act = p.in_act; w.has_bias = p.has_bias;
 #ifdef PG_ABLATE
-      { const char* e = getenv("PG_WB_DBG"); r.dbg = e ? atoi(e) : 0; }
+      { const char* e = getenv("PG_WB_DBG"); w.dbg = e ? atoi(e) : 0; }
 #else
-      r.dbg = 0;
+      w.dbg = 0;
 #endif
       for (int t = 0; t < 6; ++t) {
-        r.copy_of[t] = t < T ? copy_of[t] : 0;
-        r.q_of[t] = t < T ? max_dr - tap_dr[t] : 0;
+        w.copy_of[t] = t < T ? copy_of[t] : 0;
+        w.q_of[t] = t < T ? max_dr - tap_dr[t] : 0;
       }
       const int co_chunks = Cout / (64 * WM), ci_chunks = Cin / (32 * WN);
       long G = (one_wg ? 256 : 512) / ((long)co_chunks * ci_chunks);
@@ -988,34 +946,16 @@ int pg_wgrad_b3_launch(const float* x, const float* dy, float* part, long part_s
       // (every segment starts with hr x-only steps)
       int nseg = 1;
       while ((long)N * nseg < G && OH % (2 * nseg) == 0 && OH / (2 * nseg) >= 8) nseg *= 2;
-      r.nseg = nseg; r.seg_rows = OH / nseg; r.units = N * nseg;
-      if (G > r.units) G = r.units;
-      if (G > max_rows) G = max_rows;
-      dim3 grid((unsigned)G, (unsigned)co_chunks, (unsigned)ci_chunks);
-#define PG_WR_LAUNCH(TT, M_, N_)                                                                                  \
-  {                                                                                                               \
-    static const hipError_t attr_ = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad_b3r_kernel<TT, M_, N_>), \
-                                                        hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);  \
-    if (attr_ != hipSuccess) return -1;                                                                           \
-    hipLaunchKernelGGL((conv_wgrad_b3r_kernel<TT, M_, N_>), grid, dim3(512), shmem, st, r);                       \
-  }
-#define PG_WR_BY_T(M_, N_)                                         \
-  switch (T) {                                                     \
-    case 1: PG_WR_LAUNCH(1, M_, N_) break;                         \
-    case 2: PG_WR_LAUNCH(2, M_, N_) break;                         \
-    case 3: PG_WR_LAUNCH(3, M_, N_) break;                         \
-    default: PG_WR_LAUNCH(4, M_, N_) break;                        \
-  }
-      if (WM == 4 && WN == 4) PG_WR_LAUNCH(1, 4, 4)
-      else if (WM == 2 && WN == 4) PG_WR_LAUNCH(1, 2, 4)
-      else if (WM == 4) { if (T == 1) PG_WR_LAUNCH(1, 4, 2) else PG_WR_LAUNCH(2, 4, 2) }
-      else if (WM == 2) PG_WR_BY_T(2, 2)
-      else if (T == 6) PG_WR_LAUNCH(6, 1, 2)
-      else PG_WR_BY_T(1, 2)
-#undef PG_WR_BY_T
-#undef PG_WR_LAUNCH
-      if (hipGetLastError() != hipSuccess) return -1;
-      return (int)G;
+      w.nseg = nseg; w.seg_rows = OH / nseg; w.units = N * nseg;
+      if (G > w.units) G = w.units;
+      if (G > p.max_rows) G = p.max_rows;
+      r.family = WGF_RING;
+      // the instantiation's tap count: one-tap tiles and (4, 2) carry T = 1 / min(T, 2), the others 1..4 or 6
+      r.t[0] = (WM == 4 && WN == 4) || (WM == 2 && WN == 4) ? 1 : WM == 4 ? (T == 1 ? 1 : 2) : (WM == 1 && T == 6) ? 6 : (T <= 3 ? T : 4);
+      r.t[1] = WM; r.t[2] = WN; r.t[3] = 0;
+      r.gx = (int)G; r.gy = co_chunks; r.gz = ci_chunks; r.block = 512; r.shmem = shmem; r.G = (int)G;
+      r.TR = 1; r.tiles_per_img = OH; r.total = w.units; r.nseg = nseg; r.seg_rows = w.seg_rows;
+      return 1;
     }
   }
   // 64 dy channels per workgroup: 8 waves (four per SIMD, 2 staging slots per thread); PG_WGRAD_B3_WAVES=4 for A/B
@@ -1047,7 +987,7 @@ int pg_wgrad_b3_launch(const float* x, const float* dy, float* part, long part_s
   const int waves = big ? 8 : (MR == 2 && T <= 4) ? env_waves : 4;  // (6 and 9 taps: the accumulators no longer fit 128 registers)
   if (!big) TR = pick_rows(wb_co, wb_ci, waves == 8 ? 2L * 512 : (long)WB_DS * WB_THREADS);
   if (TR == 0) return 0;
-  a.x = x; a.dy = dy; a.part = part; a.part_stride = part_stride;
+  a.x = nullptr; a.dy = nullptr; a.part = nullptr; a.part_stride = p.stride;
   a.N = N; a.Cin = Cin; a.Cout = Cout; a.H = OH; a.W = OW; a.T = T;
   a.TR = TR; a.xh = TR + hr; a.min_dr = min_dr;
   a.tiles_per_img = (OH + TR - 1) / TR;
@@ -1055,7 +995,7 @@ int pg_wgrad_b3_launch(const float* x, const float* dy, float* part, long part_s
   a.PBR = PBR; a.dpb = TR * PBR; a.xpb = a.xh * PBR; a.ksteps = a.dpb / 4;
   a.dslots = wb_co * a.dpb; a.xslots = wb_ci * a.xpb;
   a.x_off16 = 3 * (2 * MR) * a.dpb * 16;
-  a.in_act = in_act; a.has_bias = has_bias;
+  a.in_act = p.in_act; a.has_bias = p.has_bias;
 #ifdef PG_ABLATE
   static const int dbg = []() { const char* e = getenv("PG_WB_DBG"); return e ? atoi(e) : 0; }();
   a.dbg = dbg;
@@ -1070,14 +1010,57 @@ int pg_wgrad_b3_launch(const float* x, const float* dy, float* part, long part_s
   long G = 512 / ((long)co_chunks * ci_chunks);
   if (G < 16) G = 16;
   if (G > a.total_tiles) G = a.total_tiles;
-  if (G > max_rows) G = max_rows;
-  dim3 grid((unsigned)G, (unsigned)co_chunks, (unsigned)ci_chunks);
-  if (big) {
+  if (G > p.max_rows) G = p.max_rows;
+  r.family = WGF_XCOPY;
+  r.t[0] = T; r.t[1] = MR; r.t[2] = waves; r.t[3] = CIT;
+  r.gx = (int)G; r.gy = co_chunks; r.gz = ci_chunks; r.block = 64 * waves; r.shmem = shmem; r.G = (int)G;
+  r.TR = TR; r.tiles_per_img = a.tiles_per_img; r.total = a.total_tiles;
+  return 1;
+}
+
+// Launches the instantiation the route names (family x-copy or ring). 0, or -1 when the launch failed. Called by pg_conv2d_wgrad only.
+int pg_wgrad_b3_run(const WgRoute& r, const float* x, const float* dy, float* part, hipStream_t st) {
+  const dim3 grid((unsigned)r.gx, (unsigned)r.gy, (unsigned)r.gz);
+  const size_t shmem = r.shmem;
+  const int T = r.t[0];
+  if (r.family == WGF_RING) {
+    WrArgs w = r.wr;
+    w.x = x; w.dy = dy; w.part = part;
+    const int WM = r.t[1], WN = r.t[2];
+#define PG_WR_LAUNCH(TT, M_, N_)                                                                                  \
+  {                                                                                                               \
+    static const hipError_t attr_ = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad_b3r_kernel<TT, M_, N_>), \
+                                                        hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);  \
+    if (attr_ != hipSuccess) return -1;                                                                           \
+    hipLaunchKernelGGL((conv_wgrad_b3r_kernel<TT, M_, N_>), grid, dim3(512), shmem, st, w);                       \
+  }
+#define PG_WR_BY_T(M_, N_)                                         \
+  switch (T) {                                                     \
+    case 1: PG_WR_LAUNCH(1, M_, N_) break;                         \
+    case 2: PG_WR_LAUNCH(2, M_, N_) break;                         \
+    case 3: PG_WR_LAUNCH(3, M_, N_) break;                         \
+    default: PG_WR_LAUNCH(4, M_, N_) break;                        \
+  }
+    if (WM == 4 && WN == 4) PG_WR_LAUNCH(1, 4, 4)
+    else if (WM == 2 && WN == 4) PG_WR_LAUNCH(1, 2, 4)
+    else if (WM == 4) { if (T == 1) PG_WR_LAUNCH(1, 4, 2) else PG_WR_LAUNCH(2, 4, 2) }
+    else if (WM == 2) PG_WR_BY_T(2, 2)
+    else if (T == 6) PG_WR_LAUNCH(6, 1, 2)
+    else PG_WR_BY_T(1, 2)
+#undef PG_WR_BY_T
+#undef PG_WR_LAUNCH
+    if (hipGetLastError() != hipSuccess) return -1;
+    return 0;
+  }
+  WbArgs a = r.wb;
+  a.x = x; a.dy = dy; a.part = part;
+  const int MR = r.t[1], waves = r.t[2];
+  if (r.t[3] == 4) {  // big tiles
     if (T == 1 && MR == 4) hipLaunchKernelGGL((conv_wgrad_b3_kernel<1, 4, 8, 4>), grid, dim3(512), shmem, st, a);
     else if (T == 1) hipLaunchKernelGGL((conv_wgrad_b3_kernel<1, 2, 8, 4>), grid, dim3(512), shmem, st, a);
     else hipLaunchKernelGGL((conv_wgrad_b3_kernel<2, 2, 8, 4>), grid, dim3(512), shmem, st, a);
     if (hipGetLastError() != hipSuccess) return -1;
-    return (int)G;
+    return 0;
   }
 #define PG_WB(TT)                                                                                        \
   {                                                                                                      \
@@ -1100,24 +1083,25 @@ int pg_wgrad_b3_launch(const float* x, const float* dy, float* part, long part_s
 #undef PG_WB8
 #undef PG_WB
   if (hipGetLastError() != hipSuccess) return -1;
-  return (int)G;
+  return 0;
 }
 
-// The "shifted dy" kernel (32 co x 32 ci per workgroup, full tap grids): same return convention.
-int pg_wgrad_b3s_launch(const float* x, const float* dy, float* part, long part_stride, long max_rows,
-                        int has_bias, int N, int Cin, int IH, int IW, int Cout, int OH, int OW, int T,
-                        const int* tap_dr, const int* tap_dc, int in_act, hipStream_t st) {
+// The plan of the "shifted dy" kernel (32 co x 32 ci per workgroup, full tap grids): same convention.
+int pg_wgrad_b3s_plan(const WgProblem& p, WgRoute& r) {
   static const bool on = PG_AB_ON("PG_WGRAD_B3") && PG_AB_ON("PG_WGRAD_B3S");
   if (!on) return 0;
-  if (IH != OH || IW != OW || OW % 4 != 0 || Cout % 32 != 0 || Cin % WB_CI != 0 || T < 2 || T > 9) return 0;
-  if ((((uintptr_t)x | (uintptr_t)dy) & 15) != 0) return 0;
+  const int N = p.N, Cin = p.Cin, Cout = p.Cout, OH = p.OH, OW = p.OW, T = p.T;
+  const int* tap_dr = p.tap_dr;
+  const int* tap_dc = p.tap_dc;
+  if (p.IH != OH || p.IW != OW || OW % 4 != 0 || Cout % 32 != 0 || Cin % WB_CI != 0 || T < 2 || T > 9) return 0;
+  if (!(p.x_al16 && p.dy_al16)) return 0;
   int min_dr, min_dc, hr, hc;
   pg_tap_extent(T, tap_dr, tap_dc, min_dr, hr, min_dc, hc);
   const int max_dc = min_dc + hc;
   const int NR = hr + 1, NC = hc + 1;
   if (min_dc < -1 || max_dc > 1 || NR > 3 || NR * NC != T) return 0;
-  if (has_bias && (min_dc > 0 || max_dc < 0)) return 0;  // the bias sums read the unshifted copy
-  WsArgs a;
+  if (p.has_bias && (min_dc > 0 || max_dc < 0)) return 0;  // the bias sums read the unshifted copy
+  WsArgs& a = r.ws;
   for (int i = 0; i < 9; ++i) a.tap_of[i] = -1;
   for (int t = 0; t < T; ++t) {
     const int slot = (tap_dr[t] - min_dr) * NC + (tap_dc[t] - min_dc);
@@ -1135,7 +1119,9 @@ int pg_wgrad_b3s_launch(const float* x, const float* dy, float* part, long part_
     if (tr >= OH) break;
   }
   if (TR == 0) return 0;
-  a.x = x; a.dy = dy; a.part = part; a.part_stride = part_stride;
+  if (!((NR == 3 && NC == 3) || (NR == 2 && NC == 2) || (NR == 1 && NC == 3) || (NR == 2 && NC == 1) || (NR == 2 && NC == 3)))
+    return 0;  // the instantiated grids
+  a.x = nullptr; a.dy = nullptr; a.part = nullptr; a.part_stride = p.stride;
   a.N = N; a.Cin = Cin; a.Cout = Cout; a.H = OH; a.W = OW; a.T = T;
   a.TR = TR; a.xh = TR + hr; a.min_dr = min_dr; a.min_dc = min_dc;
   a.tiles_per_img = (OH + TR - 1) / TR;
@@ -1145,22 +1131,35 @@ int pg_wgrad_b3s_launch(const float* x, const float* dy, float* part, long part_
   a.x_off16 = NC * 3 * (2 * a.dpb * 16);
   a.v0 = -min_dc;
   a.wpart = (OW % 8) != 0;
-  a.in_act = in_act; a.has_bias = has_bias;
+  a.in_act = p.in_act; a.has_bias = p.has_bias;
   const size_t shmem = ((size_t)a.x_off16 + (size_t)3 * (2 * a.xpb * 16)) * 16;
   const int co_chunks = Cout / 32, ci_chunks = Cin / WB_CI;
   long G = 512 / ((long)co_chunks * ci_chunks);
   if (G < 16) G = 16;
   if (G > a.total_tiles) G = a.total_tiles;
-  if (G > max_rows) G = max_rows;
-  dim3 grid((unsigned)G, (unsigned)co_chunks, (unsigned)ci_chunks);
+  if (G > p.max_rows) G = p.max_rows;
+  r.family = WGF_SHIFTED;
+  r.t[0] = NR; r.t[1] = NC; r.t[2] = r.t[3] = 0;
+  r.gx = (int)G; r.gy = co_chunks; r.gz = ci_chunks; r.block = WB_THREADS; r.shmem = shmem; r.G = (int)G;
+  r.TR = TR; r.tiles_per_img = a.tiles_per_img; r.total = a.total_tiles;
+  r.PBR = PBR; r.vec_dy = r.vec_x = 1; r.hr = hr; r.copies = NC;
+  return 1;
+}
+
+int pg_wgrad_b3s_run(const WgRoute& r, const float* x, const float* dy, float* part, hipStream_t st) {
+  WsArgs a = r.ws;
+  a.x = x; a.dy = dy; a.part = part;
+  const dim3 grid((unsigned)r.gx, (unsigned)r.gy, (unsigned)r.gz);
+  const size_t shmem = r.shmem;
+  const int NR = r.t[0], NC = r.t[1];
 #define PG_WS(R, C) hipLaunchKernelGGL((conv_wgrad_b3s_kernel<R, C>), grid, dim3(WB_THREADS), shmem, st, a)
   if (NR == 3 && NC == 3) PG_WS(3, 3);
   else if (NR == 2 && NC == 2) PG_WS(2, 2);
   else if (NR == 1 && NC == 3) PG_WS(1, 3);
   else if (NR == 2 && NC == 1) PG_WS(2, 1);
   else if (NR == 2 && NC == 3) PG_WS(2, 3);
-  else return 0;
+  else return -1;
 #undef PG_WS
   if (hipGetLastError() != hipSuccess) return -1;
-  return (int)G;
+  return 0;
 }

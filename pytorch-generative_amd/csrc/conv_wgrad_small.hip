@@ -15,7 +15,7 @@
 // A wave owns one 16-co tile and all four column tiles: per K step 1 + 4 fragment reads (ds_read_b32) and
 // 4 MFMAs. Persistent workgroups over (image, row tile), one row of partial sums per workgroup, then
 // conv_wgrad.hip's deterministic reduction.
-#include "common.h"
+#include "conv_wgrad_route.h"
 
 namespace {
 
@@ -24,19 +24,6 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int SW_THREADS = 256;
 constexpr int SW_CO = 64;
-constexpr int SW_COLS = 64;
-
-struct SwArgs {
-  const float* x; const float* dy; float* part;
-  long part_stride;
-  int N, Cin, Cout, H, W, T;
-  int TR, tiles_per_img, total_tiles;
-  int min_dr, min_dc, tile_w, xrows;   // x tile: xrows x tile_w per channel, origin (row0 + min_dr, min_dc)
-  int dstride;                         // dy tile row stride (floats), TR * W + pad
-  int ncols, bias_col;                 // used columns (Cin * T [+ 1]); index of the ones column or -1
-  int in_act;
-  int col_off[SW_COLS];                // LDS float offset of column j inside the x tile (ci plane + tap shift); -1: unused
-};
 
 __global__ void __launch_bounds__(SW_THREADS) conv_wgrad_small_kernel(const SwArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -125,44 +112,53 @@ __global__ void __launch_bounds__(SW_THREADS) conv_wgrad_small_kernel(const SwAr
 
 }  // namespace
 
-// Launches the small-Cin kernel when it takes the problem; returns the number of partial rows written
-// (the caller reduces them), 0 when the shape stays on the general kernels, < 0 on a launch error.
-int pg_wgrad_small_launch(const float* x, const float* dy, float* part, long part_stride, long max_rows,
-                          int has_bias, int N, int Cin, int IH, int IW, int Cout, int OH, int OW, int T,
-                          const int* tap_dr, const int* tap_dc, int in_act, hipStream_t st) {
+// The plan of the small-Cin kernel (host only): 1 and the route when it takes the problem, 0 when the shape stays on the general
+// kernels. Read by wgrad_route (conv_wgrad.hip) only.
+int pg_wgrad_small_plan(const WgProblem& p, WgRoute& r) {
   static const bool on = PG_AB_ON("PG_WGRAD_SMALL");
   if (!on) return 0;
+  const int N = p.N, Cin = p.Cin, Cout = p.Cout, OH = p.OH, OW = p.OW, T = p.T;
   // >= 32 output channels: with 16 (ImageGPT's 3x3 input layer) three of the four waves idle and the general
   // kernel measured faster (ImageGPT 100.0 k vs 99.2 k img/s)
-  if (Cin > 4 || Cout < 32 || IH != OH || IW != OW || OW % 4 != 0 || Cin * T + (has_bias ? 1 : 0) > SW_COLS || T < 2) return 0;
-  if ((((uintptr_t)dy) & 15) != 0) return 0;
-  SwArgs a;
+  if (Cin > 4 || Cout < 32 || p.IH != OH || p.IW != OW || OW % 4 != 0 || Cin * T + (p.has_bias ? 1 : 0) > SW_COLS || T < 2) return 0;
+  if (!p.dy_al16) return 0;
+  SwArgs& a = r.sw;
   int min_dr, min_dc, hr, hc;
-  pg_tap_extent(T, tap_dr, tap_dc, min_dr, hr, min_dc, hc);
+  pg_tap_extent(T, p.tap_dr, p.tap_dc, min_dr, hr, min_dc, hc);
   // rows per tile: about 128 pixels of dy per channel (64 x 132 floats = 33 KB) — two workgroups per CU
   int TR = 128 / OW;
   if (TR < 1) TR = 1;
   if (TR > OH) TR = OH;
-  a.x = x; a.dy = dy; a.part = part; a.part_stride = part_stride;
+  a.x = nullptr; a.dy = nullptr; a.part = nullptr; a.part_stride = p.stride;
   a.N = N; a.Cin = Cin; a.Cout = Cout; a.H = OH; a.W = OW; a.T = T;
   a.TR = TR; a.tiles_per_img = (OH + TR - 1) / TR; a.total_tiles = N * a.tiles_per_img;
   a.min_dr = min_dr; a.min_dc = min_dc; a.tile_w = OW + hc; a.xrows = TR + hr;
   a.dstride = TR * OW + 4;
-  a.in_act = in_act;
+  a.in_act = p.in_act;
   a.ncols = Cin * T;
-  a.bias_col = has_bias ? a.ncols : -1;
+  a.bias_col = p.has_bias ? a.ncols : -1;
   for (int j = 0; j < SW_COLS; ++j) a.col_off[j] = -1;
   for (int ci = 0; ci < Cin; ++ci)
     for (int t = 0; t < T; ++t)
-      a.col_off[ci * T + t] = ci * a.xrows * a.tile_w + (tap_dr[t] - min_dr) * a.tile_w + (tap_dc[t] - min_dc);
+      a.col_off[ci * T + t] = ci * a.xrows * a.tile_w + (p.tap_dr[t] - min_dr) * a.tile_w + (p.tap_dc[t] - min_dc);
   const size_t shmem = ((size_t)SW_CO * a.dstride + (size_t)Cin * a.xrows * a.tile_w) * sizeof(float);
   if (shmem > 64 * 1024) return 0;
   const int co_chunks = (Cout + SW_CO - 1) / SW_CO;
   long G = 512 / co_chunks;
   if (G > a.total_tiles) G = a.total_tiles;
-  if (G > max_rows) G = max_rows;
+  if (G > p.max_rows) G = p.max_rows;
   if (G < 1) return 0;
-  hipLaunchKernelGGL(conv_wgrad_small_kernel, dim3((unsigned)G, (unsigned)co_chunks), dim3(SW_THREADS), shmem, st, a);
+  r.family = WGF_SMALL;
+  r.gx = (int)G; r.gy = co_chunks; r.gz = 1; r.block = SW_THREADS; r.shmem = shmem; r.G = (int)G;
+  r.TR = TR; r.tiles_per_img = a.tiles_per_img; r.total = a.total_tiles;
+  r.hr = hr; r.vec_dy = 1;
+  return 1;
+}
+
+int pg_wgrad_small_run(const WgRoute& r, const float* x, const float* dy, float* part, hipStream_t st) {
+  SwArgs a = r.sw;
+  a.x = x; a.dy = dy; a.part = part;
+  hipLaunchKernelGGL(conv_wgrad_small_kernel, dim3((unsigned)r.gx, (unsigned)r.gy), dim3(SW_THREADS), r.shmem, st, a);
   if (hipGetLastError() != hipSuccess) return -1;
-  return (int)G;
+  return 0;
 }

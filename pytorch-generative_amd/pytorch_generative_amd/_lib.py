@@ -60,6 +60,7 @@ SIGNATURES = {
          c_ip, c_i, c_f, c_z, c_s],
     ),
     "pg_conv2d_wgrad_workspace_floats": (c_z, [c_i, c_i, c_i]),
+    "pg_conv2d_wgrad_route": (c_i, [c_i] * 10 + [c_ip, c_ip] + [c_i] * 2 + [c_ip, c_i]),
     "pg_mul_inplace": (c_i, [c_f, c_f, c_z, c_s]),
     "pg_nchw_layernorm_fwd": (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_flt, c_s]),
     "pg_nchw_layernorm_bwd": (

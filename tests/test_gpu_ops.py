@@ -48,8 +48,9 @@ CONV_CASES = [
     (2, 5, 9, 11, 7, 3, 3, 1, 1, None, "B", None, True, True),          # odd sizes, OW % 4 != 0
     (1, 4, 64, 64, 8, 3, 3, 1, 1, None, None, None, False, True),       # 64x64: several row tiles
     (17, 32, 4, 4, 32, 3, 3, 1, 1, None, None, "gelu", True, True),     # 4x4 images: 15 per tile, partial last group
-    # shapes the bf16x3 weight-gradient kernel takes (Cout % 64 == 0, Cin % 32 == 0, W % 8 == 0)
-    (3, 32, 16, 16, 64, 3, 3, 1, 1, None, "B", "relu", False, True),    # 9 taps, 3 column shifts
+    # shapes the bf16x3 weight-gradient kernels take (Cout % 64 == 0, Cin % 32 == 0, W % 8 == 0); which one, per row, is what
+    # pg_conv2d_wgrad_route says (the weight gradient always runs ALL kh * kw taps here: wgrad_all) - tests/_wgrad_cases.py asserts it
+    (3, 32, 16, 16, 64, 3, 3, 1, 1, None, "B", "relu", False, True),    # 9 taps: the full 3x3 grid goes to the shifted-dy kernel first
     (2, 64, 12, 8, 64, 2, 3, 1, 1, "hw", None, None, False, False),     # 6 taps, W = 8, no bias
     (2, 32, 10, 16, 128, 1, 3, 0, 1, None, None, "gelu", True, True),   # 3 taps, two co chunks
     (2, 96, 7, 24, 64, 2, 1, 2, 0, "hw", None, "elu", False, True),     # 2 taps, ragged last row tile
@@ -61,7 +62,7 @@ CONV_CASES = [
     (2, 64, 32, 32, 128, 1, 3, 0, 1, None, None, None, False, True),     # 1x3: three copies, no halo (ring of one row), two co chunks
     (20, 64, 32, 32, 64, 2, 2, 1, 1, "hw", None, None, False, False),    # 20 images: whole-image units + segments, no bias
     (3, 128, 32, 32, 64, 2, 3, 1, 1, "hw", None, "relu", True, True),    # 2x3: six taps, three copies, 84 KB ring (one workgroup per CU)
-    (2, 64, 32, 32, 64, 3, 3, 1, 1, None, "A", None, False, True),       # masked 3x3 type A: four taps over three column copies
+    (2, 64, 32, 32, 64, 3, 3, 1, 1, None, "A", None, False, True),       # masked 3x3 type A: four taps forward; the weight gradient runs all nine, on the shifted-dy kernel (not the ring)
     (2, 128, 32, 32, 256, 2, 1, 2, 0, "hw", None, None, False, True),    # two taps: 128 x 64 wave tiles, two ci chunks
     (2, 256, 32, 32, 256, 1, 2, 0, 1, "hw", None, "elu", False, True),   # two taps 256 -> 256: the 256 x 64 tile
     # round 6: the overlapped 16-wave kernel (conv_b3q_kernel.h), two tiles per workgroup sharing one weight slab: 6 taps with >= 256
@@ -75,7 +76,8 @@ CONV_CASES = [
     (140, 69, 32, 32, 36, 1, 1, 0, 0, None, None, None, False, True),   # fp32-MFMA kernel (ragged channels), 560 tiles
     (30, 32, 64, 64, 64, 3, 3, 1, 1, None, None, "relu", False, True),  # 64x64 3x3: 22 row tiles per image
     (700, 32, 28, 28, 32, 3, 3, 1, 1, None, "B", "relu", False, True),  # PixelCNN residual conv at bench batch
-    # 32 output channels on the bf16x3 weight-gradient kernel (round 3: one MFMA row tile per wave)
+    # 32 output channels on the bf16x3 weight-gradient kernels (round 3: one MFMA row tile per wave; these full 3x3 grids have since
+    # moved to the shifted-dy kernel, the x-copy kernel's <T, 1> keeps the tap lists that are no grid)
     (3, 32, 16, 16, 32, 3, 3, 1, 1, None, "B", "relu", False, True),
     (20, 64, 32, 32, 32, 3, 3, 1, 1, None, None, "gelu", True, True),
     (2, 32, 8, 8, 32, 3, 3, 1, 1, None, None, "gelu", False, True),     # VD-VAE 8x8 level
@@ -96,18 +98,18 @@ CONV_CASES = [
     (3, 32, 12, 12, 32, 3, 3, 1, 1, None, "B", None, False, True),      # W = 12: two pixel blocks, the second half full
     (3, 32, 10, 20, 32, 1, 3, 0, 1, None, None, "relu", False, False),  # 1 x 3 grid, W = 20, no bias
     (3, 32, 9, 16, 96, 2, 1, 2, 0, "hw", None, None, False, True),      # 2 x 1 grid, three co chunks
-    (3, 64, 8, 24, 32, 2, 3, 1, 1, "hw", None, "gelu", True, True),     # 2 x 3 grid, two ci chunks
+    (3, 64, 8, 24, 32, 2, 3, 1, 1, "hw", None, "gelu", True, True),     # 2 x 3 grid, two ci chunks: on 24-wide rows neither bf16x3 kernel's tile fits LDS, the generic fp32 kernel runs
     # half pixel blocks (W % 8 == 4) on the x-copy bf16x3 weight-gradient kernel (64 output channels)
     (40, 32, 28, 28, 64, 1, 1, 0, 0, None, None, "relu", False, True),  # PixelCNN's 1x1 32 -> 64
     (3, 32, 12, 12, 64, 2, 2, 1, 1, "hw", None, "elu", False, True),    # 2x2, two blocks per row
-    (3, 64, 20, 20, 128, 1, 3, 0, 1, None, None, None, True, True),     # 1x3, W = 20
+    (3, 64, 20, 20, 128, 1, 3, 0, 1, None, None, None, True, True),     # 1x3, W = 20: three x copies do not fit LDS, the shifted-dy kernel runs
     # big tiles of the bf16x3 weight gradient (round 5: at most 2 taps, Cin % 64 == 0 -> 64 x channels per workgroup;
-    # one tap with Cout % 128 == 0 -> 128 x 64 channels)
-    (10, 128, 32, 32, 256, 1, 1, 0, 0, None, None, None, False, True),   # GatedPixelCNN's 1x1 128 -> 256: 160 tiles over 128 walkers
+    # one tap with Cout % 128 == 0 -> 128 x 64 channels). Since round 6 the 32-wide rows among them run on the row-ring kernel.
+    (10, 128, 32, 32, 256, 1, 1, 0, 0, None, None, None, False, True),   # GatedPixelCNN's 1x1 128 -> 256: the ring's 128 x 128 one-tap tile
     (6, 64, 28, 28, 128, 1, 1, 0, 0, None, None, "relu", False, True),   # 128 x 64, half pixel blocks (W = 28)
     (3, 64, 12, 16, 64, 2, 1, 2, 0, "hw", None, "elu", False, True),     # 64 x 64, two taps (row shift)
-    (5, 128, 32, 32, 256, 2, 1, 2, 0, "hw", None, None, False, True),    # GatedPixelCNN's 2x1 128 -> 256
-    (3, 128, 10, 32, 128, 1, 2, 0, 1, "hw", None, None, True, False),    # 1x2: two column copies, no bias
+    (5, 128, 32, 32, 256, 2, 1, 2, 0, "hw", None, None, False, True),    # GatedPixelCNN's 2x1 128 -> 256 (ring, 128 x 64 tile)
+    (3, 128, 10, 32, 128, 1, 2, 0, 1, "hw", None, None, True, False),    # 1x2: two column copies, no bias (ring, 128 x 64 tile, 10-row images: no segments)
     (2, 192, 8, 8, 128, 1, 1, 0, 0, None, None, "gelu", False, True),    # 8-wide rows: TR = 8, three ci chunks
     # 4 taps where the GENERIC planner arrives at the pipelined kernel's chunk shape (Cin % 16 != 0, two output chunks):
     # stays on conv_b3_kernel (B3Plan::pipelined is set by the PG_CONV_B3P branch only); the data gradient (K = 128,
