@@ -60,7 +60,9 @@ const char* pg_last_error(void);
  * The same kernel is the data-gradient: call it with the transposed pack and negated taps.
  * `res` (optional, may be NULL) is added to the result (fused residual).
  * `dact_src`/`dact` (optional): the result is multiplied by act'(dact_src) — the data gradient of
- * a convolution whose forward fused `in_act` (dact_src = that convolution's raw input).
+ * a convolution whose forward fused `in_act` (dact_src = that convolution's raw input); behind `res` if both are
+ * given. A 1x1 problem (one tap at offset 0, IH x IW == OH x OW) takes a derivative source only with
+ * in_act == PG_ACT_NONE (PG_EINVAL otherwise: a data gradient has no input activation).
  * ------------------------------------------------------------------------------------- */
 int pg_conv2d_taps(const float* in, const float* wpk, const float* bias, const float* res,
                    float* out, int N, int Cin, int IH, int IW, int Cout, int OH, int OW,

@@ -30,7 +30,9 @@ FORMS = {  # epilogue form -> (flags, gate id + 1, dact)
 
 # One small convolution per kernel family, batch 2: (what, case of tests/test_gpu_ops.py's CONV_CASES layout — N, Cin, H, W, Cout, kh,
 # kw, ph, pw, crop, active taps, in_act, residual, bias —, route fields the FORWARD launch must show). The data gradient of the last
-# row (320 -> 16) lands on the narrow staged kernel.
+# row (320 -> 16) lands on the narrow staged kernel. (These eight run the plain epilogue through the Python layer against an fp32 oracle:
+# tests/test_gpu_ops.py::test_conv_b3_kernel_families. The table of every instantiation and epilogue form, compared with float64 through
+# the C ABI, is tests/_conv_cases.py / tests/test_gpu_conv_families.py.)
 FAMILY_CASES = [
     ("staged narrow, two output tiles", (2, 32, 8, 8, 32, 3, 3, 1, 1, None, None, None, False, True), {"kernel": 0, "MT": 2, "CG": 1}),
     ("staged narrow, four output tiles", (2, 64, 8, 8, 64, 3, 3, 1, 1, None, None, None, False, True), {"kernel": 0, "MT": 4, "CG": 1}),

@@ -1,6 +1,11 @@
 """GPU: every HIP kernel, called through the C-ABI (ctypes ops), against the CPU oracle on the
 same seeded inputs. Tolerance for fp32 results: 1e-4 relative to the tensor's max magnitude
-(BASELINE.json north_star); masks / positional encodings are bit-exact."""
+(BASELINE.json north_star); masks / positional encodings are bit-exact.
+
+The convolutions here go through the Python layer at shapes chosen model by model, against an fp32 oracle. Every kernel family,
+instantiation and epilogue form of the forward / data-gradient convolution is held to a float64 reference — bit for bit on inputs
+that fill all three bf16 pieces — by tests/test_gpu_conv_families.py (cases: tests/_conv_cases.py), the weight gradient by
+tests/test_gpu_wgrad_families.py."""
 
 import os
 
