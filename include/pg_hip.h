@@ -421,6 +421,35 @@ int pg_made_sample(const float* pack, const float* b1, const float* b2, const in
                    const float* uniforms, float* logits_out, int N, int D, int H, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * NADE (reference models/autoregressive/nade.py:42-68) as a chunked prefix scan, forward and backward (csrc/nade.hip). All
+ * tensors dense row-major fp32: x, probs, logits, g (N, D); in_w (H, D), in_b (H), h_w (D, H), h_b (D). Per sample n,
+ * a_0 = in_b; then for i = 0 .. D - 1:  l_i = h_b[i] + sum_h max(a_i[h], 0) h_w[i][h];  p_i = sigmoid(l_i);
+ * a_{i+1}[h] = fma(x[n][i], in_w[h][i], a_i[h]). x is used as given (teacher forcing, any float).
+ * pg_nade_plan (host only, no device call) is the one function that decides the domain and the geometry; both launches call
+ * it too. It fills out[0 .. PG_NADE_PLAN_INTS): [0] the chunk length over D, [1] the chunks, [2] hidden units per forward
+ * thread, [3] samples per forward workgroup, [4] H padded, [5] forward workgroups, [6] samples per backward tile, [7] partial
+ * rows of the sums over samples, [8] sample tiles a backward workgroup loops over, [9] backward workgroups, [10] LDS bytes of
+ * the largest kernel, [11] checkpoint floats = chunks * N * H padded (ckpt, and etot of the backward: per-sample tensors,
+ * they grow with N as the activations do), [12] workspace floats of the partial rows (bounded by [13] rows whatever N is),
+ * [13] the cap of the partial rows, [14] the largest H. Any D, N >= 1 and H in 1..8192 whose launches stay below 2^31
+ * workgroups (PG_ESHAPE otherwise, from the plan and the launches alike, nothing launched); PG_EINVAL for a null pointer, a
+ * short array or workspace, a non-positive dimension or checkpoints that are not 16-byte aligned.
+ *   pg_nade_fwd: writes ckpt (chunks, N, H padded), the pre-activations a_{c T} at the chunk starts, then probs and logits.
+ *   pg_nade_bwd: from g = dL/dprobs ADDS dL/d in_w, in_b, h_w, h_b into d_* (each may be NULL). It recomputes a_i inside a
+ *   chunk from ckpt by the forward's own sequence of fused multiply-adds, so the ReLU mask is the forward's bit for bit
+ *   (derivative 0 at 0). etot: scratch of checkpoint size. No gradient with respect to x.
+ * No float atomics; every sum has an order that depends on (N, D, H) alone: outputs and gradients are bit-identical from run
+ * to run, a sample's row of probs / logits also for any N. No host synchronisation (capturable).
+ * ------------------------------------------------------------------------------------- */
+#define PG_NADE_PLAN_INTS 15
+int pg_nade_plan(int D, int H, int N, long long* out, int out_len);
+int pg_nade_fwd(const float* x, const float* in_w, const float* in_b, const float* h_w, const float* h_b, float* ckpt,
+                float* probs, float* logits, int N, int D, int H, void* stream);
+int pg_nade_bwd(const float* x, const float* in_w, const float* h_w, const float* logits, const float* g, const float* ckpt,
+                float* etot, float* d_in_w, float* d_in_b, float* d_h_w, float* d_h_b, int N, int D, int H, float* ws,
+                size_t ws_floats, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Density estimators (models/mixture_models.py, models/kde.py) on streaming log-density kernels (density.hip):
  * the pairwise log-density c[n][k] = sum_d f(x[n][d], theta[k][d]) is one or two fp32-MFMA GEMMs plus a per-column
  * constant, reduced by a running logsumexp over column tiles; nothing of size N x K (x F) is written to memory.

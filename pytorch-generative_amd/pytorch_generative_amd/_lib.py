@@ -130,6 +130,9 @@ SIGNATURES = {
     "pg_made_sample_plan": (c_i, [c_i] * 3 + [c_ip, c_i]),
     "pg_made_sample_pack": (c_i, [c_f] * 3 + [c_i] * 2 + [c_s]),
     "pg_made_sample": (c_i, [c_f] * 7 + [c_i] * 3 + [c_s]),
+    "pg_nade_plan": (c_i, [c_i] * 3 + [ctypes.POINTER(ctypes.c_longlong), c_i]),
+    "pg_nade_fwd": (c_i, [c_f] * 8 + [c_i] * 3 + [c_s]),
+    "pg_nade_bwd": (c_i, [c_f] * 11 + [c_i] * 3 + [c_f, c_z, c_s]),
     "pg_mixture_workspace_floats": (c_z, [c_i] * 5),
     "pg_mixture_fwd": (c_i, [c_i] + [c_f] * 6 + [c_i] * 3 + [c_f, c_z, c_s]),
     "pg_mixture_bwd": (c_i, [c_i] + [c_f] * 9 + [c_i] * 3 + [c_f, c_z, c_s]),

@@ -7,8 +7,9 @@
 Code written against the reference's public surface (pytorch_generative/__init__.py:1-3,
 nn/__init__.py:3-13, models/__init__.py:3-24, models/<family>/<module>.reproduce, trainer.Trainer)
 then runs unmodified on the HIP operator path for the components this package covers; names of
-out-of-scope components (NADE, NICE, FullyVisibleBeliefNetwork, `models.flow`, `models.autoregressive.nade` / `.fvbn`)
-resolve to placeholders that raise on use.
+out-of-scope components (NICE, FullyVisibleBeliefNetwork, `models.flow`, `models.autoregressive.fvbn`)
+resolve to placeholders that raise on use. NADE is built and lives in `models.autoregressive.nade`; the top-level
+name `models.NADE` is not exported and keeps its placeholder under the alias.
 """
 
 import sys
@@ -18,7 +19,7 @@ import pytorch_generative_amd as _pkg
 
 _OUT_OF_SCOPE_MODULES = {
     "pytorch_generative.models.flow": ("nice",),
-    "pytorch_generative.models.autoregressive": ("nade", "fvbn"),
+    "pytorch_generative.models.autoregressive": ("fvbn",),
 }
 _OUT_OF_SCOPE_MODELS = ("NADE", "FullyVisibleBeliefNetwork", "NICE")
 

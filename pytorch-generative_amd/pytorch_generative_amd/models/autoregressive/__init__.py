@@ -4,6 +4,7 @@ from pytorch_generative_amd.models.autoregressive import (  # noqa: F401
     gated_pixel_cnn,
     image_gpt,
     made,
+    nade,
     pixel_cnn,
     pixel_cnn_pp,
     pixel_snail,

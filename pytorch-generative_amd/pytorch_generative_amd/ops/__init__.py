@@ -165,6 +165,11 @@ from pytorch_generative_amd.ops.made_sample import (  # noqa: F401
     made_sample_plan,
     made_sample_chain,
 )
+from pytorch_generative_amd.ops.nade import (  # noqa: F401
+    _NADE,
+    nade,
+    nade_plan,
+)
 from pytorch_generative_amd.ops.density import (  # noqa: F401
     _MixtureLogProb,
     MIXTURE_BERNOULLI,
