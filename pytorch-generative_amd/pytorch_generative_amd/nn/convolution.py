@@ -196,60 +196,45 @@ class Conv2d(nn.Conv2d):
                     or not ops.gpt_out_head_supported(x, pre_ln, self)):
                 raise ValueError("Conv2d: pre_ln= needs a plain 1x1 convolution on a shape gpt_out_head_supported() accepts")
             return ops.gpt_out_head(x, pre_ln, self, chain)
-        if res_slot is not None or in_sum is not None:
-            if (gate is not None or res2 is not None or n_skip or self._down2 or ops.RowDecode.current is not None
-                    or not self.mfma_ok(x, crop)):
-                raise ValueError("Conv2d: res_slot / in_sum need the plain matrix-core training path (check dual_ok first)")
-            return ops.conv2d_taps(
-                x, self.weight, self.bias, self._conv_spec(), out_hw=crop, in_act=_ACTS[in_act],
-                res=res, weight_param=self.weight, bias_param=self.bias, out_act=_ACTS[out_act],
-                out_pre_scaled=out_pre_scaled, in_post=_ACTS[in_post], res_slot=res_slot, in_sum=in_sum,
-            )
-        if gate is not None:
-            if res2 is not None or out_act is not None or out_pre_scaled or not self.gate_ok(x, crop):
-                raise ValueError("Conv2d: gate= needs a convolution (at most one residual) on a shape gate_ok() accepts")
-            if n_skip and not x.requires_grad:
-                y = ops.conv2d_taps(x, self.weight, self.bias, self._conv_spec(), out_hw=crop, in_act=_ACTS[in_act], res=res,
-                                    weight_param=self.weight, bias_param=self.bias, in_post=_ACTS[in_post],
-                                    gate=gate, gate_res=gate_res)
-                return (y,) + (x,) * n_skip
-            return ops.conv2d_taps(x, self.weight, self.bias, self._conv_spec(), out_hw=crop, in_act=_ACTS[in_act], res=res,
-                                   weight_param=self.weight, bias_param=self.bias, in_post=_ACTS[in_post], n_skip=n_skip,
-                                   gate=gate, gate_res=gate_res)
-        if res2 is not None and not self.two_residuals_ok(x, crop):
-            y = self.forward(x, crop=crop, in_act=in_act, res=res, out_act=out_act,
-                             out_pre_scaled=out_pre_scaled, in_post=in_post, n_skip=n_skip)
-            return (ops.add(y[0], res2),) + tuple(y[1:]) if n_skip else ops.add(y, res2)
-        if n_skip:
-            ctx = ops.RowDecode.current
-            if ctx is not None or self._down2 or not x.requires_grad:
-                y = self.forward(x, crop=crop, in_act=in_act, res=res, out_act=out_act,
-                                 out_pre_scaled=out_pre_scaled, in_post=in_post, res2=res2)
-                return (y,) + (x,) * n_skip
-        ctx = ops.RowDecode.current
-        if ctx is not None:
-            return self._row_forward(ctx, x, crop, in_act, res, out_act)
-        if self._down2:
-            if out_act is not None or in_post is not None:
-                raise ValueError("Conv2d: fused output activations are not available for stride 2")
-            return self._forward_down2(x, in_act, res)
-        if (out_pre_scaled or in_post is not None) and not self.mfma_ok(x, crop):
+        row = ops.RowDecode.current
+        plain = row is None and not self._down2  # one tap convolution, and more than one image row
+        if (res_slot is not None or in_sum is not None) and (
+                gate is not None or res2 is not None or n_skip or not plain or not self.mfma_ok(x, crop)):
+            raise ValueError("Conv2d: res_slot / in_sum need the plain matrix-core training path (check dual_ok first)")
+        if gate is not None and (res2 is not None or out_act is not None or out_pre_scaled or not self.gate_ok(x, crop)):
+            raise ValueError("Conv2d: gate= needs a convolution (at most one residual) on a shape gate_ok() accepts")
+        if self._down2 and row is None and (out_act is not None or in_post is not None):
+            raise ValueError("Conv2d: fused output activations are not available for stride 2")
+        # what the kernels fuse for this shape; the rest runs behind the convolution as separate launches
+        fuse_act = (not plain or gate is not None or (out_act is None and not out_pre_scaled and in_post is None)
+                    or self.mfma_ok(x, crop))
+        if (out_pre_scaled or in_post is not None) and not fuse_act:
             # the two halves of a fused activation between two convolutions only exist on the matrix-core
             # path; the caller must have checked mfma_ok() on BOTH convolutions (fail here, not in backward)
             raise ValueError("Conv2d: out_pre_scaled / in_post need the matrix-core path for this shape "
                              "(check mfma_ok first)")
-        if out_act is not None and not out_pre_scaled and not self.mfma_ok(x, crop):
+        fuse_res2 = res2 is not None and fuse_act and self.two_residuals_ok(x, crop)
+        fuse_skip = bool(n_skip) and plain and fuse_act and x.requires_grad
+        if row is not None:
+            y = self._row_forward(row, x, crop, in_act, res, out_act)
+        elif self._down2:
+            y = self._forward_down2(x, in_act, res)
+        else:
+            y = ops.conv2d_taps(
+                x, self.weight, self.bias, self._conv_spec(), out_hw=crop, in_act=_ACTS[in_act],
+                res=res if fuse_act else None, weight_param=self.weight, bias_param=self.bias,
+                out_act=_ACTS[out_act if fuse_act else None], out_pre_scaled=out_pre_scaled, in_post=_ACTS[in_post],
+                n_skip=n_skip if fuse_skip else 0, res2=res2 if fuse_res2 else None, gate=gate, gate_res=gate_res,
+                res_slot=res_slot, in_sum=in_sum,
+            )
+        y, *aliases = y if fuse_skip else (y,) + (x,) * n_skip
+        if not fuse_act:
             # shapes the matrix-core path does not take: same result from separate kernels
-            y = ops.conv2d_taps(x, self.weight, self.bias, self._conv_spec(), out_hw=crop,
-                                in_act=_ACTS[in_act], weight_param=self.weight, bias_param=self.bias)
             y = ops._Act.apply(y, _ACTS[out_act])
             y = y if res is None else ops.add(y, res)
-            return (y,) + (x,) * n_skip if n_skip else y
-        return ops.conv2d_taps(
-            x, self.weight, self.bias, self._conv_spec(), out_hw=crop, in_act=_ACTS[in_act],
-            res=res, weight_param=self.weight, bias_param=self.bias, out_act=_ACTS[out_act],
-            out_pre_scaled=out_pre_scaled, in_post=_ACTS[in_post], n_skip=n_skip, res2=res2,
-        )
+        if res2 is not None and not fuse_res2:
+            y = ops.add(y, res2)
+        return (y, *aliases) if n_skip else y
 
     def _forward_down2(self, x, in_act, res):
         """out[a, b] = sum_{u,v} w[u, v] x[2a + u - 1, 2b + v - 1] evaluated on the four 2x2 phases

@@ -62,7 +62,7 @@ from pytorch_generative_amd.ops.conv import (  # noqa: F401
     CONV_MFMA,
     _use_mfma,
     _pack_frag,
-    _pack_frag_both,
+    conv_formats,
     _pack,
     _ConvTaps,
     FUSE_PAIR,

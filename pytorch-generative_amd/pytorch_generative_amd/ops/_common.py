@@ -128,12 +128,12 @@ def _sink(param):
     return getattr(param, "_pg_grad", None) if param is not None else None
 
 
-def _grad_targets(params):
+def _grad_targets(params, sinks=None):
     """Per parameter: (tensor the kernel adds into, value to return to autograd): the direct sink if
-    the parameter has one (then autograd gets None), else a fresh zero tensor."""
+    the parameter has one (then autograd gets None), else a fresh zero tensor. `sinks`: the sinks, one per parameter,
+    where the caller resolved them already (the tensor it holds is a view of the parameter that carries the sink)."""
     tgt, ret = [], []
-    for p in params:
-        sink = _sink(p)
+    for p, sink in zip(params, map(_sink, params) if sinks is None else sinks):
         if sink is not None:
             tgt.append(sink)
             ret.append(None)
