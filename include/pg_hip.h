@@ -450,6 +450,53 @@ int pg_nade_bwd(const float* x, const float* in_w, const float* h_w, const float
                 size_t ws_floats, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Dense linear layers on large-tile fp32-MFMA GEMMs (csrc/dense_linear.hip): the coupling networks of NICE (reference
+ * models/flow/nice.py). w (out, in) dense row-major; every activation operand is (N, columns) fp32 with a ROW STRIDE in floats
+ * (ld >= columns), so one half of an (N, F) tensor is an operand as it lies.
+ * pg_dense_linear_plan (host only, no device call) is the one function that decides the domain, the tile variant, the k-split
+ * and the workspace; every launch calls it too. kind: PG_DENSE_FWD / _DGRAD / _WGRAD. It fills out[0 .. PG_DENSE_PLAN_INTS):
+ * [0] the tile variant (0: 64 x 64 on v_mfma_f32_16x16x4_f32, 1: 128 x 128 on v_mfma_f32_32x32x2_f32), [1] tile rows, [2] tile
+ * columns, [3] k per LDS chunk, [4] rows R, [5] columns C and [6] depth K of the product (forward N, out, in; data gradient
+ * N, in, out; weight gradient out, in, N), [7] row tiles, [8] column tiles, [9] k slices, [10] k per slice, [11] GEMM
+ * workgroups, [12] workgroups of the reduce launch (0 without a split), [13] the workspace floats (0 without a split).
+ * The large tile is taken where it alone gives >= 192 workgroups; else the small one, split along k where it gives < 128
+ * (at least two chunks per slice, at most 64 slices). Slices write raw partial sums to ws; a second launch adds them in slice
+ * order and applies the epilogue. Any N, in, out in 1 .. 2^30 with at most 2^31 - 1 tiles: PG_ESHAPE otherwise, from the plan and the
+ * launches alike; PG_EINVAL for a null operand, a row stride below the row length, a sign other than +1 / -1 or a short workspace.
+ *   fwd:   y = x w^T + b (b may be NULL), then relu != 0: max(., 0); or with res != NULL: y = res + sign (x w^T + b), the
+ *          additive coupling law (sign +1) and its inverse (-1); y may be res.
+ *   dgrad: dx = sign (dy w), zeroed where relu_out <= 0 (relu_out, may be NULL: the stored ReLU output that was this layer's
+ *          input), then + addend (may be NULL).
+ *   wgrad: dw += sign dy^T x, db += sign sum_n dy (db may be NULL): added into flat-gradient sinks or zeroed buffers. With a
+ *          k-split the batch is cut into slices whose partial dw and db are merged in slice order.
+ * An fp32 MFMA is an fmaf chain in k order: every output element is owned by one lane and summed in an order fixed by the
+ * shape. No float atomics, bit-identical from run to run, no host synchronisation (capturable).
+ * pg_nice_scale_fwd: z = y exp(sign s), s (F) over dense (N, F). _bwd: dy = dz exp(sign s) (dy may be NULL) and
+ *   ds[j] += sign sum_n dz[n][j] z[n][j] (ds may be NULL) through pg_nice_scale_bwd_workspace_floats floats of partial rows
+ *   (at most 64) merged in row order.
+ * pg_logistic_logprob_fwd: lp[n] = -sum_j (|z| + 2 log1p(exp(-|z|))) = sum_j -(softplus(z) + softplus(-z)) over dense (N, F),
+ *   one workgroup per sample, a fixed order. _bwd: dz[n][j] = -g[n] tanh(z[n][j] / 2).
+ * ------------------------------------------------------------------------------------- */
+#define PG_DENSE_FWD 0
+#define PG_DENSE_DGRAD 1
+#define PG_DENSE_WGRAD 2
+#define PG_DENSE_PLAN_INTS 14
+int pg_dense_linear_plan(int N, int in, int out, int kind, long long* outv, int out_len);
+int pg_dense_linear_fwd(const float* x, long ldx, const float* w, const float* b, const float* res, long ldres, int sign, float* y,
+                        long ldy, int N, int in, int out, int relu, float* ws, size_t ws_floats, void* stream);
+int pg_dense_linear_dgrad(const float* dy, long lddy, const float* w, const float* relu_out, long ldrelu, const float* addend,
+                          long ldadd, int sign, float* dx, long lddx, int N, int in, int out, float* ws, size_t ws_floats,
+                          void* stream);
+int pg_dense_linear_wgrad(const float* x, long ldx, const float* dy, long lddy, int sign, float* dw, float* db, int N, int in, int out,
+                          float* ws, size_t ws_floats, void* stream);
+int pg_nice_scale_fwd(const float* y, const float* s, float* z, int N, int F, int sign, void* stream);
+size_t pg_nice_scale_bwd_workspace_floats(int N, int F);
+int pg_nice_scale_bwd(const float* dz, const float* z, const float* s, float* dy, float* ds, int N, int F, int sign, float* ws,
+                      size_t ws_floats, void* stream);
+int pg_logistic_logprob_fwd(const float* z, float* lp, int N, int F, void* stream);
+int pg_logistic_logprob_bwd(const float* z, const float* g, float* dz, int N, int F, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Density estimators (models/mixture_models.py, models/kde.py) on streaming log-density kernels (density.hip):
  * the pairwise log-density c[n][k] = sum_d f(x[n][d], theta[k][d]) is one or two fp32-MFMA GEMMs plus a per-column
  * constant, reduced by a running logsumexp over column tiles; nothing of size N x K (x F) is written to memory.

@@ -133,6 +133,15 @@ SIGNATURES = {
     "pg_nade_plan": (c_i, [c_i] * 3 + [ctypes.POINTER(ctypes.c_longlong), c_i]),
     "pg_nade_fwd": (c_i, [c_f] * 8 + [c_i] * 3 + [c_s]),
     "pg_nade_bwd": (c_i, [c_f] * 11 + [c_i] * 3 + [c_f, c_z, c_s]),
+    "pg_dense_linear_plan": (c_i, [c_i] * 4 + [ctypes.POINTER(ctypes.c_longlong), c_i]),
+    "pg_dense_linear_fwd": (c_i, [c_f, c_l, c_f, c_f, c_f, c_l, c_i, c_f, c_l] + [c_i] * 4 + [c_f, c_z, c_s]),
+    "pg_dense_linear_dgrad": (c_i, [c_f, c_l, c_f, c_f, c_l, c_f, c_l, c_i, c_f, c_l] + [c_i] * 3 + [c_f, c_z, c_s]),
+    "pg_dense_linear_wgrad": (c_i, [c_f, c_l, c_f, c_l, c_i, c_f, c_f] + [c_i] * 3 + [c_f, c_z, c_s]),
+    "pg_nice_scale_fwd": (c_i, [c_f] * 3 + [c_i] * 3 + [c_s]),
+    "pg_nice_scale_bwd_workspace_floats": (c_z, [c_i] * 2),
+    "pg_nice_scale_bwd": (c_i, [c_f] * 5 + [c_i] * 3 + [c_f, c_z, c_s]),
+    "pg_logistic_logprob_fwd": (c_i, [c_f] * 2 + [c_i] * 2 + [c_s]),
+    "pg_logistic_logprob_bwd": (c_i, [c_f] * 3 + [c_i] * 2 + [c_s]),
     "pg_mixture_workspace_floats": (c_z, [c_i] * 5),
     "pg_mixture_fwd": (c_i, [c_i] + [c_f] * 6 + [c_i] * 3 + [c_f, c_z, c_s]),
     "pg_mixture_bwd": (c_i, [c_i] + [c_f] * 9 + [c_i] * 3 + [c_f, c_z, c_s]),

@@ -7,9 +7,10 @@
 Code written against the reference's public surface (pytorch_generative/__init__.py:1-3,
 nn/__init__.py:3-13, models/__init__.py:3-24, models/<family>/<module>.reproduce, trainer.Trainer)
 then runs unmodified on the HIP operator path for the components this package covers; names of
-out-of-scope components (NICE, FullyVisibleBeliefNetwork, `models.flow`, `models.autoregressive.fvbn`)
-resolve to placeholders that raise on use. NADE is built and lives in `models.autoregressive.nade`; the top-level
-name `models.NADE` is not exported and keeps its placeholder under the alias.
+out-of-scope components (FullyVisibleBeliefNetwork, `models.autoregressive.fvbn`) resolve to placeholders that raise on
+use. NADE is built and lives in `models.autoregressive.nade`; the top-level name `models.NADE` is not exported and keeps
+its placeholder under the alias. NICE is built and lives in `models.flows.nice` (package `flows`, plural); the reference's
+two names for it, `models.NICE` and `models.flow.nice`, keep their raising placeholders under the alias.
 """
 
 import sys

@@ -170,6 +170,15 @@ from pytorch_generative_amd.ops.nade import (  # noqa: F401
     nade,
     nade_plan,
 )
+from pytorch_generative_amd.ops.nice import (  # noqa: F401
+    _Coupling,
+    _NiceScale,
+    _LogisticLogProb,
+    coupling,
+    dense_linear_plan,
+    logistic_logprob,
+    nice_scale,
+)
 from pytorch_generative_amd.ops.density import (  # noqa: F401
     _MixtureLogProb,
     MIXTURE_BERNOULLI,

@@ -37,6 +37,15 @@ def elbo_loss(x, _, preds):
     return {"recon_loss": recon, "kl_div": kl, "loss": recon + kl}
 
 
+def nice_loss(x, _, preds):
+    """{"loss", "prior_log_likelihood", "log_det_J"} of NICE's recipe (flow/nice.py:205-213): the logistic prior's log-density
+    of z summed per sample (ops.logistic_logprob) plus log det J, negated and averaged over the batch."""
+    z, log_det_j = preds
+    log_prob = ops.logistic_logprob(z)
+    prior = log_prob.mean()
+    return {"loss": -(prior + log_det_j), "prior_log_likelihood": prior, "log_det_J": log_det_j}
+
+
 def _device(n_gpus, device_id):
     if not torch.cuda.is_available():
         raise RuntimeError("reproduce(): this path needs an MI355X (no CPU fallback)")
@@ -67,6 +76,10 @@ def run(build_model, *, loaders, loss_fn, lr, lr_decay=1.0, n_epochs, batch_size
 
 def binarized_mnist(batch_size):
     return datasets.get_mnist_loaders(batch_size, dynamically_binarize=True)
+
+
+def dequantized_mnist(batch_size):
+    return datasets.get_mnist_loaders(batch_size, dequantize=True)
 
 
 def grey_mnist(batch_size):

@@ -17,7 +17,7 @@ import os
 
 import torch
 
-from pytorch_generative_amd.models import autoregressive, vae
+from pytorch_generative_amd.models import autoregressive, flows, vae
 
 MODEL_DICT = {
     "beta_vae": vae.beta_vae,
@@ -25,6 +25,7 @@ MODEL_DICT = {
     "image_gpt": autoregressive.image_gpt,
     "made": autoregressive.made,
     "nade": autoregressive.nade,
+    "nice": flows.nice,
     "pixel_cnn": autoregressive.pixel_cnn,
     "pixel_cnn_pp": autoregressive.pixel_cnn_pp,
     "pixel_snail": autoregressive.pixel_snail,
