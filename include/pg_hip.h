@@ -497,6 +497,57 @@ int pg_logistic_logprob_fwd(const float* z, float* lp, int N, int F, void* strea
 int pg_logistic_logprob_bwd(const float* z, const float* g, float* dz, int N, int F, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * The Fully Visible Belief Network (reference models/autoregressive/fvbn.py) on packed triangular storage (csrc/fvbn.hip):
+ * logits[n][i] = b[i] + sum_{j < i} W[i][j] x[n][j]. x, dy, logits, canvas, uniforms: dense row-major fp32 (N, D); b, db (D).
+ * PACKED weight wp (P(D) floats, 16-byte aligned): row i of the strictly lower triangle holds len(i) = max(1, i) values (row 0:
+ * the reference's dummy weight, multiplied by a zero input there and never read here), then zeros up to pad(i) =
+ * roundup(len(i), 4) floats; off(i) = sum_{k < i} pad(k) = pg_fvbn_row_offset(i) (-1 for i < 0), P(D) = off(D).
+ * pg_fvbn_plan (host only, no device call) is the one function that decides the domain and every geometry; every launch calls
+ * it too. It fills out[0 .. PG_FVBN_PLAN_INTS): [0] P(D), [1] the tile edge (64: rows and columns of an output tile, on
+ * v_mfma_f32_16x16x4_f32), [2] k per LDS chunk, [3] tiles along D, [4] forward tiles along N, [5] forward workgroups,
+ * [6] (column tile, k chunk) pairs the forward multiplies, [7] weight-gradient tiles (tile column <= tile row), [8] slices
+ * along N of the weight gradient (more than one where [7] < 128; at least two chunks each, at most 64), [9] samples per slice,
+ * [10] weight-gradient workgroups, [11] workgroups of its merge launch (0 without a split), [12] workspace floats (0 without a
+ * split), [13] samples per sampler workgroup, [14] sampler workgroups, [15] sampler LDS bytes, [16] the largest D, [17] k chunks
+ * of a forward slice, [18] forward slices over all column tiles, [19] 1 where the forward is split along k (fewer than 128
+ * output tiles and a column tile with more than one slice: [5] is then slices x tiles along N), [20] workgroups of its merge
+ * launch and [21] its workspace floats (both 0 without a split).
+ * D in 1 .. 8192, N in 1 .. 2^30 with fewer than 2^31 forward workgroups: PG_ESHAPE otherwise, from the plan and the launches
+ * alike, nothing launched. PG_EINVAL for a null pointer, a short array or workspace and a wp that is not 16-byte aligned.
+ * pg_fvbn_tiles (host only) lists, for the forward (kind PG_FVBN_TILES_FWD: the (column tile, k chunk) pairs) or the weight
+ * gradient (PG_FVBN_TILES_WGRAD), the rectangles [i0, i1) x [j0, j1) of W the launch visits, 4 integers each, into out (at most
+ * cap rectangles are written; *count is their number): together they hold every (i, j < i) exactly once.
+ *   fwd:    only k chunks at or below the diagonal are multiplied; a weight at j >= i is a zero formed by a predicate, the
+ *           16-byte loads stay inside row i's own storage. x is used AS GIVEN and finite values are assumed: the reference never
+ *           reads x[:, j >= i], here such entries meet exact zeros, so a NaN or infinity there would spread.
+ *           logits[:, 0] = b[0] bit for bit. The sum over j: an fmaf chain per slice of [17] chunks, the slices added in
+ *           ascending order, then b; with a split the slices are workgroups of their own and a second launch adds their
+ *           partial sums from ws in that order: the same bits with and without a split.
+ *   wgrad:  ADDS dwp[off(i) + j] += sum_n dy[n][i] x[n][j] for j < i only and db[i] += sum_n dy[n][i] (either may be NULL):
+ *           into flat-gradient sinks or zeroed buffers. Pads and row 0 are not written (their gradient is exactly zero). With
+ *           a split the slices' partial sums go to ws and a second launch adds them in slice order. No data gradient.
+ *   sample: per sample, i = 0 .. D - 1: l = b[i] + sum_{j < i} wp[off(i) + j] x_j; x_i = canvas[n][i] where that is >= 0, else
+ *           1 if uniforms[n][i] < sigmoid(l), else 0; writes canvas and, if logits_out is not NULL, logits_out[n][i] = l.
+ *           One launch for the whole batch.
+ *   pack:   dense (D, D) -> packed: the strict lower triangle, row 0's dummy value from [0][0], zero pads. unpack: the inverse,
+ *           zeros on and above the diagonal except [0][0].
+ * An fp32 MFMA is an fmaf chain in k order; every sum has an order fixed by the shape (the sampler's by i alone), no float
+ * atomics: bit-identical from run to run, a sample's row of logits for any N and any slot. No host synchronisation (capturable).
+ * ------------------------------------------------------------------------------------- */
+#define PG_FVBN_PLAN_INTS 22
+#define PG_FVBN_TILES_FWD 0
+#define PG_FVBN_TILES_WGRAD 1
+long long pg_fvbn_row_offset(int i);
+int pg_fvbn_plan(int D, int N, long long* out, int out_len);
+int pg_fvbn_tiles(int D, int kind, long long* out, long long cap, long long* count);
+int pg_fvbn_fwd(const float* x, const float* wp, const float* b, float* logits, int N, int D, float* ws, size_t ws_floats, void* stream);
+int pg_fvbn_wgrad(const float* x, const float* dy, float* dwp, float* db, int N, int D, float* ws, size_t ws_floats, void* stream);
+int pg_fvbn_sample(const float* wp, const float* b, float* canvas, const float* uniforms, float* logits_out, int N, int D,
+                   void* stream);
+int pg_fvbn_pack(const float* dense, float* wp, int D, void* stream);
+int pg_fvbn_unpack(const float* wp, float* dense, int D, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Density estimators (models/mixture_models.py, models/kde.py) on streaming log-density kernels (density.hip):
  * the pairwise log-density c[n][k] = sum_d f(x[n][d], theta[k][d]) is one or two fp32-MFMA GEMMs plus a per-column
  * constant, reduced by a running logsumexp over column tiles; nothing of size N x K (x F) is written to memory.

@@ -137,6 +137,14 @@ SIGNATURES = {
     "pg_dense_linear_fwd": (c_i, [c_f, c_l, c_f, c_f, c_f, c_l, c_i, c_f, c_l] + [c_i] * 4 + [c_f, c_z, c_s]),
     "pg_dense_linear_dgrad": (c_i, [c_f, c_l, c_f, c_f, c_l, c_f, c_l, c_i, c_f, c_l] + [c_i] * 3 + [c_f, c_z, c_s]),
     "pg_dense_linear_wgrad": (c_i, [c_f, c_l, c_f, c_l, c_i, c_f, c_f] + [c_i] * 3 + [c_f, c_z, c_s]),
+    "pg_fvbn_row_offset": (ctypes.c_longlong, [c_i]),
+    "pg_fvbn_plan": (c_i, [c_i] * 2 + [ctypes.POINTER(ctypes.c_longlong), c_i]),
+    "pg_fvbn_tiles": (c_i, [c_i] * 2 + [ctypes.POINTER(ctypes.c_longlong), ctypes.c_longlong, ctypes.POINTER(ctypes.c_longlong)]),
+    "pg_fvbn_fwd": (c_i, [c_f] * 4 + [c_i] * 2 + [c_f, c_z, c_s]),
+    "pg_fvbn_wgrad": (c_i, [c_f] * 4 + [c_i] * 2 + [c_f, c_z, c_s]),
+    "pg_fvbn_sample": (c_i, [c_f] * 5 + [c_i] * 2 + [c_s]),
+    "pg_fvbn_pack": (c_i, [c_f] * 2 + [c_i, c_s]),
+    "pg_fvbn_unpack": (c_i, [c_f] * 2 + [c_i, c_s]),
     "pg_nice_scale_fwd": (c_i, [c_f] * 3 + [c_i] * 3 + [c_s]),
     "pg_nice_scale_bwd_workspace_floats": (c_z, [c_i] * 2),
     "pg_nice_scale_bwd": (c_i, [c_f] * 5 + [c_i] * 3 + [c_f, c_z, c_s]),

@@ -7,9 +7,10 @@
 Code written against the reference's public surface (pytorch_generative/__init__.py:1-3,
 nn/__init__.py:3-13, models/__init__.py:3-24, models/<family>/<module>.reproduce, trainer.Trainer)
 then runs unmodified on the HIP operator path for the components this package covers; names of
-out-of-scope components (FullyVisibleBeliefNetwork, `models.autoregressive.fvbn`) resolve to placeholders that raise on
-use. NADE is built and lives in `models.autoregressive.nade`; the top-level name `models.NADE` is not exported and keeps
-its placeholder under the alias. NICE is built and lives in `models.flows.nice` (package `flows`, plural); the reference's
+components that are not exported at the reference's place resolve to placeholders that raise on use. NADE and the
+FullyVisibleBeliefNetwork are built and live in `models.autoregressive.nade` and `models.autoregressive.fvbn`, which the alias
+serves as they are; the top-level names `models.NADE` and `models.FullyVisibleBeliefNetwork` are not exported and keep their
+placeholders under the alias. NICE is built and lives in `models.flows.nice` (package `flows`, plural); the reference's
 two names for it, `models.NICE` and `models.flow.nice`, keep their raising placeholders under the alias.
 """
 
@@ -20,7 +21,6 @@ import pytorch_generative_amd as _pkg
 
 _OUT_OF_SCOPE_MODULES = {
     "pytorch_generative.models.flow": ("nice",),
-    "pytorch_generative.models.autoregressive": ("fvbn",),
 }
 _OUT_OF_SCOPE_MODELS = ("NADE", "FullyVisibleBeliefNetwork", "NICE")
 

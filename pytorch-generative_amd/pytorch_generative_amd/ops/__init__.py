@@ -170,6 +170,17 @@ from pytorch_generative_amd.ops.nade import (  # noqa: F401
     nade,
     nade_plan,
 )
+from pytorch_generative_amd.ops.fvbn import (  # noqa: F401
+    _FVBN,
+    fvbn,
+    fvbn_offsets,
+    fvbn_pack,
+    fvbn_plan,
+    fvbn_plan_status,
+    fvbn_sample_chain,
+    fvbn_tiles,
+    fvbn_unpack,
+)
 from pytorch_generative_amd.ops.nice import (  # noqa: F401
     _Coupling,
     _NiceScale,

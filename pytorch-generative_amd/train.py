@@ -21,6 +21,7 @@ from pytorch_generative_amd.models import autoregressive, flows, vae
 
 MODEL_DICT = {
     "beta_vae": vae.beta_vae,
+    "fvbn": autoregressive.fvbn,
     "gated_pixel_cnn": autoregressive.gated_pixel_cnn,
     "image_gpt": autoregressive.image_gpt,
     "made": autoregressive.made,
