@@ -548,6 +548,67 @@ int pg_fvbn_pack(const float* dense, float* wp, int D, void* stream);
 int pg_fvbn_unpack(const float* wp, float* dense, int D, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * The dense symmetric solve of a Gaussian process (reference models/gaussian_process.py; csrc/gp.hip): squared-exponential
+ * covariance, a blocked right-looking fp32 Cholesky factorisation that can be appended to, the triangular solves and the
+ * strided GEMM update they are built from. Everything is fp32; EVERY operand is a row-major matrix with a leading dimension in
+ * floats (ld >= its columns), so a factor lives in a buffer larger than itself.
+ * pg_gp_plan (host only, no device call) is the one function that decides the domain and the geometry; every entry point calls
+ * it too (with 1 for the dimensions it does not have). It fills out[0 .. PG_GP_PLAN_INTS): [0] the panel width and tile edge
+ * (64, on v_mfma_f32_16x16x4_f32), [1] k per LDS chunk, [2] panels of n, [3] row tiles of m, [4] the covariance route (0: exact
+ * differences on the VALU, 1: |a|^2 + |b|^2 - 2 a.b with the cross term on the MFMA), [5] the largest d of route 0, [6] the
+ * tiles the symmetric covariance computes (on or below the diagonal), [7] the tiles of the cross covariance, [8] the launches
+ * of a full factorisation (3 panels - 2), [9] of a forward solve over n columns (2 panels - 1), [10] the workgroups of the
+ * first trailing update, [11] the largest n and m, [12] the largest d, [13] the largest p, [14] row tiles of p, [15] the
+ * largest d route 0 holds when it is forced.
+ * n, m in 1 .. 16384 (element offsets fit 32 bits), d in 1 .. 4096, p (columns of y) in 1 .. 4096: PG_ESHAPE otherwise, from
+ * the plan and the launches alike, nothing launched. PG_EINVAL for a null pointer, a short array, a row stride below the row
+ * length, unknown flags. Without a device an entry point returns hipErrorNoDevice (100), and only after the plan and the
+ * argument checks accepted the call.
+ *   se_kernel:  K[i][j] = std^2 exp(-|a_i - b_j|^2 / (2 lengthscale^2)) for a (n, d), b (m, d) into K (n, m). PG_GP_LOWER: only
+ *               elements with j <= i + diag_off are written and tiles wholly above that line are not visited; PG_GP_DIAG: the
+ *               elements j == i + diag_off are written as exactly std^2 + noise_var; PG_GP_MIRROR (a is b, lower, diag_off 0):
+ *               K[j][i] = K[i][j] as well, so the matrix is exactly symmetric. Route 1 clamps the squared distance at 0 before
+ *               the exp. PG_GP_SE_DIRECT / PG_GP_SE_MFMA force a route (route 0: d <= 64, PG_ESHAPE above). An element's bits
+ *               depend on its two rows alone, not on n, m or the tile it lies in.
+ *   add_diag:   A[i][i] += value for i < n.
+ *   gemm_nt:    C (R, C) = C - A B^T (PG_GP_PLUS: + A B^T) over k < K, A (R, K), B (C, K); PG_GP_B_TRANS: B is read as (K, C),
+ *               the A B form. The accumulators are SEEDED with the tile of C and the product is subtracted inside the MFMA chain:
+ *               an element is fmaf(-a_k, b_k, .) in ascending k starting from C's value, so an update applied panel after
+ *               panel is one continuous chain, whatever the blocking. PG_GP_LOWER: only elements with c <= r + diag_off are
+ *               read and written; PG_GP_MIRROR (square, lower, diag_off 0): C[c][r] = C[r][c] too. No k-split.
+ *   potrf_diag: the unblocked lower Cholesky of one diagonal block (jb <= 64 rows) in place on the VALU; rows < done are
+ *               final and untouched, rows >= done continue from the values the updates left. A pivot that is not > 0 (a NaN
+ *               included) stores base + index + 1 into *info by a plain store, only while *info is 0; the kernel goes on.
+ *   trsm_diag:  X L_kk^T = B in place (transposed != 0: X L_kk = B) for rows x jb, 64 rows per workgroup; columns < done are
+ *               final (forward form). fmaf chains in ascending (transposed: descending) k, then one IEEE division.
+ *   potrf:      the lower factor of A (n, n) in place, right-looking, at most three launches per panel of 64 columns; the strict
+ *               upper triangle is neither read nor written. n_done > 0: rows < n_done hold a finished factor and only rows
+ *               n_done .. n (holding A's values in columns 0 .. their own) are completed; the result has the bits of the full
+ *               factorisation. *info as in potrf_diag (the caller zeroes it).
+ *   trsm_right: X L^T = B in place for X (rows, n) (transposed != 0: X L = B), right-looking; col_done > 0 (forward only):
+ *               columns < col_done are final, the others hold B.
+ * No float atomics, no host synchronisation (capturable), bit-identical from run to run.
+ * ------------------------------------------------------------------------------------- */
+#define PG_GP_PLAN_INTS 16
+#define PG_GP_LOWER 1
+#define PG_GP_MIRROR 2
+#define PG_GP_DIAG 4
+#define PG_GP_PLUS 8
+#define PG_GP_B_TRANS 16
+#define PG_GP_SE_DIRECT 32
+#define PG_GP_SE_MFMA 64
+int pg_gp_plan(int n, int m, int d, int p, long long* out, int out_len);
+int pg_gp_se_kernel(const float* a, long lda, int n, const float* b, long ldb, int m, int d, float std, float lengthscale,
+                    float noise_var, float* k, long ldk, int diag_off, int flags, void* stream);
+int pg_gp_add_diag(float* a, long ld, int n, float value, void* stream);
+int pg_gp_gemm_nt(const float* a, long lda, const float* b, long ldb, float* c, long ldc, int R, int C, int K, int diag_off, int flags,
+                  void* stream);
+int pg_gp_potrf_diag(float* a, long ld, int jb, int done, int base, int* info, void* stream);
+int pg_gp_trsm_diag(const float* l, long ld, float* x, long ldx, int rows, int jb, int done, int transposed, void* stream);
+int pg_gp_potrf(float* a, long ld, int n, int n_done, int* info, void* stream);
+int pg_gp_trsm_right(const float* l, long ld, int n, float* x, long ldx, int rows, int col_done, int transposed, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Density estimators (models/mixture_models.py, models/kde.py) on streaming log-density kernels (density.hip):
  * the pairwise log-density c[n][k] = sum_d f(x[n][d], theta[k][d]) is one or two fp32-MFMA GEMMs plus a per-column
  * constant, reduced by a running logsumexp over column tiles; nothing of size N x K (x F) is written to memory.

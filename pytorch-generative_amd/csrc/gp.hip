@@ -1,0 +1,636 @@
+// gp.hip — the dense symmetric solve of a Gaussian process (reference models/gaussian_process.py): squared-exponential
+// covariance, a blocked right-looking fp32 Cholesky factorisation that can be APPENDED to, the triangular solves X L^T = B and
+// X L = B, and the strided GEMM update C = C -/+ A B^T they are built from. Everything is fp32 and every operand is a row-major
+// matrix with a leading dimension in floats, so a factor lives in a buffer larger than itself.
+//
+// The chain-order property. Element (i, j) of the factor is
+//     l_ij = (a_ij - sum_{k < j} l_ik l_jk) / l_jj          (a square root on the diagonal),
+// and every kernel here forms that sum as ONE chain v = fmaf(-l_ik, l_jk, v) in ascending k that starts from a_ij:
+//   * gp_gemm_kernel seeds its accumulators with the tile of C and multiplies -A: an fp32 MFMA is an fmaf chain per output in k
+//     order, so a trailing update applied panel after panel continues the same chain, whatever the blocking;
+//   * gp_potrf_diag_kernel and gp_trsm_diag_kernel continue it on the VALU inside the panel of 64 columns that holds j, then
+//     take one square root or one IEEE division (no explicit inverse of a diagonal block).
+// The chain of an element therefore does not depend on how many rows the matrix had when its row was factored: completing rows
+// n_done .. n of a factor (pg_gp_potrf with n_done > 0) gives the bits of the full factorisation. Panels sit at absolute
+// multiples of 64; the MFMA only multiplies whole finished panels, the panel that contains n_done is finished on the VALU.
+//
+// No float atomics, each output element is owned by one lane, every order is fixed by the shape: bit-identical from run to
+// run. No host synchronisation and no allocation: capturable. gp_plan is the one function that decides the domain and the
+// geometry; every entry point calls it, and reports a missing device only after it accepted the problem.
+#include <algorithm>
+
+#include "common.h"
+
+namespace {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int GP_T = 64;         // panel width, tile edge
+constexpr int GP_KC = 32;        // k per LDS chunk
+constexpr int GP_LD = 34;        // LDS row stride of an operand chunk: the 16x16x4 operand reads are conflict free (dense_linear.hip)
+constexpr int GP_THREADS = 256;  // 4 waves, 2 x 2, each 32 x 32 as 2 x 2 accumulators of v_mfma_f32_16x16x4_f32
+constexpr int GP_BLK_LD = 68;    // LDS row stride of the diagonal block in gp_potrf_diag_kernel
+constexpr int GP_TRI_LD = 65;    // LDS row stride of the diagonal block in gp_trsm_diag_kernel and of the rows in gp_se_direct_kernel
+constexpr int GP_MAX_N = 16384;  // n, m: element offsets of an (n, n) matrix fit 32 bits
+constexpr int GP_MAX_D = 4096;
+constexpr int GP_MAX_P = 4096;
+constexpr int GP_SE_DIRECT_D = 16;      // largest d of the exact-difference route: measured faster up to 16, slower from 32 (profiles/gp.json)
+constexpr int GP_SE_DIRECT_MAX_D = 64;  // largest d the exact-difference kernel holds in LDS when the route is forced
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// The 64 x 64 x K product of one workgroup: acc += (NEG ? -A : A) B^T with A(r, k) = a[r * a_rs + k] and
+// B(c, k) = b[c * b_rs + k * b_ks], in LDS chunks of 32 k, the next chunk in registers while this one multiplies. Ragged edges
+// are zero-filled. NORMS: thread t < 64 also sums A(r0 + t, k)^2, thread 64 + t B(c0 + t, k)^2, in k order.
+struct GpMma {
+  const float* a;
+  const float* b;
+  long a_rs, b_rs, b_ks;
+  int R, C, K;
+};
+
+template <bool BK, bool NEG, bool NORMS>
+__device__ __forceinline__ void gp_mma_tile(const GpMma& p, int r0, int c0, float* s_a, float* s_b, f32x4 (&acc)[2][2], float& norm) {
+  constexpr int PER = GP_T * GP_KC / GP_THREADS;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int lr = lane & 15, lk = lane >> 4;
+  const int wr = wave >> 1, wc = wave & 1;
+  float ra[PER], rb[PER];
+  auto load = [&](int k0) {
+#pragma unroll
+    for (int j = 0; j < PER; ++j) {
+      const int e = tid + j * GP_THREADS;
+      const int r = e / GP_KC, k = e % GP_KC;
+      const int gr = r0 + r, gk = k0 + k;
+      const float v = (gr < p.R && gk < p.K) ? p.a[(size_t)gr * p.a_rs + gk] : 0.f;
+      ra[j] = NEG ? -v : v;
+    }
+#pragma unroll
+    for (int j = 0; j < PER; ++j) {
+      const int e = tid + j * GP_THREADS;
+      const int c = BK ? e / GP_KC : e % GP_T, k = BK ? e % GP_KC : e / GP_T;
+      const int gc = c0 + c, gk = k0 + k;
+      rb[j] = (gc < p.C && gk < p.K) ? p.b[(size_t)gc * p.b_rs + (size_t)gk * p.b_ks] : 0.f;
+    }
+  };
+  auto store = [&]() {
+#pragma unroll
+    for (int j = 0; j < PER; ++j) {
+      const int e = tid + j * GP_THREADS;
+      s_a[(e / GP_KC) * GP_LD + e % GP_KC] = ra[j];
+      const int c = BK ? e / GP_KC : e % GP_T, k = BK ? e % GP_KC : e / GP_T;
+      s_b[c * GP_LD + k] = rb[j];
+    }
+  };
+  const int nch = (p.K + GP_KC - 1) / GP_KC;
+  load(0);
+  for (int ch = 0; ch < nch; ++ch) {
+    store();
+    __syncthreads();
+    if (ch + 1 < nch) load((ch + 1) * GP_KC);
+    const float* ap = s_a + (wr * 32 + lr) * GP_LD + lk;
+    const float* bp = s_b + (wc * 32 + lr) * GP_LD + lk;
+#pragma unroll
+    for (int kk = 0; kk < GP_KC; kk += 4) {
+      const float a0 = ap[kk], a1 = ap[16 * GP_LD + kk];
+      const float b0 = bp[kk], b1 = bp[16 * GP_LD + kk];
+      acc[0][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b0, acc[0][0], 0, 0, 0);
+      acc[0][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b1, acc[0][1], 0, 0, 0);
+      acc[1][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b0, acc[1][0], 0, 0, 0);
+      acc[1][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b1, acc[1][1], 0, 0, 0);
+    }
+    if (NORMS && tid < 2 * GP_T) {
+      const float* row = (tid < GP_T ? s_a + tid * GP_LD : s_b + (tid - GP_T) * GP_LD);
+#pragma unroll
+      for (int k = 0; k < GP_KC; ++k) norm = fmaf(row[k], row[k], norm);  // zero beyond K
+    }
+    __syncthreads();
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// C = C -/+ A B^T. The accumulators are seeded with the tile of C. lower: only elements with c <= r + diag_off are read and
+// written, tiles wholly above that line return at once; mirror (square, diag_off = 0): C[c][r] = C[r][c] too.
+struct GpGemmArgs {
+  GpMma m;
+  float* c;
+  long ldc;
+  int diag_off, lower, mirror, col_tiles;
+};
+
+template <bool BK, bool NEG>
+__global__ void __launch_bounds__(GP_THREADS) gp_gemm_kernel(const GpGemmArgs p) {
+  __shared__ float s_a[GP_T * GP_LD];
+  __shared__ float s_b[GP_T * GP_LD];
+  const int r0 = (blockIdx.x / p.col_tiles) * GP_T, c0 = (blockIdx.x % p.col_tiles) * GP_T;
+  if (p.lower && c0 > r0 + (GP_T - 1) + p.diag_off) return;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int lr = lane & 15, lk = lane >> 4, wr = wave >> 1, wc = wave & 1;
+  f32x4 acc[2][2];
+  // D layout of 16x16: column = lane & 15, row = 4 (lane >> 4) + reg
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int gr = r0 + (wr * 2 + i) * 16 + 4 * lk + q, gc = c0 + (wc * 2 + j) * 16 + lr;
+        const bool ok = gr < p.m.R && gc < p.m.C && (!p.lower || gc <= gr + p.diag_off);
+        acc[i][j][q] = ok ? p.c[(size_t)gr * p.ldc + gc] : 0.f;
+      }
+  float unused = 0.f;
+  gp_mma_tile<BK, NEG, false>(p.m, r0, c0, s_a, s_b, acc, unused);
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int gr = r0 + (wr * 2 + i) * 16 + 4 * lk + q, gc = c0 + (wc * 2 + j) * 16 + lr;
+        if (!(gr < p.m.R && gc < p.m.C && (!p.lower || gc <= gr + p.diag_off))) continue;
+        p.c[(size_t)gr * p.ldc + gc] = acc[i][j][q];
+        if (p.mirror && gc != gr) p.c[(size_t)gc * p.ldc + gr] = acc[i][j][q];
+      }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// Squared-exponential covariance K[i][j] = std^2 exp(-|a_i - b_j|^2 / (2 l^2)): neg_inv = -1 / (2 l^2) and std2 come from the
+// host. lower / mirror as in the GEMM; diag: elements with j == i + diag_off are written as exactly diag_val.
+struct GpSeArgs {
+  const float* a;
+  const float* b;
+  float* k;
+  long lda, ldb, ldk;
+  int n, m, d, diag_off, lower, mirror, diag, col_tiles;
+  float std2, neg_inv, diag_val;
+};
+
+__device__ __forceinline__ void gp_se_store(const GpSeArgs& p, int gr, int gc, float sq) {
+  if (!(gr < p.n && gc < p.m && (!p.lower || gc <= gr + p.diag_off))) return;
+  float v = p.std2 * expf(sq * p.neg_inv);
+  if (p.diag && gc == gr + p.diag_off) v = p.diag_val;
+  p.k[(size_t)gr * p.ldk + gc] = v;
+  if (p.mirror && gc != gr) p.k[(size_t)gc * p.ldk + gr] = v;
+}
+
+// exact differences sum_k (a_ik - b_jk)^2 on the VALU, k ascending; d <= 64. A thread owns 4 x 4 elements of the tile.
+__global__ void __launch_bounds__(GP_THREADS) gp_se_direct_kernel(const GpSeArgs p) {
+  __shared__ float s_a[GP_T * GP_TRI_LD];
+  __shared__ float s_b[GP_T * GP_TRI_LD];
+  const int r0 = (blockIdx.x / p.col_tiles) * GP_T, c0 = (blockIdx.x % p.col_tiles) * GP_T;
+  if (p.lower && c0 > r0 + (GP_T - 1) + p.diag_off) return;
+  const int tid = threadIdx.x;
+  for (int e = tid; e < GP_T * p.d; e += GP_THREADS) {
+    const int r = e / p.d, k = e % p.d;
+    s_a[r * GP_TRI_LD + k] = r0 + r < p.n ? p.a[(size_t)(r0 + r) * p.lda + k] : 0.f;
+    s_b[r * GP_TRI_LD + k] = c0 + r < p.m ? p.b[(size_t)(c0 + r) * p.ldb + k] : 0.f;
+  }
+  __syncthreads();
+  const int tx = tid & 15, ty = tid >> 4;
+  float sq[4][4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) sq[i][j] = 0.f;
+  for (int k = 0; k < p.d; ++k) {
+    float av[4], bv[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      av[i] = s_a[(ty + 16 * i) * GP_TRI_LD + k];
+      bv[i] = s_b[(tx + 16 * i) * GP_TRI_LD + k];
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float df = av[i] - bv[j];
+        sq[i][j] = fmaf(df, df, sq[i][j]);
+      }
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) gp_se_store(p, r0 + ty + 16 * i, c0 + tx + 16 * j, sq[i][j]);
+}
+
+// |a|^2 + |b|^2 - 2 a.b with the cross term on the MFMA, clamped at 0 before the exp
+__global__ void __launch_bounds__(GP_THREADS) gp_se_mfma_kernel(const GpSeArgs p) {
+  __shared__ float s_a[GP_T * GP_LD];
+  __shared__ float s_b[GP_T * GP_LD];
+  __shared__ float s_n[2 * GP_T];
+  const int r0 = (blockIdx.x / p.col_tiles) * GP_T, c0 = (blockIdx.x % p.col_tiles) * GP_T;
+  if (p.lower && c0 > r0 + (GP_T - 1) + p.diag_off) return;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int lr = lane & 15, lk = lane >> 4, wr = wave >> 1, wc = wave & 1;
+  GpMma m;
+  m.a = p.a;
+  m.b = p.b;
+  m.a_rs = p.lda;
+  m.b_rs = p.ldb;
+  m.b_ks = 1;
+  m.R = p.n;
+  m.C = p.m;
+  m.K = p.d;
+  f32x4 acc[2][2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) acc[i][j][q] = 0.f;
+  float norm = 0.f;
+  gp_mma_tile<true, false, true>(m, r0, c0, s_a, s_b, acc, norm);
+  if (threadIdx.x < 2 * GP_T) s_n[threadIdx.x] = norm;
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int r = (wr * 2 + i) * 16 + 4 * lk + q, c = (wc * 2 + j) * 16 + lr;
+        const float sq = fmaf(-2.f, acc[i][j][q], s_n[r] + s_n[GP_T + c]);
+        gp_se_store(p, r0 + r, c0 + c, fmaxf(sq, 0.f));
+      }
+}
+
+__global__ void __launch_bounds__(256) gp_add_diag_kernel(float* __restrict__ a, long ld, int n, float value) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) a[(size_t)i * ld + i] += value;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// The unblocked Cholesky of one diagonal block (jb <= 64 rows), right-looking inside the block, one workgroup. Rows < done
+// are final and are not written; rows >= done continue their chains from the values the updates left. Per column j: phase A
+// forms column j of the factor into col[] (a square root for the pivot if j >= done, an IEEE division below it for rows >=
+// done); phase B writes it back and applies it to the columns c in (j, i] of the rows i >= done. A pivot that is not > 0
+// (a NaN included) is recorded as base + j + 1 in *info, by one plain store and only while *info is 0; the kernel goes on.
+__global__ void __launch_bounds__(GP_THREADS) gp_potrf_diag_kernel(float* __restrict__ a, long ld, int jb, int done, int base,
+                                                                   int* __restrict__ info) {
+  __shared__ float s[GP_T * GP_BLK_LD];
+  __shared__ float col[GP_T];
+  const int tid = threadIdx.x;
+  for (int e = tid; e < GP_T * GP_T; e += GP_THREADS) {
+    const int i = e >> 6, c = e & 63;
+    s[i * GP_BLK_LD + c] = (i < jb && c <= i) ? a[(size_t)i * ld + c] : 0.f;
+  }
+  int bad = 0;
+  const int ui = tid >> 2, uc = tid & 3;  // the row and the column residue this thread updates
+  for (int j = 0; j < jb; ++j) {
+    __syncthreads();
+    if (tid < GP_T) {
+      const float d = s[j * GP_BLK_LD + j];
+      const bool pivot = j >= done;
+      const float ljj = pivot ? sqrtf(d) : d;
+      if (pivot && !(d > 0.f) && bad == 0) bad = base + j + 1;
+      const float v = s[tid * GP_BLK_LD + j];
+      col[tid] = tid == j ? ljj : ((tid > j && tid >= done) ? v / ljj : v);
+    }
+    __syncthreads();
+    if (tid < GP_T && tid >= j) s[tid * GP_BLK_LD + j] = col[tid];
+    if (ui >= done && ui > j) {
+      const float li = col[ui];
+      for (int q = (j + 1) >> 2; q <= ui >> 2; ++q) {
+        const int c = 4 * q + uc;
+        if (c > j && c <= ui) s[ui * GP_BLK_LD + c] = fmaf(-li, col[c], s[ui * GP_BLK_LD + c]);
+      }
+    }
+  }
+  __syncthreads();
+  for (int e = tid; e < GP_T * GP_T; e += GP_THREADS) {
+    const int i = e >> 6, c = e & 63;
+    if (i < jb && i >= done && c <= i) a[(size_t)i * ld + c] = s[i * GP_BLK_LD + c];
+  }
+  if (tid == 0 && bad != 0 && *info == 0) *info = bad;
+}
+
+// The substitution against one diagonal block, 64 rows of X per workgroup, four lanes per row, each with the columns
+// j = 4 q + (lane & 3) of its row in registers; x_k goes to the row's lanes by a shuffle.
+//   forward (BACK = false): X L^T = B, x_ij = (b_ij - sum_{k < j} x_ik l_jk) / l_jj, k ascending; columns < done are final.
+//   backward (BACK = true): X L = B,   x_ij = (b_ij - sum_{k > j} x_ik l_kj) / l_jj, k descending.
+template <bool BACK>
+__global__ void __launch_bounds__(GP_THREADS) gp_trsm_diag_kernel(const float* __restrict__ l, long ld, float* __restrict__ x, long ldx,
+                                                                  int rows, int jb, int done) {
+  __shared__ float s_l[GP_T * GP_TRI_LD];
+  const int tid = threadIdx.x, lane = tid & 63;
+  for (int e = tid; e < GP_T * GP_T; e += GP_THREADS) {
+    const int j = e >> 6, k = e & 63;
+    float v = j == k ? 1.f : 0.f;  // rows beyond jb: the identity
+    if (j < jb && k <= j) v = l[(size_t)j * ld + k];
+    s_l[j * GP_TRI_LD + k] = v;
+  }
+  const int row = blockIdx.x * GP_T + (tid >> 2), c = tid & 3;
+  float v[16];
+#pragma unroll
+  for (int q = 0; q < 16; ++q) {
+    const int j = 4 * q + c;
+    v[q] = (row < rows && j < jb) ? x[(size_t)row * ldx + j] : 0.f;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int kk = 0; kk < GP_T; ++kk) {
+    const int k = BACK ? GP_T - 1 - kk : kk;
+    if (k < jb) {  // the same in every lane
+      const int qk = k >> 2, ck = k & 3;
+      float cand = v[qk];
+      if (BACK || k >= done) cand = cand / s_l[k * GP_TRI_LD + k];
+      const float xk = __shfl(cand, (lane & ~3) | ck);
+      if (c == ck) v[qk] = xk;
+      if (BACK) {
+#pragma unroll
+        for (int q = 0; q <= qk; ++q) {
+          const int j = 4 * q + c;
+          if (j < k) v[q] = fmaf(-xk, s_l[k * GP_TRI_LD + j], v[q]);
+        }
+      } else {
+#pragma unroll
+        for (int q = qk; q < 16; ++q) {
+          const int j = 4 * q + c;
+          if (j > k && j >= done) v[q] = fmaf(-xk, s_l[j * GP_TRI_LD + k], v[q]);
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < 16; ++q) {
+    const int j = 4 * q + c;
+    if (row < rows && j < jb && j >= done) x[(size_t)row * ldx + j] = v[q];
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// The one function that decides the domain and the geometry: pg_gp_plan reports it, every entry point goes by it.
+struct GpPlan {
+  int n, m, d, p, panels, row_tiles, se_route;
+  long se_sym_tiles, se_cross_tiles, potrf_launches, trsm_launches, trailing_groups;
+};
+
+int gp_plan(int n, int m, int d, int p, GpPlan& pl, const char* name) {
+  PG_REQUIRE(n >= 1 && m >= 1 && d >= 1 && p >= 1, PG_ESHAPE, "%s: n = %d, m = %d, d = %d, p = %d must all be >= 1", name, n, m, d, p);
+  PG_REQUIRE(n <= GP_MAX_N && m <= GP_MAX_N, PG_ESHAPE, "%s: n = %d, m = %d: at most %d rows (element offsets stay inside 32 bits)", name, n, m,
+             GP_MAX_N);
+  PG_REQUIRE(d <= GP_MAX_D && p <= GP_MAX_P, PG_ESHAPE, "%s: d = %d (at most %d), p = %d (at most %d)", name, d, GP_MAX_D, p, GP_MAX_P);
+  pl.n = n;
+  pl.m = m;
+  pl.d = d;
+  pl.p = p;
+  pl.panels = pg_cdiv(n, GP_T);
+  pl.row_tiles = pg_cdiv(m, GP_T);
+  pl.se_route = d <= GP_SE_DIRECT_D ? 0 : 1;
+  pl.se_sym_tiles = (long)pl.panels * (pl.panels + 1) / 2;
+  pl.se_cross_tiles = (long)pl.row_tiles * pl.panels;
+  pl.potrf_launches = 3L * pl.panels - 2;  // diagonal block, panel solve, trailing update; the last panel has no rows below
+  pl.trsm_launches = 2L * pl.panels - 1;   // panel solve, update of the columns to the right
+  pl.trailing_groups = (long)(pl.panels - 1) * (pl.panels - 1);
+  return 0;
+}
+
+#define GP_PLAN_OR_RETURN(pl, n, m, d, p, name)        \
+  GpPlan pl;                                           \
+  {                                                    \
+    const int rc__ = gp_plan(n, m, d, p, pl, name);    \
+    if (rc__) return rc__;                             \
+  }                                                    \
+  (void)pl;
+
+// a missing device is reported once the plan and the argument checks accepted the call
+int gp_device(const char* name) {
+  static bool seen = false;
+  if (seen) return 0;
+  int count = 0;
+  if (hipGetDeviceCount(&count) != hipSuccess || count < 1) {
+    (void)hipGetLastError();
+    pg_set_error("%s: no HIP device", name);
+    return (int)hipErrorNoDevice;
+  }
+  seen = true;
+  return 0;
+}
+
+// the launches; arguments are checked by the callers
+int gp_gemm(const float* a, long lda, const float* b, long ldb, float* c, long ldc, int R, int C, int K, int diag_off, int flags,
+            hipStream_t st, const char* name) {
+  GpGemmArgs p;
+  p.m.a = a;
+  p.m.a_rs = lda;
+  p.m.b = b;
+  const bool bt = (flags & PG_GP_B_TRANS) != 0;
+  p.m.b_rs = bt ? 1 : ldb;
+  p.m.b_ks = bt ? ldb : 1;
+  p.m.R = R;
+  p.m.C = C;
+  p.m.K = K;
+  p.c = c;
+  p.ldc = ldc;
+  p.diag_off = diag_off;
+  p.lower = (flags & PG_GP_LOWER) != 0;
+  p.mirror = (flags & PG_GP_MIRROR) != 0;
+  p.col_tiles = pg_cdiv(C, GP_T);
+  const dim3 grid((unsigned)((long)pg_cdiv(R, GP_T) * p.col_tiles));
+  const bool plus = (flags & PG_GP_PLUS) != 0;
+  if (bt) {
+    if (plus)
+      hipLaunchKernelGGL((gp_gemm_kernel<false, false>), grid, dim3(GP_THREADS), 0, st, p);
+    else
+      hipLaunchKernelGGL((gp_gemm_kernel<false, true>), grid, dim3(GP_THREADS), 0, st, p);
+  } else {
+    if (plus)
+      hipLaunchKernelGGL((gp_gemm_kernel<true, false>), grid, dim3(GP_THREADS), 0, st, p);
+    else
+      hipLaunchKernelGGL((gp_gemm_kernel<true, true>), grid, dim3(GP_THREADS), 0, st, p);
+  }
+  PG_LAUNCH_CHECK(name);
+  return 0;
+}
+
+int gp_potrf_diag(float* a, long ld, int jb, int done, int base, int* info, hipStream_t st, const char* name) {
+  hipLaunchKernelGGL(gp_potrf_diag_kernel, dim3(1), dim3(GP_THREADS), 0, st, a, ld, jb, done, base, info);
+  PG_LAUNCH_CHECK(name);
+  return 0;
+}
+
+int gp_trsm_diag(const float* l, long ld, float* x, long ldx, int rows, int jb, int done, int back, hipStream_t st, const char* name) {
+  const dim3 grid((unsigned)pg_cdiv(rows, GP_T));
+  if (back)
+    hipLaunchKernelGGL(gp_trsm_diag_kernel<true>, grid, dim3(GP_THREADS), 0, st, l, ld, x, ldx, rows, jb, 0);
+  else
+    hipLaunchKernelGGL(gp_trsm_diag_kernel<false>, grid, dim3(GP_THREADS), 0, st, l, ld, x, ldx, rows, jb, done);
+  PG_LAUNCH_CHECK(name);
+  return 0;
+}
+
+#define GP_TRY(call)           \
+  do {                         \
+    const int rc__ = (call);   \
+    if (rc__) return rc__;     \
+  } while (0)
+
+}  // namespace
+
+PG_EXPORT int pg_gp_plan(int n, int m, int d, int p, long long* out, int out_len) {
+  PG_REQUIRE(out && out_len >= PG_GP_PLAN_INTS, PG_EINVAL, "pg_gp_plan: null pointer or short output array");
+  GP_PLAN_OR_RETURN(pl, n, m, d, p, "pg_gp_plan");
+  out[0] = GP_T;
+  out[1] = GP_KC;
+  out[2] = pl.panels;
+  out[3] = pl.row_tiles;
+  out[4] = pl.se_route;
+  out[5] = GP_SE_DIRECT_D;
+  out[6] = pl.se_sym_tiles;
+  out[7] = pl.se_cross_tiles;
+  out[8] = pl.potrf_launches;
+  out[9] = pl.trsm_launches;
+  out[10] = pl.trailing_groups;
+  out[11] = GP_MAX_N;
+  out[12] = GP_MAX_D;
+  out[13] = GP_MAX_P;
+  out[14] = pg_cdiv(p, GP_T);
+  out[15] = GP_SE_DIRECT_MAX_D;
+  return 0;
+}
+
+PG_EXPORT int pg_gp_se_kernel(const float* a, long lda, int n, const float* b, long ldb, int m, int d, float std, float lengthscale,
+                              float noise_var, float* k, long ldk, int diag_off, int flags, void* stream) {
+  GP_PLAN_OR_RETURN(pl, n, m, d, 1, "pg_gp_se_kernel");
+  PG_REQUIRE(a && b && k, PG_EINVAL, "pg_gp_se_kernel: null pointer");
+  PG_REQUIRE(lda >= d && ldb >= d && ldk >= m, PG_EINVAL, "pg_gp_se_kernel: a row stride below its row length");
+  PG_REQUIRE(lengthscale > 0.f && std == std && noise_var == noise_var, PG_EINVAL,
+             "pg_gp_se_kernel: lengthscale = %g must be > 0, std and noise_var no NaN", (double)lengthscale);
+  const int known = PG_GP_LOWER | PG_GP_MIRROR | PG_GP_DIAG | PG_GP_SE_DIRECT | PG_GP_SE_MFMA;
+  PG_REQUIRE((flags & ~known) == 0 && (flags & (PG_GP_SE_DIRECT | PG_GP_SE_MFMA)) != (PG_GP_SE_DIRECT | PG_GP_SE_MFMA), PG_EINVAL,
+             "pg_gp_se_kernel: flags %d", flags);
+  PG_REQUIRE(diag_off > -GP_MAX_N && diag_off < GP_MAX_N, PG_EINVAL, "pg_gp_se_kernel: diag_off = %d", diag_off);
+  PG_REQUIRE(!(flags & PG_GP_MIRROR) || ((flags & PG_GP_LOWER) && a == b && lda == ldb && n == m && diag_off == 0), PG_EINVAL,
+             "pg_gp_se_kernel: the mirror takes the symmetric form (a is b, lower, diag_off = 0)");
+  int route = pl.se_route;
+  if (flags & PG_GP_SE_MFMA) route = 1;
+  if (flags & PG_GP_SE_DIRECT) {
+    PG_REQUIRE(d <= GP_SE_DIRECT_MAX_D, PG_ESHAPE, "pg_gp_se_kernel: the exact-difference route holds d <= %d, got %d", GP_SE_DIRECT_MAX_D, d);
+    route = 0;
+  }
+  GP_TRY(gp_device("pg_gp_se_kernel"));
+  GpSeArgs p;
+  p.a = a;
+  p.b = b;
+  p.k = k;
+  p.lda = lda;
+  p.ldb = ldb;
+  p.ldk = ldk;
+  p.n = n;
+  p.m = m;
+  p.d = d;
+  p.diag_off = diag_off;
+  p.lower = (flags & PG_GP_LOWER) != 0;
+  p.mirror = (flags & PG_GP_MIRROR) != 0;
+  p.diag = (flags & PG_GP_DIAG) != 0;
+  p.col_tiles = pg_cdiv(m, GP_T);
+  p.std2 = std * std;
+  p.neg_inv = -0.5f / (lengthscale * lengthscale);
+  p.diag_val = p.std2 + noise_var;
+  const dim3 grid((unsigned)((long)pg_cdiv(n, GP_T) * p.col_tiles));
+  if (route == 0)
+    hipLaunchKernelGGL(gp_se_direct_kernel, grid, dim3(GP_THREADS), 0, (hipStream_t)stream, p);
+  else
+    hipLaunchKernelGGL(gp_se_mfma_kernel, grid, dim3(GP_THREADS), 0, (hipStream_t)stream, p);
+  PG_LAUNCH_CHECK("pg_gp_se_kernel");
+  return 0;
+}
+
+PG_EXPORT int pg_gp_add_diag(float* a, long ld, int n, float value, void* stream) {
+  GP_PLAN_OR_RETURN(pl, n, 1, 1, 1, "pg_gp_add_diag");
+  PG_REQUIRE(a && ld >= n, PG_EINVAL, "pg_gp_add_diag: null pointer or a row stride below the row length");
+  GP_TRY(gp_device("pg_gp_add_diag"));
+  hipLaunchKernelGGL(gp_add_diag_kernel, dim3((unsigned)pg_cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, a, ld, n, value);
+  PG_LAUNCH_CHECK("pg_gp_add_diag");
+  return 0;
+}
+
+PG_EXPORT int pg_gp_gemm_nt(const float* a, long lda, const float* b, long ldb, float* c, long ldc, int R, int C, int K, int diag_off,
+                            int flags, void* stream) {
+  GP_PLAN_OR_RETURN(pl, R, C, 1, 1, "pg_gp_gemm_nt");
+  PG_REQUIRE(K >= 1 && K <= GP_MAX_N, PG_ESHAPE, "pg_gp_gemm_nt: K = %d outside 1 .. %d", K, GP_MAX_N);
+  PG_REQUIRE(a && b && c, PG_EINVAL, "pg_gp_gemm_nt: null pointer");
+  const int known = PG_GP_LOWER | PG_GP_MIRROR | PG_GP_PLUS | PG_GP_B_TRANS;
+  PG_REQUIRE((flags & ~known) == 0, PG_EINVAL, "pg_gp_gemm_nt: flags %d", flags);
+  PG_REQUIRE(lda >= K && ldb >= ((flags & PG_GP_B_TRANS) ? C : K) && ldc >= C, PG_EINVAL, "pg_gp_gemm_nt: a row stride below its row length");
+  PG_REQUIRE(diag_off > -GP_MAX_N && diag_off < GP_MAX_N, PG_EINVAL, "pg_gp_gemm_nt: diag_off = %d", diag_off);
+  PG_REQUIRE(!(flags & PG_GP_MIRROR) || ((flags & PG_GP_LOWER) && R == C && diag_off == 0), PG_EINVAL,
+             "pg_gp_gemm_nt: the mirror takes a square lower update with diag_off = 0");
+  GP_TRY(gp_device("pg_gp_gemm_nt"));
+  return gp_gemm(a, lda, b, ldb, c, ldc, R, C, K, diag_off, flags, (hipStream_t)stream, "pg_gp_gemm_nt");
+}
+
+PG_EXPORT int pg_gp_potrf_diag(float* a, long ld, int jb, int done, int base, int* info, void* stream) {
+  PG_REQUIRE(jb >= 1 && jb <= GP_T && done >= 0 && done <= jb && base >= 0, PG_ESHAPE,
+             "pg_gp_potrf_diag: jb = %d (1 .. %d), done = %d (0 .. jb), base = %d (>= 0)", jb, GP_T, done, base);
+  GP_PLAN_OR_RETURN(pl, (int)std::min<long>((long)base + jb, 1L << 30), 1, 1, 1, "pg_gp_potrf_diag");  // the block ends inside n <= 16384
+  PG_REQUIRE(a && info && ld >= jb, PG_EINVAL, "pg_gp_potrf_diag: null pointer or a row stride below the row length");
+  GP_TRY(gp_device("pg_gp_potrf_diag"));
+  return gp_potrf_diag(a, ld, jb, done, base, info, (hipStream_t)stream, "pg_gp_potrf_diag");
+}
+
+PG_EXPORT int pg_gp_trsm_diag(const float* l, long ld, float* x, long ldx, int rows, int jb, int done, int transposed, void* stream) {
+  GP_PLAN_OR_RETURN(pl, 1, rows, 1, 1, "pg_gp_trsm_diag");
+  PG_REQUIRE(jb >= 1 && jb <= GP_T && done >= 0 && done <= jb, PG_ESHAPE, "pg_gp_trsm_diag: jb = %d (1 .. %d), done = %d (0 .. jb)", jb, GP_T,
+             done);
+  PG_REQUIRE(l && x && ld >= jb && ldx >= jb, PG_EINVAL, "pg_gp_trsm_diag: null pointer or a row stride below the row length");
+  PG_REQUIRE(!transposed || done == 0, PG_EINVAL, "pg_gp_trsm_diag: the X L = B form completes no columns (done = %d)", done);
+  GP_TRY(gp_device("pg_gp_trsm_diag"));
+  return gp_trsm_diag(l, ld, x, ldx, rows, jb, done, transposed != 0, (hipStream_t)stream, "pg_gp_trsm_diag");
+}
+
+PG_EXPORT int pg_gp_potrf(float* a, long ld, int n, int n_done, int* info, void* stream) {
+  GP_PLAN_OR_RETURN(pl, n, 1, 1, 1, "pg_gp_potrf");
+  PG_REQUIRE(n_done >= 0 && n_done <= n, PG_ESHAPE, "pg_gp_potrf: n_done = %d outside 0 .. n = %d", n_done, n);
+  PG_REQUIRE(a && info && ld >= n, PG_EINVAL, "pg_gp_potrf: null pointer or a row stride below the row length");
+  GP_TRY(gp_device("pg_gp_potrf"));
+  if (n_done == n) return 0;
+  const hipStream_t st = (hipStream_t)stream;
+  const char* name = "pg_gp_potrf";
+  const int first = n_done / GP_T;  // the first panel with unfinished columns
+  // the new rows through the finished whole panels: solve against the panel's diagonal block, update the columns to its right
+  for (int k = 0; k < first; ++k) {
+    const int j0 = k * GP_T, rows = n - n_done, right = n - (j0 + GP_T);
+    float* x = a + (size_t)n_done * ld + j0;
+    GP_TRY(gp_trsm_diag(a + (size_t)j0 * ld + j0, ld, x, ld, rows, GP_T, 0, 0, st, name));
+    GP_TRY(gp_gemm(x, ld, a + (size_t)(j0 + GP_T) * ld + j0, ld, x + GP_T, ld, rows, right, GP_T, n_done - (j0 + GP_T), PG_GP_LOWER, st, name));
+  }
+  for (int k = first; k < pl.panels; ++k) {
+    const int j0 = k * GP_T, jb = std::min(GP_T, n - j0), below = n - j0 - jb;
+    float* diag = a + (size_t)j0 * ld + j0;
+    GP_TRY(gp_potrf_diag(diag, ld, jb, std::max(0, n_done - j0), j0, info, st, name));
+    if (below > 0) {
+      float* x = diag + (size_t)GP_T * ld;
+      GP_TRY(gp_trsm_diag(diag, ld, x, ld, below, GP_T, 0, 0, st, name));
+      GP_TRY(gp_gemm(x, ld, x, ld, x + GP_T, ld, below, below, GP_T, 0, PG_GP_LOWER, st, name));
+    }
+  }
+  return 0;
+}
+
+PG_EXPORT int pg_gp_trsm_right(const float* l, long ld, int n, float* x, long ldx, int rows, int col_done, int transposed, void* stream) {
+  GP_PLAN_OR_RETURN(pl, n, rows, 1, 1, "pg_gp_trsm_right");
+  PG_REQUIRE(col_done >= 0 && col_done <= n, PG_ESHAPE, "pg_gp_trsm_right: col_done = %d outside 0 .. n = %d", col_done, n);
+  PG_REQUIRE(l && x && ld >= n && ldx >= n, PG_EINVAL, "pg_gp_trsm_right: null pointer or a row stride below the row length");
+  PG_REQUIRE(!transposed || col_done == 0, PG_EINVAL, "pg_gp_trsm_right: the X L = B form completes no columns (col_done = %d)", col_done);
+  GP_TRY(gp_device("pg_gp_trsm_right"));
+  if (col_done == n) return 0;
+  const hipStream_t st = (hipStream_t)stream;
+  const char* name = "pg_gp_trsm_right";
+  if (transposed) {
+    for (int k = pl.panels - 1; k >= 0; --k) {
+      const int j0 = k * GP_T, jb = std::min(GP_T, n - j0);
+      GP_TRY(gp_trsm_diag(l + (size_t)j0 * ld + j0, ld, x + j0, ldx, rows, jb, 0, 1, st, name));
+      if (j0 > 0) GP_TRY(gp_gemm(x + j0, ldx, l + (size_t)j0 * ld, ld, x, ldx, rows, j0, jb, 0, PG_GP_B_TRANS, st, name));
+    }
+    return 0;
+  }
+  const int first = col_done / GP_T;
+  // the finished whole panels act on the new columns as one product: the same chain as panel after panel
+  if (first > 0) GP_TRY(gp_gemm(x, ldx, l + (size_t)col_done * ld, ld, x + col_done, ldx, rows, n - col_done, first * GP_T, 0, 0, st, name));
+  for (int k = first; k < pl.panels; ++k) {
+    const int j0 = k * GP_T, jb = std::min(GP_T, n - j0), right = n - j0 - jb;
+    GP_TRY(gp_trsm_diag(l + (size_t)j0 * ld + j0, ld, x + j0, ldx, rows, jb, std::max(0, col_done - j0), 0, st, name));
+    if (right > 0) GP_TRY(gp_gemm(x + j0, ldx, l + (size_t)(j0 + GP_T) * ld + j0, ld, x + j0 + GP_T, ldx, rows, right, GP_T, 0, 0, st, name));
+  }
+  return 0;
+}

@@ -145,6 +145,14 @@ SIGNATURES = {
     "pg_fvbn_sample": (c_i, [c_f] * 5 + [c_i] * 2 + [c_s]),
     "pg_fvbn_pack": (c_i, [c_f] * 2 + [c_i, c_s]),
     "pg_fvbn_unpack": (c_i, [c_f] * 2 + [c_i, c_s]),
+    "pg_gp_plan": (c_i, [c_i] * 4 + [ctypes.POINTER(ctypes.c_longlong), c_i]),
+    "pg_gp_se_kernel": (c_i, [c_f, c_l, c_i, c_f, c_l, c_i, c_i, c_flt, c_flt, c_flt, c_f, c_l, c_i, c_i, c_s]),
+    "pg_gp_add_diag": (c_i, [c_f, c_l, c_i, c_flt, c_s]),
+    "pg_gp_gemm_nt": (c_i, [c_f, c_l, c_f, c_l, c_f, c_l] + [c_i] * 5 + [c_s]),
+    "pg_gp_potrf_diag": (c_i, [c_f, c_l] + [c_i] * 3 + [c_f, c_s]),
+    "pg_gp_trsm_diag": (c_i, [c_f, c_l, c_f, c_l] + [c_i] * 4 + [c_s]),
+    "pg_gp_potrf": (c_i, [c_f, c_l, c_i, c_i, c_f, c_s]),
+    "pg_gp_trsm_right": (c_i, [c_f, c_l, c_i, c_f, c_l] + [c_i] * 3 + [c_s]),
     "pg_nice_scale_fwd": (c_i, [c_f] * 3 + [c_i] * 3 + [c_s]),
     "pg_nice_scale_bwd_workspace_floats": (c_z, [c_i] * 2),
     "pg_nice_scale_bwd": (c_i, [c_f] * 5 + [c_i] * 3 + [c_f, c_z, c_s]),

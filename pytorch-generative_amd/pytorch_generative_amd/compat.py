@@ -11,7 +11,8 @@ components that are not exported at the reference's place resolve to placeholder
 FullyVisibleBeliefNetwork are built and live in `models.autoregressive.nade` and `models.autoregressive.fvbn`, which the alias
 serves as they are; the top-level names `models.NADE` and `models.FullyVisibleBeliefNetwork` are not exported and keep their
 placeholders under the alias. NICE is built and lives in `models.flows.nice` (package `flows`, plural); the reference's
-two names for it, `models.NICE` and `models.flow.nice`, keep their raising placeholders under the alias.
+two names for it, `models.NICE` and `models.flow.nice`, keep their raising placeholders under the alias. The Gaussian process
+is served as `models.gaussian_process`; as in the reference there is no top-level `models.GaussianProcess`.
 """
 
 import sys
@@ -55,6 +56,7 @@ def install_alias(name="pytorch_generative"):
         f"{name}.models.autoregressive": _pkg.models.autoregressive,
         f"{name}.models.vae": _pkg.models.vae,
         f"{name}.models.kde": _pkg.models.kde,
+        f"{name}.models.gaussian_process": _pkg.models.gaussian_process,
         f"{name}.models.mixture_models": _pkg.models.mixture_models,
         f"{name}.trainer": _pkg.trainer,
         f"{name}.datasets": _pkg.datasets,

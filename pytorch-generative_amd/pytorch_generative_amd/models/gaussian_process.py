@@ -1,0 +1,268 @@
+"""The Gaussian process model on the MI355X path (reference models/gaussian_process.py).
+
+p(f) = N(f | mean(x), kernel(x, x')); observations carry independent noise of variance noise_var. Same constructor, `fit`,
+`predict` and `sample` as the reference, and the same `noise_var` buffer. The reference solves the full (n, n) training
+covariance with an LU factorisation inside every `predict`; here the covariance is factored ONCE by a blocked fp32 Cholesky
+(ops.cholesky_, csrc/gp.hip) into a buffer that grows, and a `fit` of further points only completes the new rows of the factor
+(`incremental`, below): O(n^2) per added point instead of O(n^3), as the Bayesian-optimisation loop of the reference's notebook
+(fit one point, predict, sample, repeat) wants it.
+
+With K = kernel(train, train) + noise_var I = L L^T, r = y - mean(train), z = L^-1 r and alpha = L^-T z, `predict(x)` is
+    Kx^T = kernel(x, train)                (m, n): the training rows stay where they lie
+    mu   = mean(x) + Kx^T alpha            (ops.gemm_nt_)
+    W    = Kx^T L^-T                       (ops.trsm_right_, one forward solve)
+    sig  = kernel(x, x) - W W^T            (ops.gemm_nt_, lower triangle only, mirrored: exactly symmetric)
+
+Stated deviations from the reference:
+  * Cholesky replaces LU. Where the training covariance is numerically singular (noise_var = 0 on dense data) the reference
+    returns noise; this raises torch.linalg.LinAlgError naming the failed pivot.
+  * Outputs carry no gradient, and an input that requires grad raises. Gradients with respect to hyperparameters and a
+    marginal likelihood are not built.
+  * `sample` draws on the GPU from torch's generator and returns fp32 on the device (the reference: float64 from numpy).
+SquaredExponential and Const restate the two callables the reference defines only in its notebook."""
+
+import torch
+from torch import nn
+
+from pytorch_generative_amd import ops
+from pytorch_generative_amd.models import base
+
+_TILE = 64
+JITTER_LADDER = (0.0, 1e-6, 1e-5, 1e-4, 1e-3, 1e-2)
+
+
+def _host_value(owner, name):
+    """The hyperparameter `name` of `owner` as a Python float. A tensor is read (a host synchronisation if it lives on the GPU)
+    only when it is another tensor, lies elsewhere or was modified in place since the last look, so a `predict` with unchanged
+    hyperparameters synchronises nothing. A change made through `.data` is not seen: call GaussianProcess.reset_cache()."""
+    value = getattr(owner, name)
+    if not torch.is_tensor(value):
+        return float(value)
+    cache = owner.__dict__.setdefault("_host_cache", {})
+    key = (id(value), value._version, value.data_ptr())
+    hit = cache.get(name)
+    if hit is None or hit[0] != key:
+        hit = (key, float(value.detach()))
+        cache[name] = hit
+    return hit[1]
+
+
+class SquaredExponential(nn.Module):
+    """k(a, b) = std^2 exp(-|a - b|^2 / (2 lengthscale^2)). std and lengthscale: floats, tensors, or (default) Parameters
+    initialised to 1. Called on 2-D GPU tensors it returns the (rows of left, rows of right) covariance from ops.se_kernel;
+    `kernel(x, x)` (the same tensor twice) is exactly symmetric with the diagonal exactly std^2."""
+
+    def __init__(self, std=None, lengthscale=None):
+        super().__init__()
+        self.std = nn.Parameter(torch.tensor(1.0)) if std is None else std
+        self.lengthscale = nn.Parameter(torch.tensor(1.0)) if lengthscale is None else lengthscale
+
+    def hyperparameters(self):
+        return _host_value(self, "std"), _host_value(self, "lengthscale")
+
+    def forward(self, left, right):
+        std, lengthscale = self.hyperparameters()
+        return ops.se_kernel(left, right, std, lengthscale)
+
+
+class Const(nn.Module):
+    """mean(x) = value for every row: (rows of x, 1) on x's device. value: a float, a tensor, or (default) a Parameter
+    initialised to 0."""
+
+    def __init__(self, value=None):
+        super().__init__()
+        self.value = nn.Parameter(torch.tensor(0.0)) if value is None else value
+
+    def hyperparameters(self):
+        return (_host_value(self, "value"),)
+
+    def forward(self, x):
+        return torch.full((x.shape[0], 1), self.hyperparameters()[0], device=x.device, dtype=torch.float32)
+
+
+class GaussianProcess(base.GenerativeModel):
+    """The Gaussian process model.
+
+    incremental (class attribute, default True; set it on the class or an instance): a `fit` of further points completes
+    only the new rows of the cached factor (`_factor_route == "append"`; the factor has the bits of a full factorisation).
+    The factor is made afresh (`"full"`) when incremental is False, when a hyperparameter value (std, lengthscale, value,
+    noise_var) differs from the one the factor was made with, and when the kernel or the mean is a callable other than
+    SquaredExponential / Const: the model cannot see such a callable's state, so it never appends with it, and after CHANGING
+    that state call reset_cache() — otherwise a cached factor keeps serving `predict` (a SquaredExponential or Const beside such a
+    callable is still watched: a change of its values makes the factor afresh). incremental = False is always safe.
+
+    `_kernel_route` is "se" (SquaredExponential kernel and Const mean: covariances straight from ops.se_kernel) or
+    "callable" (the callables are called on the device tensors; a square result kernel(t, t) is copied as it is, but only its
+    lower triangle is read: the factorisation and the covariance update never look above the diagonal, the output is mirrored)."""
+
+    incremental = True
+
+    def __init__(self, mean, kernel, noise_var=None):
+        """mean: prior mean function mu(x) -> (rows, 1) or (rows, p). kernel: prior covariance function K(x, x').
+        noise_var: the variance of the observation noise (None: noiseless observations)."""
+        super().__init__()
+        self.mean = mean
+        self.kernel = kernel
+        self.register_buffer("noise_var", torch.tensor(noise_var or 0.0))
+        self.train_x = None
+        self.train_y = None
+        self._kernel_route = "se" if isinstance(kernel, SquaredExponential) and isinstance(mean, Const) else "callable"
+        self._factor_route = None
+        self._sample_jitter = None
+        self._sample_factor = None
+        self.reset_cache()
+
+    def reset_cache(self):
+        """Drops the cached factor: the next `predict` factors the whole training covariance."""
+        self._factor = None    # (cap, cap): the lower factor of the leading (_n_factored, _n_factored) block
+        self._zt = None        # (p, cap): rows of z^T = (L^-1 (y - mean))^T
+        self._alpha_t = None   # (p, cap): rows of alpha^T
+        self._n_factored = 0
+        self._factor_key = None
+
+    def fit(self, x, y):
+        """Appends (x (rows, d), y (rows, p)) to the training data, as the reference does; the factor follows at the next
+        `predict`."""
+        if x.dim() != 2 or y.dim() != 2 or x.shape[0] != y.shape[0]:
+            raise ValueError(f"fit: expected x (rows, d) and y (rows, p), got {tuple(x.shape)} and {tuple(y.shape)}")
+        if x.requires_grad or y.requires_grad:
+            raise ValueError("fit: the Gaussian process builds no gradients (a training tensor requires grad)")
+        first = self.train_x is None
+        self.train_x = x if first else torch.cat((self.train_x, x))
+        self.train_y = y if first else torch.cat((self.train_y, y))
+
+    # -- covariances and means ----------------------------------------------------------------------------------------------
+    def _hyper(self):
+        """What the cached factor depends on besides the data, as host values."""
+        seen = tuple(part.hyperparameters() if isinstance(part, (SquaredExponential, Const)) else None for part in (self.kernel, self.mean))
+        return (self._kernel_route, *seen, _host_value(self, "noise_var"))
+
+    def _cross(self, x):
+        """kernel(x, train), (m, n), in memory of its own (the solve overwrites it)."""
+        if self._kernel_route == "se":
+            return self.kernel(x, self.train_x)
+        out = self.kernel(x, self.train_x)
+        return out.clone() if out.is_contiguous() else out.contiguous()
+
+    def _prior(self, x, mirror):
+        """kernel(x, x), (m, m), in memory of its own; with mirror=False only its lower triangle is promised."""
+        if self._kernel_route == "se":
+            std, lengthscale = self.kernel.hyperparameters()
+            return ops.se_kernel(x, x, std, lengthscale, mirror=mirror)
+        return self.kernel(x, x).clone(memory_format=torch.contiguous_format)
+
+    def _train_rows(self, lo, hi, out, noise):
+        """Rows lo .. hi of kernel(train, train) + noise I into out (hi - lo, hi): columns 0 .. their own."""
+        x = self.train_x
+        if self._kernel_route == "se":
+            std, lengthscale = self.kernel.hyperparameters()
+            if lo == 0:
+                ops.se_kernel(x, x, std, lengthscale, noise, out=out, mirror=False)
+            else:
+                ops.se_kernel(x[lo:hi], x, std, lengthscale, noise, out=out, diag_offset=lo)
+        else:
+            out.copy_(self.kernel(x, x))
+            ops.add_diag_(out, noise)
+
+    # -- the factor -----------------------------------------------------------------------------------------------------------
+    def _grow(self, n, p, keep):
+        """Buffers for n rows: the capacity is a multiple of 64 and doubles when full; `keep` rows of the old factor and of
+        z are carried over by plain tensor copies."""
+        cap = 0 if self._factor is None else self._factor.shape[0]
+        if n <= cap and self._zt.shape[0] == p:
+            return
+        new_cap = max(cap, _TILE)
+        while new_cap < n:
+            new_cap *= 2
+        dev = self.train_x.device
+        factor = torch.zeros((new_cap, new_cap), device=dev, dtype=torch.float32)
+        zt = torch.zeros((p, new_cap), device=dev, dtype=torch.float32)
+        if keep:
+            factor[:keep, :keep].copy_(self._factor[:keep, :keep])
+            zt[:, :keep].copy_(self._zt[:, :keep])
+        self._factor, self._zt = factor, zt
+        self._alpha_t = torch.zeros((p, new_cap), device=dev, dtype=torch.float32)
+
+    def _ensure_factor(self):
+        n, p = self.train_y.shape
+        key = self._hyper()
+        same = (self._factor is not None and key == self._factor_key and self._factor.device == self.train_x.device
+                and self._zt.shape[0] == p)
+        if same and self._n_factored == n:
+            return
+        done = self._n_factored if (same and self.incremental and self._kernel_route == "se" and 0 < self._n_factored < n) else 0
+        self._factor_route = "append" if done else "full"
+        noise = key[-1]
+        try:
+            self._grow(n, p, done)
+            lower = self._factor[:n, :n]
+            self._train_rows(done, n, self._factor[done:n, :n], noise)
+            info = ops.cholesky_(lower, n_done=done)
+            resid = self.train_y[done:] - self.mean(self.train_x[done:])
+            self._zt[:, done:n].copy_(resid.t())
+            ops.trsm_right_(lower, self._zt[:, :n], col_done=done)
+            self._alpha_t[:, :n].copy_(self._zt[:, :n])
+            ops.trsm_right_(lower, self._alpha_t[:, :n], transposed=True)
+            failed = int(info)  # the one host synchronisation of a factorisation
+        except Exception:
+            self.reset_cache()
+            raise
+        if failed:
+            self.reset_cache()
+            raise torch.linalg.LinAlgError(
+                f"GaussianProcess: the training covariance is not positive definite in fp32: the pivot at index {failed - 1} of {n} "
+                f"is not > 0 (noise_var = {noise:g}). Pass a positive noise_var (or a larger one), or remove duplicate points.")
+        self._n_factored, self._factor_key = n, key
+
+    # -- the reference's interface ----------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def predict(self, x):
+        """The predicted mean (m, p) and covariance (m, m) at x (m, d): the posterior after `fit`, else the prior
+        mean(x), kernel(x, x). fp32 on the GPU, no gradient. With an unchanged factor nothing synchronises with the host (the
+        call can be captured into a graph); the `predict` after a `fit` reads one int32 back."""
+        if x.requires_grad:
+            raise ValueError("predict: the Gaussian process builds no gradients (x requires grad)")
+        if self.train_x is None:
+            return self.mean(x), self._prior(x, mirror=True)
+        self._ensure_factor()
+        n, p = self.train_y.shape
+        lower = self._factor[:n, :n]
+        w = self._cross(x)
+        mu = self.mean(x).expand(x.shape[0], p).clone(memory_format=torch.contiguous_format)
+        ops.gemm_nt_(mu, w, self._alpha_t[:, :n], add=True)
+        ops.trsm_right_(lower, w)
+        sig = self._prior(x, mirror=False)
+        ops.gemm_nt_(sig, w, w, lower=True, mirror=True)
+        return mu, sig
+
+    @torch.no_grad()
+    def sample(self, x, n_samples, generator=None):
+        """n_samples draws (n_samples, m) of the process at x (m, d), from the posterior after `fit`, else from the prior:
+        mu^T + Z L_s^T with Z = torch.randn((n_samples, m), generator=generator) on the GPU, drawn once, and L_s the Cholesky
+        factor of sig + j mean(diag(kernel(x, x))) I, j the first of 0, 1e-6, 1e-5, ..., 1e-2 that factors
+        (torch.linalg.LinAlgError if none does). The jitter is scaled by the PRIOR diagonal: the rounding noise of sig is
+        eps cond times the prior scale, however small the posterior variance. Needs p = 1, as the reference's squeeze.
+        `_sample_jitter` holds the j taken and `_sample_factor` L_s (strict upper triangle zero)."""
+        mu, sig = self.predict(x)
+        if mu.shape[1] != 1:
+            raise ValueError(f"sample: needs one output column, the mean has shape {tuple(mu.shape)}")
+        m = x.shape[0]
+        if self._kernel_route == "se":
+            scale = self.kernel.hyperparameters()[0] ** 2
+        else:
+            scale = float(self.kernel(x, x).diagonal().mean())
+        factor = None
+        for jitter in JITTER_LADDER:
+            factor = sig.clone()
+            if jitter:
+                ops.add_diag_(factor, jitter * scale)
+            if int(ops.cholesky_(factor)) == 0:
+                break
+        else:
+            raise torch.linalg.LinAlgError(
+                f"GaussianProcess.sample: the predicted covariance ({m} points) does not factor in fp32 even with a jitter of "
+                f"{JITTER_LADDER[-1]:g} of the prior variance; pass a positive noise_var or fewer, better separated points")
+        self._sample_jitter, self._sample_factor = jitter, factor.tril_()
+        z = torch.randn((n_samples, m), device=x.device, dtype=torch.float32, generator=generator)
+        out = mu.t().expand(n_samples, m).clone(memory_format=torch.contiguous_format)
+        return ops.gemm_nt_(out, z, self._sample_factor, add=True)

@@ -247,3 +247,13 @@ from pytorch_generative_amd.ops.vae import (  # noqa: F401
     col_subsample2,
     col_zero_insert2,
 )
+from pytorch_generative_amd.ops.gp import (  # noqa: F401
+    GP_PLAN_INTS,
+    gp_plan_status,
+    gp_plan,
+    se_kernel,
+    add_diag_,
+    gemm_nt_,
+    cholesky_,
+    trsm_right_,
+)

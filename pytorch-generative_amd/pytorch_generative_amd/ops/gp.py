@@ -1,0 +1,164 @@
+"""ops.gp — the dense symmetric solve of a Gaussian process on the kernels of csrc/gp.hip: squared-exponential covariance, a
+blocked fp32 Cholesky factorisation that can be appended to, the triangular solves X L^T = B and X L = B, and the strided GEMM
+update C = C -/+ A B^T. Every operand is a 2-D fp32 tensor whose rows are contiguous and whose row stride may be larger than
+its row (a view of a larger buffer is an operand as it lies). Functions ending in an underscore work in place. No gradients.
+
+Part of the operator layer (pytorch_generative_amd.ops): HIP kernels called through the C-ABI with tensor.data_ptr() and the
+current stream. No CPU / ATen fallback: a missing library, a CPU tensor or a shape outside ops.gp_plan raises."""
+
+import ctypes
+
+import torch
+
+from pytorch_generative_amd import _lib
+from pytorch_generative_amd.ops._common import _chk, _stream
+
+GP_PLAN_INTS = 16  # PG_GP_PLAN_INTS
+GP_LOWER, GP_MIRROR, GP_DIAG, GP_PLUS, GP_B_TRANS, GP_SE_DIRECT, GP_SE_MFMA = 1, 2, 4, 8, 16, 32, 64  # PG_GP_*
+_PLAN_FIELDS = ("tile", "k_chunk", "panels", "row_tiles", "se_route", "se_direct_max_d", "se_symmetric_tiles", "se_cross_tiles",
+                "potrf_launches", "trsm_launches", "trailing_workgroups", "max_n", "max_d", "max_p", "p_row_tiles",
+                "se_direct_forced_max_d")
+_SE_ROUTES = {None: 0, "direct": GP_SE_DIRECT, "mfma": GP_SE_MFMA}
+
+
+def gp_plan_status(n, m, d, p):
+    """(status, plan): the C-ABI status of pg_gp_plan (0, PG_ESHAPE = -2, PG_EINVAL = -1) and the plan dict (None on error)."""
+    out = (ctypes.c_longlong * GP_PLAN_INTS)()
+    rc = _lib.load().pg_gp_plan(int(n), int(m), int(d), int(p), out, GP_PLAN_INTS)
+    return rc, (None if rc else dict(zip(_PLAN_FIELDS, out)))
+
+
+def gp_plan(n, m, d, p):
+    """The planner's answer (pg_gp_plan, host only) for n training rows, m query rows, d input columns and p columns of y: None
+    for a problem it refuses (n, m in 1 .. 16384, d, p in 1 .. 4096), else a dict with the panel width, the k chunk, the panels
+    of n, the row tiles of m, the covariance route (0: exact differences, 1: the MFMA) and the largest d of route 0, the tiles
+    of the symmetric and the cross covariance, the launches of a full factorisation and of a forward solve, the workgroups of
+    the first trailing update, the domain's edges, the row tiles of p and the largest d route 0 takes when forced."""
+    return gp_plan_status(n, m, d, p)[1]
+
+
+def _mat(t, name):
+    """A 2-D fp32 matrix on the current GPU with contiguous rows; returns (tensor, row stride). Never copies."""
+    if t.dim() != 2:
+        raise ValueError(f"{name}: expected a 2-D matrix, got shape {tuple(t.shape)}")
+    if t.requires_grad:
+        raise ValueError(f"{name}: the Gaussian-process operators build no gradients (requires_grad is set)")
+    if t.numel() == 0:
+        raise ValueError(f"{name}: empty matrix of shape {tuple(t.shape)}")
+    _chk(t[:1, :1], name)  # the device and dtype checks of every family, on a view that is never copied
+    if t.shape[1] > 1 and t.stride(1) != 1:
+        raise ValueError(f"{name}: rows must be contiguous (strides {t.stride()})")
+    ld = t.stride(0) if t.shape[0] > 1 else max(t.shape[1], t.stride(0))
+    if ld < t.shape[1]:
+        raise ValueError(f"{name}: row stride {ld} below the row length {t.shape[1]}")
+    return t, ld
+
+
+def se_kernel(a, b, std, lengthscale, noise_var=0.0, *, out=None, mirror=True, diag_offset=None, route=None):
+    """The squared-exponential covariance K[i, j] = std^2 exp(-|a_i - b_j|^2 / (2 lengthscale^2)) of a (n, d) and b (m, d),
+    (n, m), into `out` if given (any row stride).
+
+    `b is a`: the symmetric form. Only the tiles on or below the diagonal are computed, the diagonal is exactly
+    std^2 + noise_var, and with mirror=True (default) the lower triangle is copied into the upper one, so the result is exactly
+    symmetric; with mirror=False the strict upper triangle of `out` above the diagonal tiles is left as it was.
+    diag_offset = o (cross form): only the elements j <= i + o are written and the elements j == i + o are exactly
+    std^2 + noise_var — rows of a larger symmetric matrix. Otherwise every element is written and noise_var is not used.
+    route: None (ops.gp_plan decides: exact differences for d <= 16, |a|^2 + |b|^2 - 2 a.b on the MFMA above), "direct"
+    (d <= 64) or "mfma". One launch, capturable, bit-identical from run to run; an element depends on its two rows alone."""
+    a, lda = _mat(a, "se_kernel.a")
+    sym = b is a
+    b, ldb = (a, lda) if sym else _mat(b, "se_kernel.b")
+    n, d = a.shape
+    m = b.shape[0]
+    if b.shape[1] != d:
+        raise ValueError(f"se_kernel: a has {d} columns, b {b.shape[1]}")
+    if route not in _SE_ROUTES:
+        raise ValueError(f"se_kernel: route {route!r} is none of None, 'direct', 'mfma'")
+    rc, _ = gp_plan_status(n, m, d, 1)
+    _lib.check(rc, "se_kernel")
+    if out is None:
+        out = torch.empty((n, m), device=a.device, dtype=torch.float32)
+    out, ldk = _mat(out, "se_kernel.out")
+    if tuple(out.shape) != (n, m):
+        raise ValueError(f"se_kernel: out of shape {tuple(out.shape)}, expected {(n, m)}")
+    flags = _SE_ROUTES[route]
+    off = 0
+    if sym:
+        if diag_offset is not None:
+            raise ValueError("se_kernel: diag_offset belongs to the cross form")
+        flags |= GP_LOWER | GP_DIAG | (GP_MIRROR if mirror else 0)
+    elif diag_offset is not None:
+        flags |= GP_LOWER | GP_DIAG
+        off = int(diag_offset)
+    _lib.check(_lib.load().pg_gp_se_kernel(a.data_ptr(), lda, n, b.data_ptr(), ldb, m, d, float(std), float(lengthscale), float(noise_var),
+                                           out.data_ptr(), ldk, off, flags, _stream()), "pg_gp_se_kernel")
+    return out
+
+
+def add_diag_(a, value):
+    """a[i, i] += value for the square matrix a, in place; returns a."""
+    a, ld = _mat(a, "add_diag_.a")
+    if a.shape[0] != a.shape[1]:
+        raise ValueError(f"add_diag_: expected a square matrix, got {tuple(a.shape)}")
+    _lib.check(_lib.load().pg_gp_add_diag(a.data_ptr(), ld, a.shape[0], float(value), _stream()), "pg_gp_add_diag")
+    return a
+
+
+def gemm_nt_(c, a, b, *, add=False, lower=False, mirror=False, b_transposed=False, diag_offset=0):
+    """c (R, C) -= a b^T in place (add=True: +=) for a (R, K) and b (C, K); b_transposed: b is (K, C), the a b form. Returns c.
+
+    The accumulators are seeded with c and the product is subtracted inside the fp32-MFMA chain: each element is
+    fmaf(-a_k, b_k, .) in ascending k starting from c's value, so an update applied in pieces along k has the bits of the
+    update applied at once. lower: only the elements col <= row + diag_offset are read and written; mirror (square, lower,
+    diag_offset 0): c[col, row] = c[row, col] as well. One launch, capturable, bit-identical from run to run."""
+    c, ldc = _mat(c, "gemm_nt_.c")
+    a, lda = _mat(a, "gemm_nt_.a")
+    b, ldb = _mat(b, "gemm_nt_.b")
+    r, cc = c.shape
+    k = a.shape[1]
+    want_b = (k, cc) if b_transposed else (cc, k)
+    if a.shape[0] != r or tuple(b.shape) != want_b:
+        raise ValueError(f"gemm_nt_: c {tuple(c.shape)}, a {tuple(a.shape)}, b {tuple(b.shape)} do not fit (b should be {want_b})")
+    flags = (GP_PLUS if add else 0) | (GP_LOWER if lower else 0) | (GP_MIRROR if mirror else 0) | (GP_B_TRANS if b_transposed else 0)
+    _lib.check(_lib.load().pg_gp_gemm_nt(a.data_ptr(), lda, b.data_ptr(), ldb, c.data_ptr(), ldc, r, cc, k, int(diag_offset), flags,
+                                         _stream()), "pg_gp_gemm_nt")
+    return c
+
+
+def _info(info, device):
+    if info is None:
+        return torch.zeros(1, dtype=torch.int32, device=device)
+    if not info.is_cuda or info.dtype != torch.int32 or info.numel() != 1:
+        raise ValueError("cholesky_: info must be one int32 on the GPU")
+    return info
+
+
+def cholesky_(a, n_done=0, info=None):
+    """The lower Cholesky factor of the symmetric positive definite a (n, n), in place in its lower triangle; the strict upper
+    triangle is neither read nor written. Returns info, one int32 on the GPU (a given `info` is used as it is and must be 0):
+    0, or index + 1 of the first pivot that was not > 0 — the launches return normally then and the factor holds NaNs. Reading
+    info is the caller's host synchronisation.
+
+    n_done > 0: rows < n_done already hold the factor of the leading (n_done, n_done) block and rows n_done .. n hold a's
+    values (columns 0 .. their own); only those rows are completed, and the result has the bits of the full factorisation.
+    Blocked, right-looking, at most three launches per panel of 64 columns (ops.gp_plan), capturable."""
+    a, ld = _mat(a, "cholesky_.a")
+    if a.shape[0] != a.shape[1]:
+        raise ValueError(f"cholesky_: expected a square matrix, got {tuple(a.shape)}")
+    info = _info(info, a.device)
+    _lib.check(_lib.load().pg_gp_potrf(a.data_ptr(), ld, a.shape[0], int(n_done), info.data_ptr(), _stream()), "pg_gp_potrf")
+    return info
+
+
+def trsm_right_(l, x, col_done=0, transposed=False):
+    """Solves x l^T = b (transposed=True: x l = b) in place for the lower-triangular l (n, n) — its strict upper triangle is
+    not read — and x (rows, n) holding b; returns x. col_done > 0 (forward form only): columns < col_done of x are final and
+    only the others, which hold b, are completed, with the bits of the full solve. Right-looking, two launches per panel of 64
+    columns, capturable."""
+    l, ld = _mat(l, "trsm_right_.l")
+    x, ldx = _mat(x, "trsm_right_.x")
+    if l.shape[0] != l.shape[1] or x.shape[1] != l.shape[0]:
+        raise ValueError(f"trsm_right_: l {tuple(l.shape)} and x {tuple(x.shape)} do not fit")
+    _lib.check(_lib.load().pg_gp_trsm_right(l.data_ptr(), ld, l.shape[0], x.data_ptr(), ldx, x.shape[0], int(col_done),
+                                            int(bool(transposed)), _stream()), "pg_gp_trsm_right")
+    return x
