@@ -24,11 +24,12 @@
 // (blockIdx % 8 selects the XCD), so an image's K/V enter that XCD's L2 once. Forward is two-pass
 // (row max with the score MFMA only, then exp / accumulate against the final max: no rescaling).
 #include "attention_args.h"
+#include "mfma_tile.h"
 #include <stdlib.h>
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using pg_tile::f32x4;
 
 #define MFMA4(A, B, C) __builtin_amdgcn_mfma_f32_16x16x4f32((A), (B), (C), 0, 0, 0)
 

@@ -51,16 +51,17 @@
 #include <type_traits>
 
 #include "attention_args.h"
+#include "mfma_tile.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using pg_tile::f32x4;
+using pg_tile::mfma16;
 constexpr float NEG_BIG = -1.0e30f;
 constexpr float POS_BIG = 1.0e30f;
 constexpr float PSUM_TH = 1024.0f;  // a 4-key probability sum above this (some p > 2^8) triggers a rescale
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-#define MFMA16(A, B, C) __builtin_amdgcn_mfma_f32_16x16x4f32((A), (B), (C), 0, 0, 0)
 #define MFMA16B(A, B, C) __builtin_amdgcn_mfma_f32_16x16x32_bf16((A), (B), (C), 0, 0, 0)
 #define MFMA4(A, B, C) __builtin_amdgcn_mfma_f32_4x4x1f32((A), (B), (C), 0, 0, 0)
 
@@ -644,8 +645,8 @@ __global__ void __launch_bounds__(512) attn_dkv_m44_kernel(const PgAttnArgs a) {
 #pragma unroll
       for (int t = 0; t <= TMAX; ++t) {
         if (BF16S) s[t] = MFMA16B(f.qa8, bk[t], f.cl);
-        else s[t] = MFMA16(f.qa, kf[t], f.cl);
-        dp[t] = MFMA16(f.ga, vf[t], f.cd);
+        else s[t] = mfma16(f.qa, kf[t], f.cl);
+        dp[t] = mfma16(f.ga, vf[t], f.cd);
       }
 #pragma unroll
       for (int t = 0; t <= TMAX; ++t) {
@@ -904,7 +905,7 @@ __global__ void __launch_bounds__(512, 4) attn_bwd_m44_kernel(const PgAttnArgs a
           const int t = t0 + u;
           if (t <= TMAX) {
             s[u] = MFMA16B(f.qa8, bk[t], zero4);
-            dp[u] = MFMA16(f.ga, vf[t], f.cd);
+            dp[u] = mfma16(f.ga, vf[t], f.cd);
           }
         }
 #pragma unroll

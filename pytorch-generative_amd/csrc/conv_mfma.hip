@@ -26,10 +26,11 @@
 //    float4 loads; every lane reads its own dword (conflict free).
 #include "common.h"
 #include "conv_b3.h"
+#include "mfma_tile.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using pg_tile::f32x4;
 
 constexpr int MF_THREADS = 256;
 constexpr int MF_CO_CHUNK = 64;

@@ -19,12 +19,13 @@
 // so both fragment reads are bank-conflict free. Each workgroup walks many pixel tiles and
 // flushes once with fp32 atomics (caller zeroes dw/db once per step).
 #include "conv_wgrad_route.h"
+#include "mfma_tile.h"
 #include <stdlib.h>
 #include <string.h>
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using pg_tile::f32x4;
 
 constexpr int WG_THREADS = 256;
 constexpr int CO_CHUNK = 64;  // dy channels staged per block

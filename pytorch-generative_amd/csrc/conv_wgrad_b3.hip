@@ -25,11 +25,12 @@
 // (producer / consumer waves, two half-workgroups in opposite phases): profiles/README.md, round 2,
 // items 11-13, sources under tools/exp/rejected/.
 #include "conv_wgrad_route.h"
+#include "mfma_tile.h"
 #include <stdlib.h>
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using pg_tile::f32x4;
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 

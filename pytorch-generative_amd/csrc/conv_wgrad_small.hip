@@ -16,11 +16,12 @@
 // 4 MFMAs. Persistent workgroups over (image, row tile), one row of partial sums per workgroup, then
 // conv_wgrad.hip's deterministic reduction.
 #include "conv_wgrad_route.h"
+#include "mfma_tile.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-#define MFMA16(A, B, C) __builtin_amdgcn_mfma_f32_16x16x4f32((A), (B), (C), 0, 0, 0)
+using pg_tile::f32x4;
+using pg_tile::mfma16;
 
 constexpr int SW_THREADS = 256;
 constexpr int SW_CO = 64;
@@ -88,7 +89,7 @@ __global__ void __launch_bounds__(SW_THREADS) conv_wgrad_small_kernel(const SwAr
 #pragma unroll
       for (int n = 0; n < 4; ++n) {
         const float bv = boff[n] >= 0 ? xt[boff[n] + xo] : (boff[n] == -2 ? 1.f : 0.f);
-        acc[n] = MFMA16(av, bv, acc[n]);
+        acc[n] = mfma16(av, bv, acc[n]);
       }
     }
   }

@@ -9,52 +9,34 @@
 // Every activation operand takes a row stride in floats, so a coupling block reads one half of an (N, F) tensor and writes the
 // other half of another with no copy.
 //
-// Two tile variants, 256 threads = 4 waves in a 2 x 2 arrangement each:
-//   small  64 x  64, k chunks of 32: a wave owns 32 x 32 as 2 x 2 accumulators of v_mfma_f32_16x16x4_f32;
-//   large 128 x 128, k chunks of 16: a wave owns 64 x 64 as 2 x 2 accumulators of v_mfma_f32_32x32x2_f32.
-// The next k chunk is loaded into registers while the current one multiplies out of LDS; the LDS row strides (34 and 17 floats)
-// make the MFMA operand reads of both instructions conflict free (32 banks per half-wave; DlTile). Only those reads are: in the
-// small tile the staging stores of a row-contiguous operand (the data gradient's weight, both operands of the weight gradient)
-// and the bias-sum row reads are two-way; in the large tile a k-contiguous store shares one bank of 32. An fp32 MFMA is an fmaf chain per output in k order: fp32-exact and
-// deterministic. dl_plan is the one function that decides the domain, the variant and the k-split: the large tile where it
-// alone fills three quarters of the 256 CUs, else the small one, split along k where even that leaves half the chip idle.
+// The tile, in its small (64 x 64) and large (128 x 128) variants, its LDS strides and the fmaf-chain order of every sum are
+// mfma_tile.h's; this file adds the operand addressing, the bias row sum and the epilogue. Of the LDS accesses that are not
+// conflict free there, the row-contiguous staging stores are the data gradient's weight and both operands of the weight
+// gradient, the row walk is the bias sum. dl_plan is the one function that decides the domain, the variant and the k-split:
+// the large tile where it alone fills three quarters of the 256 CUs, else the small one, split along k where even that leaves
+// half the chip idle.
 // A k-split writes raw partial sums to a caller-provided workspace; dl_reduce_kernel adds the slices in slice order and applies
 // the epilogue. Each output element is owned by one lane; no float atomics; every order depends on the shape alone, so results
 // are bit-identical from run to run. No host synchronisation, no allocation: capturable. Ragged edges are zero-filled on load
 // and guarded on store.
 #include <algorithm>
-#include <type_traits>
 
 #include "common.h"
+#include "mfma_tile.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 enum { DL_FWD = PG_DENSE_FWD, DL_DGRAD = PG_DENSE_DGRAD, DL_WGRAD = PG_DENSE_WGRAD };
-enum { DL_SMALL = 0, DL_LARGE = 1 };
+enum { DL_SMALL = pg_tile::SMALL, DL_LARGE = pg_tile::LARGE };
+template <int V>
+using DlTile = pg_tile::Tile<V>;
 
-constexpr int DL_THREADS = 256;
+constexpr int DL_THREADS = pg_tile::THREADS;
 constexpr int DL_CUS = 256;           // workgroups that fill the chip
 constexpr int DL_LARGE_MIN = 192;     // large tiles from which the large variant is taken
 constexpr int DL_SPLIT_BELOW = 128;   // small tiles below which the k range is split
 constexpr int DL_MAX_SLICES = 64;
 constexpr int DL_MAX_DIM = 1 << 30;   // k offsets stay inside an int with a chunk to spare
-
-template <int V>
-struct DlTile;
-template <>
-struct DlTile<DL_SMALL> {
-  // LDS banks a 4-byte access as (address / 4) % 32 within a half-wave. The 16x16x4 operand read of a half-wave is 16 rows x 2 k:
-  // (34 row + k) % 32 = (2 row + k) % 32, 32 distinct banks. (A stride of 36 = KC + 4 gives 4 row + k: 16 banks, two-way.)
-  static constexpr int BM = 64, BN = 64, KC = 32, LD = 34;
-};
-template <>
-struct DlTile<DL_LARGE> {
-  // 32x32x2: a half-wave reads 32 rows at one k: 17 row % 32, 32 distinct banks; so are stores along rows
-  static constexpr int BM = 128, BN = 128, KC = 16, LD = 17;
-};
 
 struct DlArgs {
   const float* a;     // A(r, k) = a[r * a_rs + k * a_ks]
@@ -81,109 +63,39 @@ __device__ __forceinline__ void dl_finish(const DlArgs& p, int r, int c, float v
   *dst = p.accumulate ? *dst + v : v;
 }
 
-// Element e of a thread's share of a ROWS x KC chunk: k-contiguous operands walk k fastest, row-contiguous ones rows fastest.
-template <int ROWS, int KC, bool KCONTIG>
-__device__ __forceinline__ void dl_coord(int e, int& r, int& k) {
-  if (KCONTIG) {
-    r = e / KC;
-    k = e % KC;
-  } else {
-    r = e % ROWS;
-    k = e / ROWS;
-  }
-}
-
 template <int V, bool AK, bool BK>
 __global__ void __launch_bounds__(DL_THREADS) dl_gemm_kernel(const DlArgs p) {
   using T = DlTile<V>;
   constexpr int BM = T::BM, BN = T::BN, KC = T::KC, LD = T::LD;
-  constexpr int A_PER = BM * KC / DL_THREADS, B_PER = BN * KC / DL_THREADS;
-  constexpr int MT = V == DL_LARGE ? 32 : 16;  // edge of one MFMA tile; a wave owns 2 x 2 of them
-  constexpr int KS = V == DL_LARGE ? 2 : 4;    // k per MFMA
   __shared__ float s_a[BM * LD];
   __shared__ float s_b[BN * LD];
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int lr = lane & (MT - 1), lk = lane / MT;
-  const int wr = wave >> 1, wc = wave & 1;
+  const pg_tile::Lanes<V> ln;
+  const int tid = ln.tid;
   const int r0 = (blockIdx.x / p.col_tiles) * BM, c0 = (blockIdx.x % p.col_tiles) * BN;
   const int kbeg = blockIdx.y * p.kper;
   const int kend = min(p.K, kbeg + p.kper);
 
-  float ra[A_PER], rb[B_PER];
-  auto load = [&](int k0) {
-#pragma unroll
-    for (int j = 0; j < A_PER; ++j) {
-      int r, k;
-      dl_coord<BM, KC, AK>(tid + j * DL_THREADS, r, k);
-      const int gr = r0 + r, gk = k0 + k;
-      ra[j] = (gr < p.R && gk < kend) ? p.a[(size_t)gr * p.a_rs + (size_t)gk * p.a_ks] : 0.f;
-    }
-#pragma unroll
-    for (int j = 0; j < B_PER; ++j) {
-      int c, k;
-      dl_coord<BN, KC, BK>(tid + j * DL_THREADS, c, k);
-      const int gc = c0 + c, gk = k0 + k;
-      rb[j] = (gc < p.C && gk < kend) ? p.b[(size_t)gc * p.b_rs + (size_t)gk * p.b_ks] : 0.f;
-    }
-  };
-  auto store = [&]() {
-#pragma unroll
-    for (int j = 0; j < A_PER; ++j) {
-      int r, k;
-      dl_coord<BM, KC, AK>(tid + j * DL_THREADS, r, k);
-      s_a[r * LD + k] = ra[j];
-    }
-#pragma unroll
-    for (int j = 0; j < B_PER; ++j) {
-      int c, k;
-      dl_coord<BN, KC, BK>(tid + j * DL_THREADS, c, k);
-      s_b[c * LD + k] = rb[j];
-    }
-  };
-
-  typedef typename std::conditional<V == DL_LARGE, f32x16, f32x4>::type acc_t;
-  constexpr int NACC = V == DL_LARGE ? 16 : 4;
-  acc_t acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int q = 0; q < NACC; ++q) acc[i][j][q] = 0.f;
-
+  pg_tile::Regs<V> ra, rb;
+  pg_tile::Acc<V> acc;
+  pg_tile::zero<V>(acc);
   float dbsum = 0.f;  // weight gradient: thread tid < BM sums row tid of A in k order
   const bool do_db = p.db != nullptr && c0 == 0;
-  const int nch = (kend - kbeg + KC - 1) / KC;
-  load(kbeg);
-  for (int ch = 0; ch < nch; ++ch) {
-    store();
-    __syncthreads();
-    if (ch + 1 < nch) load(kbeg + (ch + 1) * KC);  // in flight while this chunk multiplies
-    const float* ap = s_a + (wr * 2 * MT + lr) * LD + lk;
-    const float* bp = s_b + (wc * 2 * MT + lr) * LD + lk;
-#pragma unroll
-    for (int kk = 0; kk < KC; kk += KS) {
-      const float a0 = ap[kk], a1 = ap[MT * LD + kk];
-      const float b0 = bp[kk], b1 = bp[MT * LD + kk];
-      if constexpr (V == DL_LARGE) {
-        acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
-        acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
-        acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
-        acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
-      } else {
-        acc[0][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b0, acc[0][0], 0, 0, 0);
-        acc[0][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b1, acc[0][1], 0, 0, 0);
-        acc[1][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b0, acc[1][0], 0, 0, 0);
-        acc[1][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b1, acc[1][1], 0, 0, 0);
-      }
-    }
+  auto load = [&](int ch) {
+    pg_tile::load_operand<V, AK>(ra, p.a, p.a_rs, p.a_ks, r0, p.R, kbeg + ch * KC, kend, tid);
+    pg_tile::load_operand<V, BK>(rb, p.b, p.b_rs, p.b_ks, c0, p.C, kbeg + ch * KC, kend, tid);
+  };
+  auto store = [&]() {
+    pg_tile::store_operand<V, AK>(s_a, ra, tid);
+    pg_tile::store_operand<V, BK>(s_b, rb, tid);
+  };
+  auto bias_sum = [&](int) {
     if (do_db && tid < BM) {
       const float* row = s_a + tid * LD;
 #pragma unroll
       for (int k = 0; k < KC; ++k) dbsum += row[k];  // zero beyond the slice
     }
-    __syncthreads();
-  }
+  };
+  PG_TILE_PIPELINE(V, false, 0, (kend - kbeg + KC - 1) / KC, load, store, acc, s_a, s_b, ln, bias_sum);  // dl_plan: every slice holds a chunk
   if (do_db && tid < BM && r0 + tid < p.R) {
     if (p.part)
       p.part[(size_t)p.slices * p.R * p.C + (size_t)blockIdx.y * p.R + r0 + tid] = dbsum;
@@ -191,24 +103,13 @@ __global__ void __launch_bounds__(DL_THREADS) dl_gemm_kernel(const DlArgs p) {
       p.db[r0 + tid] += p.scale * dbsum;
   }
 
-  // D layouts: 16x16: column = lane & 15, row = 4 (lane >> 4) + reg; 32x32: column = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int gc = c0 + (wc * 2 + j) * MT + lr;
-      if (gc >= p.C) continue;
-#pragma unroll
-      for (int q = 0; q < NACC; ++q) {
-        const int row = V == DL_LARGE ? (q & 3) + 8 * (q >> 2) + 4 * lk : 4 * lk + q;
-        const int gr = r0 + (wr * 2 + i) * MT + row;
-        if (gr >= p.R) continue;
-        if (p.part)
-          p.part[((size_t)blockIdx.y * p.R + gr) * p.C + gc] = acc[i][j][q];
-        else
-          dl_finish(p, gr, gc, acc[i][j][q]);
-      }
-    }
+  PG_TILE_FOR_EACH_OUTPUT(V, ln, li, lj) {
+    const int gr = r0 + li, gc = c0 + lj;
+    if (gc >= p.C || gr >= p.R) continue;
+    if (p.part)
+      p.part[((size_t)blockIdx.y * p.R + gr) * p.C + gc] = PG_TILE_OUTPUT(acc);
+    else
+      dl_finish(p, gr, gc, PG_TILE_OUTPUT(acc));
   }
 }
 

@@ -33,6 +33,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "mfma_tile.h"
 
 namespace {
 
@@ -49,7 +50,7 @@ constexpr int DN_MAX_SPLITS = 64;    // forward column splits
 constexpr int DN_MAX_NSPLITS = 16;   // backward row ranges
 constexpr int DN_MAX_TILES = 65535;  // gridDim.y / .z
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using pg_tile::f32x4;
 
 enum { DN_BERNOULLI = PG_MIXTURE_BERNOULLI, DN_GAUSSIAN = PG_MIXTURE_GAUSSIAN };
 

@@ -5,9 +5,8 @@
 // len(i) = max(1, i) values (row 0: the dummy weight the reference multiplies by a zero input) followed by zeros up to
 // pad(i) = roundup(len(i), 4) floats; off(i) = sum_{k < i} pad(k), P(D) = off(D). Every row starts 16-byte aligned.
 //
-//   forward  rows n, cols i, k = j: 64 x 64 output tiles, k chunks of 32, v_mfma_f32_16x16x4_f32 (the small tile of
-//            dense_linear.hip: 4 waves 2 x 2, 2 x 2 accumulators each, LDS row stride 34, next chunk in flight while this one
-//            multiplies). Column tile c reads k only up to min(D, 64 c + 64) - 1: nothing above the diagonal is multiplied.
+//   forward  rows n, cols i, k = j, on the small tile of mfma_tile.h (64 x 64, k chunks of 32; geometry, LDS stride and chain
+//            order are stated there). Column tile c reads k only up to min(D, 64 c + 64) - 1: nothing above the diagonal is multiplied.
 //            The weight operand is read with 16-byte loads inside row i's own storage (a chunk of 4 starting at j < i ends
 //            before off(i) + pad(i)) and every element j >= i is replaced by zero by a predicate, so neither the next row's
 //            storage nor row 0's dummy weight is ever read. Heavy column tiles are launched first. The sum over j has a
@@ -15,7 +14,7 @@
 //            order. Where there are fewer than 128 output tiles the slices become workgroups of their own, write raw
 //            partial sums to a workspace and a second launch adds them in the same order: the same bits as without a split,
 //            so a sample's row does not depend on N.
-//   wgrad    rows i, cols j, k = n: 64 x 64 tiles of dW with tile column <= tile row only (a triangular tile index), written
+//   wgrad    rows i, cols j, k = n: the same tile, 64 x 64 tiles of dW with tile column <= tile row only (a triangular tile index), written
 //            straight into the packed layout where j < i < D; pads and row 0 are never written. db from the tiles of tile
 //            column 0. Where the triangle has fewer than 128 tiles the batch is cut into slices whose raw partial sums go to a
 //            workspace and are merged in slice order by a second launch (as dense_linear.hip's k-split).
@@ -27,15 +26,17 @@
 #include <algorithm>
 
 #include "common.h"
+#include "mfma_tile.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int FV_THREADS = 256;
-constexpr int FV_T = 64;             // edge of an output tile
-constexpr int FV_KC = 32;            // k per LDS chunk
-constexpr int FV_LD = 34;            // LDS row stride: (2 row + k) % 32 are 32 distinct banks for a half-wave's operand read
+using pg_tile::f32x4;
+constexpr int FV_V = pg_tile::SMALL;  // forward and weight gradient run on the small tile of mfma_tile.h
+using FvTile = pg_tile::Tile<FV_V>;
+constexpr int FV_THREADS = pg_tile::THREADS;
+constexpr int FV_T = FvTile::BM;     // edge of an output tile
+constexpr int FV_KC = FvTile::KC;    // k per LDS chunk
+constexpr int FV_LD = FvTile::LD;    // LDS row stride
 constexpr int FV_SLICE = 4;          // forward: k chunks of a slice, the unit of its two-level sum and of its k-split
 constexpr int FV_CUS = 256;          // workgroups that fill the chip
 constexpr int FV_SPLIT_BELOW = 128;  // weight-gradient tiles below which the batch is split
@@ -81,20 +82,6 @@ struct FvFwdArgs {
   int base[FV_MAX_D / FV_T + 1];  // base[ct]: the first slice of column tile ct; base[col_tiles] = slices
 };
 
-#define FV_MFMA_CHUNK(acc, s_a, s_b)                                               \
-  {                                                                                \
-    const float* ap = s_a + (wr * 32 + lr) * FV_LD + lk;                           \
-    const float* bp = s_b + (wc * 32 + lr) * FV_LD + lk;                           \
-    _Pragma("unroll") for (int kk = 0; kk < FV_KC; kk += 4) {                      \
-      const float a0 = ap[kk], a1 = ap[16 * FV_LD + kk];                           \
-      const float b0 = bp[kk], b1 = bp[16 * FV_LD + kk];                           \
-      acc[0][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b0, acc[0][0], 0, 0, 0); \
-      acc[0][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b1, acc[0][1], 0, 0, 0); \
-      acc[1][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b0, acc[1][0], 0, 0, 0); \
-      acc[1][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b1, acc[1][1], 0, 0, 0); \
-    }                                                                              \
-  }
-
 // The sum over j of one output has a two-level order fixed by i alone: an fmaf chain inside every slice of FV_SLICE chunks
 // (each started from zero), the slices added in ascending order, then the bias. SPLIT = false: a workgroup walks all slices of
 // its column tile and adds them in registers. SPLIT = true: one workgroup per (slice, row tile) writes its raw chain to the
@@ -105,9 +92,8 @@ __global__ void __launch_bounds__(FV_THREADS) fv_fwd_kernel(const FvFwdArgs p) {
   constexpr int B_PER = FV_T * FV_KC / 4 / FV_THREADS;  // 2 chunks of 4 weights
   __shared__ float s_a[FV_T * FV_LD];
   __shared__ float s_b[FV_T * FV_LD];
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int lr = lane & 15, lk = lane >> 4;
-  const int wr = wave >> 1, wc = wave & 1;
+  const pg_tile::Lanes<FV_V> ln;
+  const int tid = ln.tid;
   int ct, rt, ch_beg, ch_end, s = 0;
   if (SPLIT) {
     s = (int)(blockIdx.x % p.slices);
@@ -136,7 +122,8 @@ __global__ void __launch_bounds__(FV_THREADS) fv_fwd_kernel(const FvFwdArgs p) {
 
   float ra[A_PER];
   f32x4 rb[B_PER];
-  auto load = [&](int k0) {
+  auto load = [&](int ch) {
+    const int k0 = ch * FV_KC;
 #pragma unroll
     for (int j = 0; j < A_PER; ++j) {
       const int e = tid + j * FV_THREADS;
@@ -170,57 +157,28 @@ __global__ void __launch_bounds__(FV_THREADS) fv_fwd_kernel(const FvFwdArgs p) {
     }
   };
 
-  f32x4 acc[2][2], tot[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) acc[i][j][q] = tot[i][j][q] = 0.f;
-
-  if (ch_beg < nch) load(ch_beg * FV_KC);
-  for (int ch = ch_beg; ch < nch; ++ch) {
-    store();
-    __syncthreads();
-    if (ch + 1 < nch) load((ch + 1) * FV_KC);  // in flight while this chunk multiplies
-    FV_MFMA_CHUNK(acc, s_a, s_b)
+  pg_tile::Acc<FV_V> acc, tot;
+  pg_tile::zero<FV_V>(acc);
+  pg_tile::zero<FV_V>(tot);
+  auto fold = [&](int ch) {
     if (!SPLIT && ((ch + 1) % FV_SLICE == 0 || ch + 1 == nch)) {  // a slice is complete: add it, start the next from zero
 #pragma unroll
       for (int i = 0; i < 2; ++i)
 #pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            tot[i][j][q] += acc[i][j][q];
-            acc[i][j][q] = 0.f;
-          }
+        for (int j = 0; j < 2; ++j) {
+          tot[i][j] += acc[i][j];
+          acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+        }
     }
-    __syncthreads();
-  }
+  };
+  PG_TILE_PIPELINE(FV_V, true, ch_beg, nch, load, store, acc, s_a, s_b, ln, fold);
 
-  // D layout of 16x16x4: column = lane & 15, row = 4 (lane >> 4) + reg
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int lj = (wc * 2 + j) * 16 + lr;
-      const int gc = c0 + lj;
-      if (SPLIT) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int li = (wr * 2 + i) * 16 + 4 * lk + q;
-          p.part[((size_t)s * p.row_tiles + rt) * (FV_T * FV_T) + li * FV_T + lj] = acc[i][j][q];
-        }
-      } else {
-        if (gc >= p.D) continue;
-        const float bias = p.b[gc];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int gr = r0 + (wr * 2 + i) * 16 + 4 * lk + q;
-          if (gr < p.N) p.y[(size_t)gr * p.D + gc] = tot[i][j][q] + bias;
-        }
-      }
-    }
+  PG_TILE_FOR_EACH_OUTPUT(FV_V, ln, li, lj) {
+    const int gr = r0 + li, gc = c0 + lj;
+    if (SPLIT)
+      p.part[((size_t)s * p.row_tiles + rt) * (FV_T * FV_T) + li * FV_T + lj] = PG_TILE_OUTPUT(acc);
+    else if (gc < p.D && gr < p.N)
+      p.y[(size_t)gr * p.D + gc] = PG_TILE_OUTPUT(tot) + p.b[gc];
   }
 }
 
@@ -249,9 +207,8 @@ __global__ void __launch_bounds__(FV_THREADS) fv_wgrad_kernel(const FvWgArgs p) 
   constexpr int PER = FV_T * FV_KC / FV_THREADS;  // 8 floats of each operand per thread and chunk
   __shared__ float s_a[FV_T * FV_LD];  // dy^T: rows i, k = n
   __shared__ float s_b[FV_T * FV_LD];  // x^T: rows j, k = n
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int lr = lane & 15, lk = lane >> 4;
-  const int wr = wave >> 1, wc = wave & 1;
+  const pg_tile::Lanes<FV_V> ln;
+  const int tid = ln.tid;
   int ti, tj;
   fv_tri((int)blockIdx.x, ti, tj);
   const int r0 = ti * FV_T, c0 = tj * FV_T;
@@ -259,11 +216,11 @@ __global__ void __launch_bounds__(FV_THREADS) fv_wgrad_kernel(const FvWgArgs p) 
   const int nend = min(p.N, nbeg + p.nper);
 
   float ra[PER], rb[PER];
-  auto load = [&](int n0) {
+  auto load = [&](int ch) {
 #pragma unroll
     for (int j = 0; j < PER; ++j) {
       const int e = tid + j * FV_THREADS;
-      const int r = e % FV_T, gn = n0 + e / FV_T;
+      const int r = e % FV_T, gn = nbeg + ch * FV_KC + e / FV_T;
       const bool ok = gn < nend;
       ra[j] = (ok && r0 + r < p.D) ? p.dy[(size_t)gn * p.D + r0 + r] : 0.f;
       rb[j] = (ok && c0 + r < p.D) ? p.x[(size_t)gn * p.D + c0 + r] : 0.f;
@@ -278,30 +235,18 @@ __global__ void __launch_bounds__(FV_THREADS) fv_wgrad_kernel(const FvWgArgs p) 
     }
   };
 
-  f32x4 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) acc[i][j][q] = 0.f;
-
+  pg_tile::Acc<FV_V> acc;
+  pg_tile::zero<FV_V>(acc);
   float dbsum = 0.f;  // thread tid < 64 sums row tid of dy^T in n order
   const bool do_db = p.db != nullptr && tj == 0;
-  const int nch = (nend - nbeg + FV_KC - 1) / FV_KC;
-  if (nch > 0) load(nbeg);
-  for (int ch = 0; ch < nch; ++ch) {
-    store();
-    __syncthreads();
-    if (ch + 1 < nch) load(nbeg + (ch + 1) * FV_KC);
-    FV_MFMA_CHUNK(acc, s_a, s_b)
+  auto bias_sum = [&](int) {
     if (do_db && tid < FV_T) {
       const float* row = s_a + tid * FV_LD;
 #pragma unroll
       for (int k = 0; k < FV_KC; ++k) dbsum += row[k];  // zero beyond the slice
     }
-    __syncthreads();
-  }
+  };
+  PG_TILE_PIPELINE(FV_V, true, 0, (nend - nbeg + FV_KC - 1) / FV_KC, load, store, acc, s_a, s_b, ln, bias_sum);
   if (do_db && tid < FV_T) {
     if (p.part)
       p.part[(size_t)p.slices * p.tiles * (FV_T * FV_T) + (size_t)blockIdx.y * (p.col_tiles * FV_T) + r0 + tid] = dbsum;
@@ -310,22 +255,12 @@ __global__ void __launch_bounds__(FV_THREADS) fv_wgrad_kernel(const FvWgArgs p) 
   }
   if (!p.part && !p.dwp) return;
 
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int lj = (wc * 2 + j) * 16 + lr;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int li = (wr * 2 + i) * 16 + 4 * lk + q;
-        if (p.part) {
-          p.part[((size_t)blockIdx.y * p.tiles + blockIdx.x) * (FV_T * FV_T) + li * FV_T + lj] = acc[i][j][q];
-        } else {
-          const int gi = r0 + li, gj = c0 + lj;
-          if (gi < p.D && gj < gi) p.dwp[fv_off(gi) + gj] += acc[i][j][q];
-        }
-      }
-    }
+  PG_TILE_FOR_EACH_OUTPUT(FV_V, ln, li, lj) {
+    const int gi = r0 + li, gj = c0 + lj;
+    if (p.part)
+      p.part[((size_t)blockIdx.y * p.tiles + blockIdx.x) * (FV_T * FV_T) + li * FV_T + lj] = PG_TILE_OUTPUT(acc);
+    else if (gi < p.D && gj < gi)
+      p.dwp[fv_off(gi) + gj] += PG_TILE_OUTPUT(acc);
   }
 }
 

@@ -6,8 +6,9 @@
 // The chain-order property. Element (i, j) of the factor is
 //     l_ij = (a_ij - sum_{k < j} l_ik l_jk) / l_jj          (a square root on the diagonal),
 // and every kernel here forms that sum as ONE chain v = fmaf(-l_ik, l_jk, v) in ascending k that starts from a_ij:
-//   * gp_gemm_kernel seeds its accumulators with the tile of C and multiplies -A: an fp32 MFMA is an fmaf chain per output in k
-//     order, so a trailing update applied panel after panel continues the same chain, whatever the blocking;
+//   * gp_gemm_kernel seeds its accumulators with the tile of C and multiplies -A on the tile of mfma_tile.h, whose sums are one
+//     fmaf chain per output in k order from whatever the accumulator held: a trailing update applied panel after panel
+//     continues the same chain, whatever the blocking;
 //   * gp_potrf_diag_kernel and gp_trsm_diag_kernel continue it on the VALU inside the panel of 64 columns that holds j, then
 //     take one square root or one IEEE division (no explicit inverse of a diagonal block).
 // The chain of an element therefore does not depend on how many rows the matrix had when its row was factored: completing rows
@@ -20,15 +21,16 @@
 #include <algorithm>
 
 #include "common.h"
+#include "mfma_tile.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int GP_T = 64;         // panel width, tile edge
-constexpr int GP_KC = 32;        // k per LDS chunk
-constexpr int GP_LD = 34;        // LDS row stride of an operand chunk: the 16x16x4 operand reads are conflict free (dense_linear.hip)
-constexpr int GP_THREADS = 256;  // 4 waves, 2 x 2, each 32 x 32 as 2 x 2 accumulators of v_mfma_f32_16x16x4_f32
+constexpr int GP_V = pg_tile::SMALL;  // the MFMA products run on the small tile of mfma_tile.h
+using GpTile = pg_tile::Tile<GP_V>;
+constexpr int GP_T = GpTile::BM;   // panel width, tile edge
+constexpr int GP_KC = GpTile::KC;  // k per LDS chunk
+constexpr int GP_LD = GpTile::LD;  // LDS row stride of an operand chunk
+constexpr int GP_THREADS = pg_tile::THREADS;
 constexpr int GP_BLK_LD = 68;    // LDS row stride of the diagonal block in gp_potrf_diag_kernel
 constexpr int GP_TRI_LD = 65;    // LDS row stride of the diagonal block in gp_trsm_diag_kernel and of the rows in gp_se_direct_kernel
 constexpr int GP_MAX_N = 16384;  // n, m: element offsets of an (n, n) matrix fit 32 bits
@@ -39,8 +41,8 @@ constexpr int GP_SE_DIRECT_MAX_D = 64;  // largest d the exact-difference kernel
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // The 64 x 64 x K product of one workgroup: acc += (NEG ? -A : A) B^T with A(r, k) = a[r * a_rs + k] and
-// B(c, k) = b[c * b_rs + k * b_ks], in LDS chunks of 32 k, the next chunk in registers while this one multiplies. Ragged edges
-// are zero-filled. NORMS: thread t < 64 also sums A(r0 + t, k)^2, thread 64 + t B(c0 + t, k)^2, in k order.
+// B(c, k) = b[c * b_rs + k * b_ks], on mfma_tile.h's pipeline (BK: B is k-contiguous). Ragged edges are zero-filled. NORMS:
+// thread t < 64 also sums A(r0 + t, k)^2, thread 64 + t B(c0 + t, k)^2, in k order.
 struct GpMma {
   const float* a;
   const float* b;
@@ -49,62 +51,26 @@ struct GpMma {
 };
 
 template <bool BK, bool NEG, bool NORMS>
-__device__ __forceinline__ void gp_mma_tile(const GpMma& p, int r0, int c0, float* s_a, float* s_b, f32x4 (&acc)[2][2], float& norm) {
-  constexpr int PER = GP_T * GP_KC / GP_THREADS;
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int lr = lane & 15, lk = lane >> 4;
-  const int wr = wave >> 1, wc = wave & 1;
-  float ra[PER], rb[PER];
-  auto load = [&](int k0) {
-#pragma unroll
-    for (int j = 0; j < PER; ++j) {
-      const int e = tid + j * GP_THREADS;
-      const int r = e / GP_KC, k = e % GP_KC;
-      const int gr = r0 + r, gk = k0 + k;
-      const float v = (gr < p.R && gk < p.K) ? p.a[(size_t)gr * p.a_rs + gk] : 0.f;
-      ra[j] = NEG ? -v : v;
-    }
-#pragma unroll
-    for (int j = 0; j < PER; ++j) {
-      const int e = tid + j * GP_THREADS;
-      const int c = BK ? e / GP_KC : e % GP_T, k = BK ? e % GP_KC : e / GP_T;
-      const int gc = c0 + c, gk = k0 + k;
-      rb[j] = (gc < p.C && gk < p.K) ? p.b[(size_t)gc * p.b_rs + (size_t)gk * p.b_ks] : 0.f;
-    }
+__device__ __forceinline__ void gp_mma_tile(const GpMma& p, int r0, int c0, float* s_a, float* s_b, const pg_tile::Lanes<GP_V>& ln,
+                                            pg_tile::Acc<GP_V>& acc, float& norm) {
+  const int tid = ln.tid;
+  pg_tile::Regs<GP_V> ra, rb;
+  auto load = [&](int ch) {
+    pg_tile::load_operand<GP_V, true, NEG>(ra, p.a, p.a_rs, 1, r0, p.R, ch * GP_KC, p.K, tid);
+    pg_tile::load_operand<GP_V, BK>(rb, p.b, p.b_rs, p.b_ks, c0, p.C, ch * GP_KC, p.K, tid);
   };
   auto store = [&]() {
-#pragma unroll
-    for (int j = 0; j < PER; ++j) {
-      const int e = tid + j * GP_THREADS;
-      s_a[(e / GP_KC) * GP_LD + e % GP_KC] = ra[j];
-      const int c = BK ? e / GP_KC : e % GP_T, k = BK ? e % GP_KC : e / GP_T;
-      s_b[c * GP_LD + k] = rb[j];
-    }
+    pg_tile::store_operand<GP_V, true>(s_a, ra, tid);
+    pg_tile::store_operand<GP_V, BK>(s_b, rb, tid);
   };
-  const int nch = (p.K + GP_KC - 1) / GP_KC;
-  load(0);
-  for (int ch = 0; ch < nch; ++ch) {
-    store();
-    __syncthreads();
-    if (ch + 1 < nch) load((ch + 1) * GP_KC);
-    const float* ap = s_a + (wr * 32 + lr) * GP_LD + lk;
-    const float* bp = s_b + (wc * 32 + lr) * GP_LD + lk;
-#pragma unroll
-    for (int kk = 0; kk < GP_KC; kk += 4) {
-      const float a0 = ap[kk], a1 = ap[16 * GP_LD + kk];
-      const float b0 = bp[kk], b1 = bp[16 * GP_LD + kk];
-      acc[0][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b0, acc[0][0], 0, 0, 0);
-      acc[0][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b1, acc[0][1], 0, 0, 0);
-      acc[1][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b0, acc[1][0], 0, 0, 0);
-      acc[1][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b1, acc[1][1], 0, 0, 0);
-    }
+  auto norms = [&](int) {
     if (NORMS && tid < 2 * GP_T) {
       const float* row = (tid < GP_T ? s_a + tid * GP_LD : s_b + (tid - GP_T) * GP_LD);
 #pragma unroll
       for (int k = 0; k < GP_KC; ++k) norm = fmaf(row[k], row[k], norm);  // zero beyond K
     }
-    __syncthreads();
-  }
+  };
+  PG_TILE_PIPELINE(GP_V, false, 0, (p.K + GP_KC - 1) / GP_KC, load, store, acc, s_a, s_b, ln, norms);  // every caller has K >= 1
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -123,33 +89,21 @@ __global__ void __launch_bounds__(GP_THREADS) gp_gemm_kernel(const GpGemmArgs p)
   __shared__ float s_b[GP_T * GP_LD];
   const int r0 = (blockIdx.x / p.col_tiles) * GP_T, c0 = (blockIdx.x % p.col_tiles) * GP_T;
   if (p.lower && c0 > r0 + (GP_T - 1) + p.diag_off) return;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int lr = lane & 15, lk = lane >> 4, wr = wave >> 1, wc = wave & 1;
-  f32x4 acc[2][2];
-  // D layout of 16x16: column = lane & 15, row = 4 (lane >> 4) + reg
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int gr = r0 + (wr * 2 + i) * 16 + 4 * lk + q, gc = c0 + (wc * 2 + j) * 16 + lr;
-        const bool ok = gr < p.m.R && gc < p.m.C && (!p.lower || gc <= gr + p.diag_off);
-        acc[i][j][q] = ok ? p.c[(size_t)gr * p.ldc + gc] : 0.f;
-      }
+  const pg_tile::Lanes<GP_V> ln;
+  pg_tile::Acc<GP_V> acc;
+  PG_TILE_FOR_EACH_OUTPUT(GP_V, ln, li, lj) {  // the chain continues from C
+    const int gr = r0 + li, gc = c0 + lj;
+    const bool ok = gr < p.m.R && gc < p.m.C && (!p.lower || gc <= gr + p.diag_off);
+    PG_TILE_OUTPUT(acc) = ok ? p.c[(size_t)gr * p.ldc + gc] : 0.f;
+  }
   float unused = 0.f;
-  gp_mma_tile<BK, NEG, false>(p.m, r0, c0, s_a, s_b, acc, unused);
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int gr = r0 + (wr * 2 + i) * 16 + 4 * lk + q, gc = c0 + (wc * 2 + j) * 16 + lr;
-        if (!(gr < p.m.R && gc < p.m.C && (!p.lower || gc <= gr + p.diag_off))) continue;
-        p.c[(size_t)gr * p.ldc + gc] = acc[i][j][q];
-        if (p.mirror && gc != gr) p.c[(size_t)gc * p.ldc + gr] = acc[i][j][q];
-      }
+  gp_mma_tile<BK, NEG, false>(p.m, r0, c0, s_a, s_b, ln, acc, unused);
+  PG_TILE_FOR_EACH_OUTPUT(GP_V, ln, li, lj) {
+    const int gr = r0 + li, gc = c0 + lj;
+    if (!(gr < p.m.R && gc < p.m.C && (!p.lower || gc <= gr + p.diag_off))) continue;
+    p.c[(size_t)gr * p.ldc + gc] = PG_TILE_OUTPUT(acc);
+    if (p.mirror && gc != gr) p.c[(size_t)gc * p.ldc + gr] = PG_TILE_OUTPUT(acc);
+  }
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -219,8 +173,7 @@ __global__ void __launch_bounds__(GP_THREADS) gp_se_mfma_kernel(const GpSeArgs p
   __shared__ float s_n[2 * GP_T];
   const int r0 = (blockIdx.x / p.col_tiles) * GP_T, c0 = (blockIdx.x % p.col_tiles) * GP_T;
   if (p.lower && c0 > r0 + (GP_T - 1) + p.diag_off) return;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int lr = lane & 15, lk = lane >> 4, wr = wave >> 1, wc = wave & 1;
+  const pg_tile::Lanes<GP_V> ln;
   GpMma m;
   m.a = p.a;
   m.b = p.b;
@@ -230,27 +183,16 @@ __global__ void __launch_bounds__(GP_THREADS) gp_se_mfma_kernel(const GpSeArgs p
   m.R = p.n;
   m.C = p.m;
   m.K = p.d;
-  f32x4 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) acc[i][j][q] = 0.f;
+  pg_tile::Acc<GP_V> acc;
+  pg_tile::zero<GP_V>(acc);
   float norm = 0.f;
-  gp_mma_tile<true, false, true>(m, r0, c0, s_a, s_b, acc, norm);
+  gp_mma_tile<true, false, true>(m, r0, c0, s_a, s_b, ln, acc, norm);
   if (threadIdx.x < 2 * GP_T) s_n[threadIdx.x] = norm;
   __syncthreads();
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int r = (wr * 2 + i) * 16 + 4 * lk + q, c = (wc * 2 + j) * 16 + lr;
-        const float sq = fmaf(-2.f, acc[i][j][q], s_n[r] + s_n[GP_T + c]);
-        gp_se_store(p, r0 + r, c0 + c, fmaxf(sq, 0.f));
-      }
+  PG_TILE_FOR_EACH_OUTPUT(GP_V, ln, r, c) {
+    const float sq = fmaf(-2.f, PG_TILE_OUTPUT(acc), s_n[r] + s_n[GP_T + c]);
+    gp_se_store(p, r0 + r, c0 + c, fmaxf(sq, 0.f));
+  }
 }
 
 __global__ void __launch_bounds__(256) gp_add_diag_kernel(float* __restrict__ a, long ld, int n, float value) {

@@ -31,11 +31,12 @@
 
 #include "common.h"
 #include "gpt_ends.h"
+#include "mfma_tile.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-#define MFMA16(A, B, C) __builtin_amdgcn_mfma_f32_16x16x4f32((A), (B), (C), 0, 0, 0)
+using pg_tile::f32x4;
+using pg_tile::mfma16;
 
 constexpr int C = 16, HD = 64, QKV = 48;
 constexpr int GB_THREADS = 256;  // 4 waves
@@ -185,7 +186,7 @@ __device__ __forceinline__ void head_chain(const f32x4& xv, const HeadFrags& f, 
   for (int m = 0; m < 3; ++m) {
     out[m] = f.bias[m];
 #pragma unroll
-    for (int r = 0; r < 4; ++r) out[m] = MFMA16(f.wf[m][r], y[r], out[m]);
+    for (int r = 0; r < 4; ++r) out[m] = mfma16(f.wf[m][r], y[r], out[m]);
   }
 }
 __device__ __forceinline__ void store_qkv_tiles(float* __restrict__ qb, int L, int g, const f32x4 (&q)[3]) {
@@ -289,7 +290,7 @@ __device__ __forceinline__ f32x4 head_bwd_chain(const f32x4& xv, const f32x4& gx
 #pragma unroll
   for (int m = 0; m < 3; ++m) {
 #pragma unroll
-    for (int r = 0; r < 4; ++r) dy = MFMA16(f.wt(m, r), dqv[m][r], dy);
+    for (int r = 0; r < 4; ++r) dy = mfma16(f.wt(m, r), dqv[m][r], dy);
   }
   // LayerNorm backward (dy is the gradient of y = xhat * gamma + beta)
   f32x4 gy;
@@ -317,7 +318,7 @@ __device__ __forceinline__ f32x4 head_bwd_chain(const f32x4& xv, const f32x4& gx
     const f32x4 dqtm = lds_row4(tq, 16 * m + j, g);  // A[i = ch 16m+j][k = px 4g+e]
     acc.accb[m] += sum4(dqtm);
 #pragma unroll
-    for (int e = 0; e < 4; ++e) acc.accw[m] = MFMA16(dqtm[e], yt[e], acc.accw[m]);
+    for (int e = 0; e < 4; ++e) acc.accw[m] = mfma16(dqtm[e], yt[e], acc.accw[m]);
   }
   return dxv;
 }
@@ -422,7 +423,7 @@ struct TailFrags {
 __device__ __forceinline__ f32x4 tail_chain(const f32x4& xv, const f32x4& ov, const TailFrags& f, float eps) {
   f32x4 xm = xv + f.bpv;
 #pragma unroll
-  for (int r = 0; r < 4; ++r) xm = MFMA16(f.wpf[r], ov[r], xm);
+  for (int r = 0; r < 4; ++r) xm = mfma16(f.wpf[r], ov[r], xm);
   const Ln s = ln_stats(xm, eps);
   f32x4 y;
 #pragma unroll
@@ -432,13 +433,13 @@ __device__ __forceinline__ f32x4 tail_chain(const f32x4& xv, const f32x4& ov, co
   for (int m = 0; m < 4; ++m) {
     h[m] = f.b1r[m];
 #pragma unroll
-    for (int r = 0; r < 4; ++r) h[m] = MFMA16(f.w1f[m][r], y[r], h[m]);
+    for (int r = 0; r < 4; ++r) h[m] = mfma16(f.w1f[m][r], y[r], h[m]);
   }
   f32x4 out = (xm + f.b2v) + xv;
 #pragma unroll
   for (int m = 0; m < 4; ++m) {
 #pragma unroll
-    for (int r = 0; r < 4; ++r) out = MFMA16(f.w2f[m][r], gelu_f(h[m][r]), out);
+    for (int r = 0; r < 4; ++r) out = mfma16(f.w2f[m][r], gelu_f(h[m][r]), out);
   }
   return out;
 }
@@ -589,7 +590,7 @@ __device__ __forceinline__ void tail_bwd_chain(const f32x4& xv, const f32x4& ov,
   // ---- recompute the forward: x_mid, LN2
   f32x4 xm = xv + f.bpv;
 #pragma unroll
-  for (int r = 0; r < 4; ++r) xm = MFMA16(f.wpf[r], ov[r], xm);
+  for (int r = 0; r < 4; ++r) xm = mfma16(f.wpf[r], ov[r], xm);
   const Ln s = ln_stats(xm, eps);
   f32x4 y;
 #pragma unroll
@@ -608,8 +609,8 @@ __device__ __forceinline__ void tail_bwd_chain(const f32x4& xv, const f32x4& ov,
     f32x4 h = {f.b1r(m, 0), f.b1r(m, 1), f.b1r(m, 2), f.b1r(m, 3)}, dg = zero4;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      h = MFMA16(f.w1f(m, r), y[r], h);
-      dg = MFMA16(f.w2t(m, r), dv[r], dg);
+      h = mfma16(f.w1f(m, r), y[r], h);
+      dg = mfma16(f.w2t(m, r), dv[r], dg);
     }
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -620,15 +621,15 @@ __device__ __forceinline__ void tail_bwd_chain(const f32x4& xv, const f32x4& ov,
       const float dh = dg[r] * fmaf(hv, pdf, cdf);
       tg[(4 * g + r) * TS + j] = hv * cdf;
       th[(4 * g + r) * TS + j] = dh;
-      dy = MFMA16(f.w1t(m, r), dh, dy);
+      dy = mfma16(f.w1t(m, r), dh, dy);
     }
     const f32x4 gt = lds_row4(tg, j, g);  // B[k = px][hidden 16m+j]
     const f32x4 ht = lds_row4(th, j, g);  // A[i = hidden 16m+j][k = px]
     acc.db1[m] += sum4(ht);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      acc.acc2[m] = MFMA16(dvt[e], gt[e], acc.acc2[m]);  // dW2[co][hidden] += D[px][co] G[px][hidden]
-      acc.acc1[m] = MFMA16(ht[e], yt[e], acc.acc1[m]);   // dW1[hidden][c]  += dH[px][hidden] y[px][c]
+      acc.acc2[m] = mfma16(dvt[e], gt[e], acc.acc2[m]);  // dW2[co][hidden] += D[px][co] G[px][hidden]
+      acc.acc1[m] = mfma16(ht[e], yt[e], acc.acc1[m]);   // dW1[hidden][c]  += dH[px][hidden] y[px][c]
     }
   }
   // ---- LN2 backward, d x_mid = D + LN2'(dY)
@@ -651,13 +652,13 @@ __device__ __forceinline__ void tail_bwd_chain(const f32x4& xv, const f32x4& ov,
     gxv[r] = dv[r] + dxm[r];
   }
 #pragma unroll
-  for (int r = 0; r < 4; ++r) dov = MFMA16(f.wpt[r], dxm[r], dov);
+  for (int r = 0; r < 4; ++r) dov = mfma16(f.wpt[r], dxm[r], dov);
   // ---- dWp[co][ci] += dx_mid[px][co] o[px][ci]
   const f32x4 xt = lds_row4(tx, j, g);  // A[i = co j][k = px]
   const f32x4 ot = lds_row4(to, j, g);  // B[k = px][ci = j]
   acc.dbp += sum4(xt);
 #pragma unroll
-  for (int e = 0; e < 4; ++e) acc.accp = MFMA16(xt[e], ot[e], acc.accp);
+  for (int e = 0; e < 4; ++e) acc.accp = mfma16(xt[e], ot[e], acc.accp);
 }
 // a wave's sums -> its T_PART floats of LDS staging
 __device__ __forceinline__ void tail_bwd_stage(float* mine, const TailBwdAcc& acc, int j, int g) {

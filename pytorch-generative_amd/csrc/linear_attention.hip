@@ -28,6 +28,7 @@
 // then la_den_bwd_kernel adds the denominator's terms per pixel (dphi(q)[h] += gs[h] Kc[h], dphi(k)[h'] +=
 // sum_{h >= h'} gs[h] phi(q)[h]: the cross-head term of the cumsum) and multiplies by phi'(t) = t > 0 ? 1 : phi(t).
 #include "common.h"
+#include "mfma_tile.h"
 
 namespace {
 
@@ -36,7 +37,7 @@ constexpr int LA_D = 64;           // largest head dim (PG_ESHAPE above)
 constexpr int LA_LD = LA_T + 1;    // LDS row stride in floats: the column reads of the MFMA operands are conflict free
 constexpr int LA_THREADS = 256;    // 4 waves
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using pg_tile::f32x4;
 
 #define LA_MFMA(A, B, C) __builtin_amdgcn_mfma_f32_16x16x4f32((A), (B), (C), 0, 0, 0)
 

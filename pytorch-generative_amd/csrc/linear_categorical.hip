@@ -37,11 +37,12 @@
 
 #include "categorical.h"
 #include "common.h"
+#include "mfma_tile.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-#define MFMA16(A, B, C) __builtin_amdgcn_mfma_f32_16x16x4f32((A), (B), (C), 0, 0, 0)
+using pg_tile::f32x4;
+using pg_tile::mfma16;
 
 constexpr int LC_PX = 16;             // pixels per tile
 constexpr int LC_MAX_ROWS = 1024;     // workgroups (= partial rows) at most: four waves per CU
@@ -128,10 +129,10 @@ __device__ __forceinline__ f32x4 lc_z(const float* wp, const float* bp, const fl
       av = *reinterpret_cast<const float4*>(wr + 4 * c4);
       bv = hs4[c4 * LC_PX + j];
     }
-    acc = MFMA16(av.x, bv.x, acc);
-    acc = MFMA16(av.y, bv.y, acc);
-    acc = MFMA16(av.z, bv.z, acc);
-    acc = MFMA16(av.w, bv.w, acc);
+    acc = mfma16(av.x, bv.x, acc);
+    acc = mfma16(av.y, bv.y, acc);
+    acc = mfma16(av.z, bv.z, acc);
+    acc = mfma16(av.w, bv.w, acc);
   }
   return acc;
 }
@@ -373,7 +374,7 @@ __global__ void __launch_bounds__(64) lc_bwd_kernel(LcArgs a) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
               const int k = min(k0 + 4 * g + r, K - 1);
-              dha[ct] = MFMA16(wp[((size_t)k * C + c) * Cin + ci], d[r], dha[ct]);
+              dha[ct] = mfma16(wp[((size_t)k * C + c) * Cin + ci], d[r], dha[ct]);
             }
           }
         }
@@ -397,7 +398,7 @@ __global__ void __launch_bounds__(64) lc_bwd_kernel(LcArgs a) {
               cw[r] = (k < K && ci < Cin) ? accW[((size_t)k * C + c) * Cin + ci] : 0.f;
             }
 #pragma unroll
-            for (int e = 0; e < 4; ++e) cw = MFMA16(ta[e], hs[((cic >> 2) * LC_PX + 4 * g + e) * 4 + (cic & 3)], cw);
+            for (int e = 0; e < 4; ++e) cw = mfma16(ta[e], hs[((cic >> 2) * LC_PX + 4 * g + e) * 4 + (cic & 3)], cw);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
               const int k = k0 + 4 * g + r;

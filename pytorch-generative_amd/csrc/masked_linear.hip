@@ -23,6 +23,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "mfma_tile.h"
 
 namespace {
 
@@ -34,7 +35,7 @@ constexpr int ML_THREADS = 256;
 constexpr int ML_A_PER = ML_BM * ML_KC / ML_THREADS;  // 16 staged A elements per thread
 constexpr int ML_B_PER = ML_BN * ML_KC / ML_THREADS;  // 8 staged B elements per thread
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using pg_tile::f32x4;
 
 enum { ML_FWD = 0, ML_DGRAD = 1, ML_WGRAD = 2 };
 

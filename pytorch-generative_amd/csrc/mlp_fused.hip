@@ -23,11 +23,12 @@
 // workgroup's waves in LDS, written as one partial row per workgroup and summed by a second kernel
 // (deterministic, no atomics), exactly like conv_wgrad.hip.
 #include "common.h"
+#include "mfma_tile.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-#define MFMA16(A, B, C) __builtin_amdgcn_mfma_f32_16x16x4f32((A), (B), (C), 0, 0, 0)
+using pg_tile::f32x4;
+using pg_tile::mfma16;
 
 constexpr int C = 16, HD = 64;           // channels, hidden units (the only instantiated shape)
 constexpr int MLP_THREADS = 256;         // 4 waves
@@ -79,13 +80,13 @@ __global__ void __launch_bounds__(MLP_THREADS) mlp_fwd_kernel(const MlpArgs a) {
     for (int m = 0; m < 4; ++m) {
       h[m] = b1r[m];
 #pragma unroll
-      for (int s = 0; s < 4; ++s) h[m] = MFMA16(w1f[m][s], xb[s], h[m]);
+      for (int s = 0; s < 4; ++s) h[m] = mfma16(w1f[m][s], xb[s], h[m]);
     }
     f32x4 yv = b2r + rv;
 #pragma unroll
     for (int m = 0; m < 4; ++m) {
 #pragma unroll
-      for (int r = 0; r < 4; ++r) yv = MFMA16(w2f[m][r], gelu_f(h[m][r]), yv);
+      for (int r = 0; r < 4; ++r) yv = mfma16(w2f[m][r], gelu_f(h[m][r]), yv);
     }
 #pragma unroll
     for (int r = 0; r < 4; ++r) a.y[base + (size_t)(4 * g + r) * a.L] = yv[r];
@@ -149,8 +150,8 @@ __global__ void __launch_bounds__(MLP_THREADS) mlp_bwd_kernel(const MlpArgs a) {
       dg[m] = zero4;
 #pragma unroll
       for (int s = 0; s < 4; ++s) {
-        h[m] = MFMA16(w1f[m][s], xb[s], h[m]);
-        dg[m] = MFMA16(w2t[m][s], dyb[s], dg[m]);
+        h[m] = mfma16(w1f[m][s], xb[s], h[m]);
+        dg[m] = mfma16(w2t[m][s], dyb[s], dg[m]);
       }
     }
     // G = gelu(H), dH = dG * gelu'(H); both also go to LDS transposed for the weight gradients
@@ -169,7 +170,7 @@ __global__ void __launch_bounds__(MLP_THREADS) mlp_bwd_kernel(const MlpArgs a) {
         tg[hid * TS + j] = gv;
         th[hid * TS + j] = dh;
         db1[m][r] += dh;
-        dxv = MFMA16(w1t[m][r], dh, dxv);
+        dxv = mfma16(w1t[m][r], dh, dxv);
       }
     }
 #pragma unroll
@@ -183,8 +184,8 @@ __global__ void __launch_bounds__(MLP_THREADS) mlp_bwd_kernel(const MlpArgs a) {
       const f32x4 ht = *reinterpret_cast<const f32x4*>(th + (16 * m + j) * TS + 4 * g);  // A[i=hidden][k=px]
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        acc2[m] = MFMA16(dyt[e], gt[e], acc2[m]);  // dW2[co][hidden] += dY[px][co] G[px][hidden]
-        acc1[m] = MFMA16(ht[e], xt[e], acc1[m]);   // dW1[hidden][c] += dH[px][hidden] X[px][c]
+        acc2[m] = mfma16(dyt[e], gt[e], acc2[m]);  // dW2[co][hidden] += dY[px][co] G[px][hidden]
+        acc1[m] = mfma16(ht[e], xt[e], acc1[m]);   // dW1[hidden][c] += dH[px][hidden] X[px][c]
       }
     }
   }

@@ -16,6 +16,7 @@
 // each WRITES its whole (codes x dims) tile of the workspace (no zero fill needed, none is assumed), and
 // vq_cbgrad_finish_kernel adds the ranges in order: no float atomics, bit-reproducible in both determinism modes.
 #include "common.h"
+#include "mfma_tile.h"
 
 namespace {
 
@@ -38,7 +39,7 @@ constexpr int VT_MAX_D = 1 << 20;
 constexpr int VT_MAX_K = 65535 * CG_BK;               // gridDim.y of the gradient kernel
 constexpr long VT_MAX_P = (1L << 31) - 1 - VT_BM;     // idx and block offsets stay in int range
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using pg_tile::f32x4;
 
 __global__ void __launch_bounds__(VT_THREADS) vq_tiled_assign_kernel(
     const float* __restrict__ x, const float* __restrict__ emb, int* __restrict__ idx, float* __restrict__ q,
