@@ -609,6 +609,51 @@ int pg_gp_potrf(float* a, long ld, int n, int n_done, int* info, void* stream);
 int pg_gp_trsm_right(const float* l, long ld, int n, float* x, long ldx, int rows, int col_done, int transposed, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * The log marginal likelihood of a Gaussian process and its gradients with respect to the hyperparameters (csrc/gp_mll.hip),
+ * from the cached factor K = K_f + noise_var I = L L^T, z^T = (L^-1 r)^T (p, n) and alpha^T = (K^-1 r)^T (p, n), r = y - value:
+ *     log p(y) = -1/2 sum z^2 - p sum_i log L_ii - (n p / 2) log 2 pi,      G = alpha alpha^T - p K^-1,
+ *     d/d std = sum_ij G_ij K_f,ij / std,   d/d lengthscale = sum_ij G_ij K_f,ij D2_ij / (2 l^3),   d/d noise_var = tr G / 2,
+ *     d/d value = sum alpha.
+ * K^-1 = X X^T with X = L^-T UPPER triangular, so every product is triangular: about n^3 / 3 flops for X and for X X^T each.
+ * Operands as above (fp32, row-major, leading dimension in floats). pg_gp_mll_plan (host only) is the one function that decides
+ * the domain — that of pg_gp_plan: n in 1 .. 16384, d, p in 1 .. 4096 — and the geometry; every entry point below calls it and
+ * follows the status conventions above (PG_ESHAPE, PG_EINVAL, hipErrorNoDevice only for an accepted call). It fills
+ * out[0 .. PG_GP_MLL_PLAN_INTS): [0] the tile edge (64), [1] panels P of n, [2] the launches of the inverse (2 P - 1), [3] the
+ * 64x64x64 tile-products of the inverse on the MFMA (sum_k (k + 1)(P - 1 - k)), [4] the tiles X X^T writes (on or below the
+ * diagonal, P (P + 1) / 2), [5] its tile-products (sum_I (I + 1)(P - I): tile (I, J) starts its k loop at row tile I), [6] the
+ * tiles the reduction visits (P (P + 1) / 2), [7] its partial rows (one per tile, three floats each), [8] the workspace floats
+ * the caller passes to se_mll_sums (3 x [7]), [9] the covariance route of the reduction (that of pg_gp_plan: 0 exact
+ * differences, 1 the MFMA), [10] the largest d of route 0, [11] the largest n, [12] d, [13] p, [14] the k chunks of the outer
+ * product alpha_i . alpha_j (every p takes the in-kernel MFMA route), [15] the launches of the reduction (2).
+ *   trtri_t:     X = L^-T into the upper triangle of x (diagonal included); the strict lower triangle of x and the strict upper
+ *                triangle of l are neither read nor written; x must not be l. The right-looking solve of X L^T = I in panels
+ *                at absolute multiples of 64: panel k is solved for the rows above its end only (rows below are zero) by the
+ *                fmaf chain in ascending k and one IEEE division on the VALU (no explicit inverse of a diagonal block beyond
+ *                the block's own result), then the (k + 1) x (P - 1 - k) tiles to its right are updated on the MFMA, the
+ *                accumulators seeded with x (zero where a tile is touched first).
+ *   gram_upper:  H = X X^T for the upper triangular X, on the lower triangle of h (diagonal included); flags = PG_GP_MIRROR:
+ *                h[j][i] = h[i][j] too. Tile (I, J), J <= I, starts its k loop at 64 I; the strict lower triangle of x is
+ *                not read. Each element is one fmaf chain in ascending k. No k-split. h must not be x.
+ *   se_mll_sums: one workgroup per 64 x 64 tile on or below the diagonal recomputes D2 and K_f from the rows of x (n, d) (the
+ *                routes and the bits of se_kernel; the diagonal is K_f = std^2, D2 = 0 exactly), forms
+ *                G_ij = sum_c alpha_ic alpha_jc - p H_ij in registers (only the lower triangle of h is read) and sums
+ *                G K_f, G K_f D2 (off-diagonal elements twice) and G_ii; K_f, D2 and G are never written. Every workgroup
+ *                writes its three fp32 partials into ws (ws_floats >= plan[8], PG_EINVAL below); a second launch of one
+ *                workgroup adds them in double — thread t the tiles t, t + 256, ... ascending, then a fixed tree — and writes
+ *                out[0 .. 3) = d/d std, d/d lengthscale, d/d noise_var. lengthscale > 0, std != 0.
+ *   mll_value:   one workgroup, fixed order, double accumulators: out[0] = log p(y), out[1] = sum alpha.
+ * out is device memory. No float atomics, no allocation, no host synchronisation (capturable), bit-identical from run to run.
+ * ------------------------------------------------------------------------------------- */
+#define PG_GP_MLL_PLAN_INTS 16
+int pg_gp_mll_plan(int n, int d, int p, long long* out, int out_len);
+int pg_gp_trtri_t(const float* l, long ld, int n, float* x, long ldx, void* stream);
+int pg_gp_gram_upper(const float* x, long ldx, int n, float* h, long ldh, int flags, void* stream);
+int pg_gp_se_mll_sums(const float* x, long ldx, int n, int d, float std, float lengthscale, const float* h, long ldh,
+                      const float* alpha_t, long lda, int p, float* ws, size_t ws_floats, float* out, void* stream);
+int pg_gp_mll_value(const float* l, long ld, int n, const float* zt, long ldz, const float* alpha_t, long lda, int p, float* out,
+                    void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Density estimators (models/mixture_models.py, models/kde.py) on streaming log-density kernels (density.hip):
  * the pairwise log-density c[n][k] = sum_d f(x[n][d], theta[k][d]) is one or two fp32-MFMA GEMMs plus a per-column
  * constant, reduced by a running logsumexp over column tiles; nothing of size N x K (x F) is written to memory.

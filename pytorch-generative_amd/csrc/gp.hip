@@ -18,60 +18,9 @@
 // No float atomics, each output element is owned by one lane, every order is fixed by the shape: bit-identical from run to
 // run. No host synchronisation and no allocation: capturable. gp_plan is the one function that decides the domain and the
 // geometry; every entry point calls it, and reports a missing device only after it accepted the problem.
-#include <algorithm>
-
-#include "common.h"
-#include "mfma_tile.h"
+#include "gp_common.h"
 
 namespace {
-
-constexpr int GP_V = pg_tile::SMALL;  // the MFMA products run on the small tile of mfma_tile.h
-using GpTile = pg_tile::Tile<GP_V>;
-constexpr int GP_T = GpTile::BM;   // panel width, tile edge
-constexpr int GP_KC = GpTile::KC;  // k per LDS chunk
-constexpr int GP_LD = GpTile::LD;  // LDS row stride of an operand chunk
-constexpr int GP_THREADS = pg_tile::THREADS;
-constexpr int GP_BLK_LD = 68;    // LDS row stride of the diagonal block in gp_potrf_diag_kernel
-constexpr int GP_TRI_LD = 65;    // LDS row stride of the diagonal block in gp_trsm_diag_kernel and of the rows in gp_se_direct_kernel
-constexpr int GP_MAX_N = 16384;  // n, m: element offsets of an (n, n) matrix fit 32 bits
-constexpr int GP_MAX_D = 4096;
-constexpr int GP_MAX_P = 4096;
-constexpr int GP_SE_DIRECT_D = 16;      // largest d of the exact-difference route: measured faster up to 16, slower from 32 (profiles/gp.json)
-constexpr int GP_SE_DIRECT_MAX_D = 64;  // largest d the exact-difference kernel holds in LDS when the route is forced
-
-// ---------------------------------------------------------------------------------------------------------------------------
-// The 64 x 64 x K product of one workgroup: acc += (NEG ? -A : A) B^T with A(r, k) = a[r * a_rs + k] and
-// B(c, k) = b[c * b_rs + k * b_ks], on mfma_tile.h's pipeline (BK: B is k-contiguous). Ragged edges are zero-filled. NORMS:
-// thread t < 64 also sums A(r0 + t, k)^2, thread 64 + t B(c0 + t, k)^2, in k order.
-struct GpMma {
-  const float* a;
-  const float* b;
-  long a_rs, b_rs, b_ks;
-  int R, C, K;
-};
-
-template <bool BK, bool NEG, bool NORMS>
-__device__ __forceinline__ void gp_mma_tile(const GpMma& p, int r0, int c0, float* s_a, float* s_b, const pg_tile::Lanes<GP_V>& ln,
-                                            pg_tile::Acc<GP_V>& acc, float& norm) {
-  const int tid = ln.tid;
-  pg_tile::Regs<GP_V> ra, rb;
-  auto load = [&](int ch) {
-    pg_tile::load_operand<GP_V, true, NEG>(ra, p.a, p.a_rs, 1, r0, p.R, ch * GP_KC, p.K, tid);
-    pg_tile::load_operand<GP_V, BK>(rb, p.b, p.b_rs, p.b_ks, c0, p.C, ch * GP_KC, p.K, tid);
-  };
-  auto store = [&]() {
-    pg_tile::store_operand<GP_V, true>(s_a, ra, tid);
-    pg_tile::store_operand<GP_V, BK>(s_b, rb, tid);
-  };
-  auto norms = [&](int) {
-    if (NORMS && tid < 2 * GP_T) {
-      const float* row = (tid < GP_T ? s_a + tid * GP_LD : s_b + (tid - GP_T) * GP_LD);
-#pragma unroll
-      for (int k = 0; k < GP_KC; ++k) norm = fmaf(row[k], row[k], norm);  // zero beyond K
-    }
-  };
-  PG_TILE_PIPELINE(GP_V, false, 0, (p.K + GP_KC - 1) / GP_KC, load, store, acc, s_a, s_b, ln, norms);  // every caller has K >= 1
-}
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // C = C -/+ A B^T. The accumulators are seeded with the tile of C. lower: only elements with c <= r + diag_off are read and
@@ -299,55 +248,6 @@ __global__ void __launch_bounds__(GP_THREADS) gp_trsm_diag_kernel(const float* _
   }
 }
 
-// ---------------------------------------------------------------------------------------------------------------------------
-// The one function that decides the domain and the geometry: pg_gp_plan reports it, every entry point goes by it.
-struct GpPlan {
-  int n, m, d, p, panels, row_tiles, se_route;
-  long se_sym_tiles, se_cross_tiles, potrf_launches, trsm_launches, trailing_groups;
-};
-
-int gp_plan(int n, int m, int d, int p, GpPlan& pl, const char* name) {
-  PG_REQUIRE(n >= 1 && m >= 1 && d >= 1 && p >= 1, PG_ESHAPE, "%s: n = %d, m = %d, d = %d, p = %d must all be >= 1", name, n, m, d, p);
-  PG_REQUIRE(n <= GP_MAX_N && m <= GP_MAX_N, PG_ESHAPE, "%s: n = %d, m = %d: at most %d rows (element offsets stay inside 32 bits)", name, n, m,
-             GP_MAX_N);
-  PG_REQUIRE(d <= GP_MAX_D && p <= GP_MAX_P, PG_ESHAPE, "%s: d = %d (at most %d), p = %d (at most %d)", name, d, GP_MAX_D, p, GP_MAX_P);
-  pl.n = n;
-  pl.m = m;
-  pl.d = d;
-  pl.p = p;
-  pl.panels = pg_cdiv(n, GP_T);
-  pl.row_tiles = pg_cdiv(m, GP_T);
-  pl.se_route = d <= GP_SE_DIRECT_D ? 0 : 1;
-  pl.se_sym_tiles = (long)pl.panels * (pl.panels + 1) / 2;
-  pl.se_cross_tiles = (long)pl.row_tiles * pl.panels;
-  pl.potrf_launches = 3L * pl.panels - 2;  // diagonal block, panel solve, trailing update; the last panel has no rows below
-  pl.trsm_launches = 2L * pl.panels - 1;   // panel solve, update of the columns to the right
-  pl.trailing_groups = (long)(pl.panels - 1) * (pl.panels - 1);
-  return 0;
-}
-
-#define GP_PLAN_OR_RETURN(pl, n, m, d, p, name)        \
-  GpPlan pl;                                           \
-  {                                                    \
-    const int rc__ = gp_plan(n, m, d, p, pl, name);    \
-    if (rc__) return rc__;                             \
-  }                                                    \
-  (void)pl;
-
-// a missing device is reported once the plan and the argument checks accepted the call
-int gp_device(const char* name) {
-  static bool seen = false;
-  if (seen) return 0;
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count < 1) {
-    (void)hipGetLastError();
-    pg_set_error("%s: no HIP device", name);
-    return (int)hipErrorNoDevice;
-  }
-  seen = true;
-  return 0;
-}
-
 // the launches; arguments are checked by the callers
 int gp_gemm(const float* a, long lda, const float* b, long ldb, float* c, long ldc, int R, int C, int K, int diag_off, int flags,
             hipStream_t st, const char* name) {
@@ -399,12 +299,6 @@ int gp_trsm_diag(const float* l, long ld, float* x, long ldx, int rows, int jb, 
   PG_LAUNCH_CHECK(name);
   return 0;
 }
-
-#define GP_TRY(call)           \
-  do {                         \
-    const int rc__ = (call);   \
-    if (rc__) return rc__;     \
-  } while (0)
 
 }  // namespace
 

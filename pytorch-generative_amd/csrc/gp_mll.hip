@@ -1,0 +1,466 @@
+// gp_mll.hip — the log marginal likelihood of a Gaussian process and its gradients with respect to the hyperparameters, from
+// the factor K = K_f + noise_var I = L L^T that gp.hip caches (r = y - value, z = L^-1 r, alpha = L^-T z):
+//     log p(y) = -1/2 sum z^2 - p sum_i log L_ii - (n p / 2) log 2 pi
+//     G = alpha alpha^T - p K^-1,   d/d std = sum G K_f / std,   d/d l = sum G K_f D2 / (2 l^3),   d/d noise_var = tr G / 2.
+//
+// The triangular structure. K^-1 = X X^T with X = L^-T, which is UPPER triangular:
+//   * pg_gp_trtri_t solves X L^T = I right-looking in panels of 64 columns at absolute multiples of 64. Row r of X is zero left of
+//     column r, so panel k is solved for the rows above its end only: the diagonal block and the blocks above it by the fmaf
+//     chain plus one division of gp.hip's substitution on the VALU (the diagonal block starts from the identity and keeps its
+//     upper triangle), then the (k + 1) x (P - 1 - k) tiles to the right on the MFMA, seeded with x — with zero for the row
+//     tile k, which is touched for the first time. Element (r, c) is one chain (delta_rc - sum_{k < c} x_rk l_ck) / l_cc in
+//     ascending k, as in gp.hip.
+//   * pg_gp_gram_upper forms (X X^T)_ij = sum_{k >= max(i, j)} x_ik x_jk for the tiles on or below the diagonal; tile (I, J)
+//     starts its k loop at 64 I. What lies below the diagonal of x is garbage and is masked to zero on the way into LDS: it adds
+//     exact zeros to a chain in ascending k.
+//   Both cost about n^3 / 3 flops, as the factorisation does.
+//   * pg_gp_se_mll_sums contracts G with K_f and K_f D2 without writing either: one workgroup per tile on or below the diagonal
+//     forms alpha_i . alpha_j on the MFMA, D2 by se_kernel's two routes (same bits), reads the tile of H = X X^T once, and reduces
+//     three sums in a fixed order — lane (16 elements in the order of PG_TILE_FOR_EACH_OUTPUT), wave (shuffle tree), the four
+//     waves in order — to one fp32 partial row per tile. gp_mll_finish_kernel adds the rows in double: thread t the tiles t,
+//     t + 256, ... ascending, then a fixed tree over the 256 threads.
+// No float atomics, no host synchronisation, no allocation: capturable, bit-identical from run to run. gp_mll_plan is the one
+// function that decides domain and geometry; every entry point calls it and reports a missing device only afterwards.
+#include "gp_common.h"
+
+namespace {
+
+constexpr int MLL_DIRECT_LD = GP_SE_DIRECT_D + 1;  // LDS row stride of the rows of x on the exact-difference route
+constexpr int MLL_SUMS = 3;                        // sum G K_f, sum G K_f D2, tr G
+
+// Tile t of the triangular enumeration (0, 0), (1, 0), (1, 1), (2, 0), ...: I its row tile, J <= I its column tile.
+__device__ __forceinline__ void mll_tri_tile(int t, int& I, int& J) {
+  I = (int)((sqrtf(8.f * (float)t + 1.f) - 1.f) * 0.5f);
+  while ((I + 1) * (I + 2) / 2 <= t) ++I;
+  while (I * (I + 1) / 2 > t) --I;
+  J = t - I * (I + 1) / 2;
+}
+
+// A thread's share of the chunk at absolute column k0 of rows row0 .. row0 + 63 of the upper triangular x: zero below the
+// diagonal (k < row: not read), from row R and from column kend on; negated on the way in if NEG.
+template <bool NEG>
+__device__ __forceinline__ void mll_load_upper(pg_tile::Regs<GP_V>& reg, const float* __restrict__ x, long ldx, int row0, int R, int k0,
+                                               int kend, int tid) {
+#pragma unroll
+  for (int j = 0; j < GP_T * GP_KC / GP_THREADS; ++j) {
+    int r, k;
+    pg_tile::coord<GP_T, GP_KC, true>(tid + j * GP_THREADS, r, k);
+    const int gr = row0 + r, gk = k0 + k;
+    const float v = (gr < R && gk < kend && gk >= gr) ? x[(size_t)gr * ldx + gk] : 0.f;
+    reg[j] = NEG ? -v : v;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// Panel k of X L^T = I, columns j0 .. j0 + jb of the rows 0 .. j0 + jb: gp.hip's forward substitution against the diagonal block
+// l (jb, jb), 64 rows per workgroup, four lanes per row. x points at column j0 of row 0. The workgroup of the diagonal block
+// (rows j0 ..) starts from the identity and writes the columns on or right of the diagonal only; the others continue from the
+// values the updates left.
+__global__ void __launch_bounds__(GP_THREADS) gp_trtri_diag_kernel(const float* __restrict__ l, long ld, float* __restrict__ x, long ldx,
+                                                                   int j0, int jb) {
+  __shared__ float s_l[GP_T * GP_TRI_LD];
+  const int tid = threadIdx.x, lane = tid & 63;
+  for (int e = tid; e < GP_T * GP_T; e += GP_THREADS) {
+    const int j = e >> 6, k = e & 63;
+    float v = j == k ? 1.f : 0.f;  // rows beyond jb: the identity
+    if (j < jb && k <= j) v = l[(size_t)j * ld + k];
+    s_l[j * GP_TRI_LD + k] = v;
+  }
+  const int rows = j0 + jb;
+  const int row = blockIdx.x * GP_T + (tid >> 2), c = tid & 3;
+  const bool diag = (int)blockIdx.x * GP_T == j0;
+  const int first = diag ? row - j0 : 0;  // the first column of the panel this row owns
+  float v[16];
+#pragma unroll
+  for (int q = 0; q < 16; ++q) {
+    const int j = 4 * q + c;
+    float b = 0.f;
+    if (row < rows && j < jb) b = diag ? (j == first ? 1.f : 0.f) : x[(size_t)row * ldx + j];
+    v[q] = b;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < GP_T; ++k) {
+    if (k < jb) {  // the same in every lane
+      const int qk = k >> 2, ck = k & 3;
+      const float cand = v[qk] / s_l[k * GP_TRI_LD + k];
+      const float xk = __shfl(cand, (lane & ~3) | ck);
+      if (c == ck) v[qk] = xk;
+#pragma unroll
+      for (int q = qk; q < 16; ++q) {
+        const int j = 4 * q + c;
+        if (j > k) v[q] = fmaf(-xk, s_l[j * GP_TRI_LD + k], v[q]);
+      }
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < 16; ++q) {
+    const int j = 4 * q + c;
+    if (row < rows && j < jb && j >= first) x[(size_t)row * ldx + j] = v[q];
+  }
+}
+
+// The update after panel k (j0 = 64 k): x[r][c] -= sum_{k' < 64} x[r][j0 + k'] l[c][j0 + k'] for the rows r < j0 + 64 and the
+// columns c >= j0 + 64, one 64 x 64 tile per workgroup. The row tile of the panel itself has not been written yet: it is
+// seeded with zero and its operand is the upper triangle of the diagonal block.
+__global__ void __launch_bounds__(GP_THREADS) gp_trtri_update_kernel(const float* __restrict__ l, long ld, float* __restrict__ x, long ldx,
+                                                                     int n, int j0, int col_tiles) {
+  __shared__ float s_a[GP_T * GP_LD];
+  __shared__ float s_b[GP_T * GP_LD];
+  const int r0 = (blockIdx.x / col_tiles) * GP_T, c0 = j0 + GP_T + (blockIdx.x % col_tiles) * GP_T;
+  const bool fresh = r0 == j0;
+  const pg_tile::Lanes<GP_V> ln;
+  const int tid = ln.tid;
+  pg_tile::Acc<GP_V> acc;
+  PG_TILE_FOR_EACH_OUTPUT(GP_V, ln, li, lj) {  // the chain continues from x
+    const int gr = r0 + li, gc = c0 + lj;
+    PG_TILE_OUTPUT(acc) = (!fresh && gc < n) ? x[(size_t)gr * ldx + gc] : 0.f;
+  }
+  pg_tile::Regs<GP_V> ra, rb;
+  auto load = [&](int ch) {
+    mll_load_upper<true>(ra, x, ldx, r0, j0 + GP_T, j0 + ch * GP_KC, j0 + GP_T, tid);
+    pg_tile::load_operand<GP_V, true>(rb, l + j0, ld, 1, c0, n, ch * GP_KC, GP_T, tid);
+  };
+  auto store = [&]() {
+    pg_tile::store_operand<GP_V, true>(s_a, ra, tid);
+    pg_tile::store_operand<GP_V, true>(s_b, rb, tid);
+  };
+  auto none = [](int) {};
+  PG_TILE_PIPELINE(GP_V, false, 0, GP_T / GP_KC, load, store, acc, s_a, s_b, ln, none);
+  PG_TILE_FOR_EACH_OUTPUT(GP_V, ln, li, lj) {
+    const int gr = r0 + li, gc = c0 + lj;
+    if (gc < n) x[(size_t)gr * ldx + gc] = PG_TILE_OUTPUT(acc);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// H = X X^T on the tiles on or below the diagonal: tile (I, J) sums k from 64 I on.
+__global__ void __launch_bounds__(GP_THREADS) gp_gram_upper_kernel(const float* __restrict__ x, long ldx, int n, float* __restrict__ h,
+                                                                   long ldh, int mirror) {
+  __shared__ float s_a[GP_T * GP_LD];
+  __shared__ float s_b[GP_T * GP_LD];
+  int I, J;
+  mll_tri_tile(blockIdx.x, I, J);
+  const int r0 = I * GP_T, c0 = J * GP_T;
+  const pg_tile::Lanes<GP_V> ln;
+  const int tid = ln.tid;
+  pg_tile::Acc<GP_V> acc;
+  pg_tile::zero<GP_V>(acc);
+  pg_tile::Regs<GP_V> ra, rb;
+  auto load = [&](int ch) {
+    mll_load_upper<false>(ra, x, ldx, r0, n, ch * GP_KC, n, tid);
+    mll_load_upper<false>(rb, x, ldx, c0, n, ch * GP_KC, n, tid);
+  };
+  auto store = [&]() {
+    pg_tile::store_operand<GP_V, true>(s_a, ra, tid);
+    pg_tile::store_operand<GP_V, true>(s_b, rb, tid);
+  };
+  auto none = [](int) {};
+  PG_TILE_PIPELINE(GP_V, false, r0 / GP_KC, (n + GP_KC - 1) / GP_KC, load, store, acc, s_a, s_b, ln, none);  // r0 < n: a chunk at least
+  PG_TILE_FOR_EACH_OUTPUT(GP_V, ln, li, lj) {
+    const int gr = r0 + li, gc = c0 + lj;
+    if (!(gr < n && gc <= gr)) continue;
+    h[(size_t)gr * ldh + gc] = PG_TILE_OUTPUT(acc);
+    if (mirror && gc != gr) h[(size_t)gc * ldh + gr] = PG_TILE_OUTPUT(acc);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// The reduction. ROUTE 0: exact differences (d <= 16), ROUTE 1: |a|^2 + |b|^2 - 2 a.b on the MFMA, clamped at 0.
+struct GpMllSumsArgs {
+  const float* x;
+  const float* h;
+  const float* at;
+  float* ws;
+  long ldx, ldh, lda;
+  int n, d, p;
+  float std2, neg_inv, pf;
+};
+
+template <int ROUTE>
+__global__ void __launch_bounds__(GP_THREADS) gp_se_mll_sums_kernel(const GpMllSumsArgs p) {
+  __shared__ float s_a[GP_T * GP_LD];
+  __shared__ float s_b[GP_T * GP_LD];
+  __shared__ float s_n[2 * GP_T];
+  __shared__ float s_red[4 * MLL_SUMS];
+  int I, J;
+  mll_tri_tile(blockIdx.x, I, J);
+  const int r0 = I * GP_T, c0 = J * GP_T;
+  const pg_tile::Lanes<GP_V> ln;
+  const int tid = ln.tid;
+
+  // alpha_i . alpha_j over the p columns of y: alpha^T is (p, n), so both operands are row-contiguous
+  pg_tile::Acc<GP_V> g;
+  pg_tile::zero<GP_V>(g);
+  {
+    pg_tile::Regs<GP_V> ra, rb;
+    auto load = [&](int ch) {
+      pg_tile::load_operand<GP_V, false>(ra, p.at, 1, p.lda, r0, p.n, ch * GP_KC, p.p, tid);
+      pg_tile::load_operand<GP_V, false>(rb, p.at, 1, p.lda, c0, p.n, ch * GP_KC, p.p, tid);
+    };
+    auto store = [&]() {
+      pg_tile::store_operand<GP_V, false>(s_a, ra, tid);
+      pg_tile::store_operand<GP_V, false>(s_b, rb, tid);
+    };
+    auto none = [](int) {};
+    PG_TILE_PIPELINE(GP_V, false, 0, (p.p + GP_KC - 1) / GP_KC, load, store, g, s_a, s_b, ln, none);
+  }
+
+  // the squared distances, with the bits of se_kernel's route
+  pg_tile::Acc<GP_V> sq;
+  pg_tile::zero<GP_V>(sq);
+  if (ROUTE == 0) {
+    for (int e = tid; e < GP_T * p.d; e += GP_THREADS) {
+      const int r = e / p.d, k = e % p.d;
+      s_a[r * MLL_DIRECT_LD + k] = r0 + r < p.n ? p.x[(size_t)(r0 + r) * p.ldx + k] : 0.f;
+      s_b[r * MLL_DIRECT_LD + k] = c0 + r < p.n ? p.x[(size_t)(c0 + r) * p.ldx + k] : 0.f;
+    }
+    __syncthreads();
+    for (int k = 0; k < p.d; ++k) {
+      float av[2][4], bv[2];
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) av[i][q] = s_a[pg_tile::out_row<GP_V>(ln, i, q) * MLL_DIRECT_LD + k];
+        bv[i] = s_b[pg_tile::out_col<GP_V>(ln, i) * MLL_DIRECT_LD + k];
+      }
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const float df = av[i][q] - bv[j];
+            sq[i][j][q] = fmaf(df, df, sq[i][j][q]);
+          }
+    }
+  } else {
+    GpMma m;
+    m.a = p.x;
+    m.b = p.x;
+    m.a_rs = p.ldx;
+    m.b_rs = p.ldx;
+    m.b_ks = 1;
+    m.R = p.n;
+    m.C = p.n;
+    m.K = p.d;
+    float norm = 0.f;
+    gp_mma_tile<true, false, true>(m, r0, c0, s_a, s_b, ln, sq, norm);
+    if (tid < 2 * GP_T) s_n[tid] = norm;
+    __syncthreads();
+    PG_TILE_FOR_EACH_OUTPUT(GP_V, ln, r, c) {
+      PG_TILE_OUTPUT(sq) = fmaxf(fmaf(-2.f, PG_TILE_OUTPUT(sq), s_n[r] + s_n[GP_T + c]), 0.f);
+    }
+  }
+
+  float sum[MLL_SUMS] = {0.f, 0.f, 0.f};
+  PG_TILE_FOR_EACH_OUTPUT(GP_V, ln, li, lj) {
+    const int gr = r0 + li, gc = c0 + lj;
+    if (!(gr < p.n && gc <= gr)) continue;
+    const float gv = fmaf(-p.pf, p.h[(size_t)gr * p.ldh + gc], PG_TILE_OUTPUT(g));
+    if (gc == gr) {  // K_f = std^2 and D2 = 0 exactly
+      sum[0] = fmaf(gv, p.std2, sum[0]);
+      sum[2] += gv;
+    } else {  // (i, j) and (j, i)
+      const float d2 = PG_TILE_OUTPUT(sq);
+      const float t = 2.f * gv * (p.std2 * expf(d2 * p.neg_inv));
+      sum[0] += t;
+      sum[1] = fmaf(t, d2, sum[1]);
+    }
+  }
+#pragma unroll
+  for (int s = 0; s < MLL_SUMS; ++s) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) sum[s] += __shfl_down(sum[s], off);
+    if ((tid & 63) == 0) s_red[(tid >> 6) * MLL_SUMS + s] = sum[s];
+  }
+  __syncthreads();
+  if (tid < MLL_SUMS)
+    p.ws[(size_t)blockIdx.x * MLL_SUMS + tid] =
+        ((s_red[tid] + s_red[MLL_SUMS + tid]) + s_red[2 * MLL_SUMS + tid]) + s_red[3 * MLL_SUMS + tid];
+}
+
+// The sum of `len` doubles per thread slot, a fixed tree over the 256 threads; the total is in s[0 .. len) afterwards.
+template <int LEN>
+__device__ __forceinline__ void mll_tree(double* s, const double (&v)[LEN], int tid) {
+#pragma unroll
+  for (int k = 0; k < LEN; ++k) s[k * GP_THREADS + tid] = v[k];
+  __syncthreads();
+  for (int half = GP_THREADS / 2; half >= 1; half >>= 1) {
+    if (tid < half) {
+#pragma unroll
+      for (int k = 0; k < LEN; ++k) s[k * GP_THREADS + tid] += s[k * GP_THREADS + tid + half];
+    }
+    __syncthreads();
+  }
+}
+
+__global__ void __launch_bounds__(GP_THREADS) gp_mll_finish_kernel(const float* __restrict__ ws, int tiles, double inv_std, double inv_2l3,
+                                                                   float* __restrict__ out) {
+  __shared__ double s[MLL_SUMS * GP_THREADS];
+  const int tid = threadIdx.x;
+  double v[MLL_SUMS] = {0., 0., 0.};
+  for (int t = tid; t < tiles; t += GP_THREADS) {
+#pragma unroll
+    for (int k = 0; k < MLL_SUMS; ++k) v[k] += (double)ws[(size_t)t * MLL_SUMS + k];
+  }
+  mll_tree<MLL_SUMS>(s, v, tid);
+  if (tid == 0) {
+    out[0] = (float)(s[0] * inv_std);
+    out[1] = (float)(s[GP_THREADS] * inv_2l3);
+    out[2] = (float)(0.5 * s[2 * GP_THREADS]);
+  }
+}
+
+// log p(y) and sum alpha: one workgroup, thread t the elements t, t + 256, ... of every row ascending, then the fixed tree.
+__global__ void __launch_bounds__(GP_THREADS) gp_mll_value_kernel(const float* __restrict__ l, long ld, int n, const float* __restrict__ zt,
+                                                                  long ldz, const float* __restrict__ at, long lda, int p,
+                                                                  float* __restrict__ out) {
+  __shared__ double s[3 * GP_THREADS];
+  const int tid = threadIdx.x;
+  double v[3] = {0., 0., 0.};  // sum z^2, sum log L_ii, sum alpha
+  for (int c = 0; c < p; ++c)
+    for (int i = tid; i < n; i += GP_THREADS) {
+      const double z = (double)zt[(size_t)c * ldz + i];
+      v[0] = fma(z, z, v[0]);
+      v[2] += (double)at[(size_t)c * lda + i];
+    }
+  for (int i = tid; i < n; i += GP_THREADS) v[1] += log((double)l[(size_t)i * ld + i]);
+  mll_tree<3>(s, v, tid);
+  if (tid == 0) {
+    const double log_2pi = 1.8378770664093454835606594728112;
+    out[0] = (float)(-0.5 * s[0] - (double)p * s[GP_THREADS] - 0.5 * (double)n * (double)p * log_2pi);
+    out[1] = (float)s[2 * GP_THREADS];
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// The one function that decides the domain (gp_plan's) and the geometry of everything above.
+struct GpMllPlan {
+  int panels, se_route, p_chunks;
+  long trtri_launches, trtri_products, tiles, gram_products, ws_floats;
+};
+
+int gp_mll_plan(int n, int d, int p, GpMllPlan& ml, const char* name) {
+  GP_PLAN_OR_RETURN(pl, n, 1, d, p, name);
+  const long P = pl.panels;
+  ml.panels = pl.panels;
+  ml.se_route = pl.se_route;
+  ml.p_chunks = pg_cdiv(p, GP_KC);
+  ml.trtri_launches = 2 * P - 1;                 // a substitution per panel, an update after every panel but the last
+  ml.trtri_products = (P - 1) * P * (P + 1) / 6;  // sum_k (k + 1)(P - 1 - k)
+  ml.tiles = P * (P + 1) / 2;
+  ml.gram_products = P * (P + 1) * (P + 2) / 6;  // sum_I (I + 1)(P - I)
+  ml.ws_floats = MLL_SUMS * ml.tiles;
+  return 0;
+}
+
+#define GP_MLL_PLAN_OR_RETURN(ml, n, d, p, name)      \
+  GpMllPlan ml;                                       \
+  {                                                   \
+    const int rc__ = gp_mll_plan(n, d, p, ml, name);  \
+    if (rc__) return rc__;                            \
+  }                                                   \
+  (void)ml;
+
+}  // namespace
+
+PG_EXPORT int pg_gp_mll_plan(int n, int d, int p, long long* out, int out_len) {
+  PG_REQUIRE(out && out_len >= PG_GP_MLL_PLAN_INTS, PG_EINVAL, "pg_gp_mll_plan: null pointer or short output array");
+  GP_MLL_PLAN_OR_RETURN(ml, n, d, p, "pg_gp_mll_plan");
+  out[0] = GP_T;
+  out[1] = ml.panels;
+  out[2] = ml.trtri_launches;
+  out[3] = ml.trtri_products;
+  out[4] = ml.tiles;
+  out[5] = ml.gram_products;
+  out[6] = ml.tiles;
+  out[7] = ml.tiles;
+  out[8] = ml.ws_floats;
+  out[9] = ml.se_route;
+  out[10] = GP_SE_DIRECT_D;
+  out[11] = GP_MAX_N;
+  out[12] = GP_MAX_D;
+  out[13] = GP_MAX_P;
+  out[14] = ml.p_chunks;
+  out[15] = 2;
+  return 0;
+}
+
+PG_EXPORT int pg_gp_trtri_t(const float* l, long ld, int n, float* x, long ldx, void* stream) {
+  GP_MLL_PLAN_OR_RETURN(ml, n, 1, 1, "pg_gp_trtri_t");
+  PG_REQUIRE(l && x && ld >= n && ldx >= n, PG_EINVAL, "pg_gp_trtri_t: null pointer or a row stride below the row length");
+  PG_REQUIRE(l != x, PG_EINVAL, "pg_gp_trtri_t: x must not be l (they share the diagonal)");
+  GP_TRY(gp_device("pg_gp_trtri_t"));
+  const hipStream_t st = (hipStream_t)stream;
+  for (int k = 0; k < ml.panels; ++k) {
+    const int j0 = k * GP_T, jb = std::min(GP_T, n - j0), right = ml.panels - 1 - k;
+    hipLaunchKernelGGL(gp_trtri_diag_kernel, dim3((unsigned)(k + 1)), dim3(GP_THREADS), 0, st, l + (size_t)j0 * ld + j0, ld, x + j0, ldx, j0,
+                       jb);
+    PG_LAUNCH_CHECK("pg_gp_trtri_t");
+    if (right > 0) {
+      hipLaunchKernelGGL(gp_trtri_update_kernel, dim3((unsigned)((k + 1) * right)), dim3(GP_THREADS), 0, st, l, ld, x, ldx, n, j0, right);
+      PG_LAUNCH_CHECK("pg_gp_trtri_t");
+    }
+  }
+  return 0;
+}
+
+PG_EXPORT int pg_gp_gram_upper(const float* x, long ldx, int n, float* h, long ldh, int flags, void* stream) {
+  GP_MLL_PLAN_OR_RETURN(ml, n, 1, 1, "pg_gp_gram_upper");
+  PG_REQUIRE(x && h && ldx >= n && ldh >= n, PG_EINVAL, "pg_gp_gram_upper: null pointer or a row stride below the row length");
+  PG_REQUIRE((flags & ~PG_GP_MIRROR) == 0, PG_EINVAL, "pg_gp_gram_upper: flags %d", flags);
+  PG_REQUIRE(x != h, PG_EINVAL, "pg_gp_gram_upper: h must not be x (they share the diagonal)");
+  GP_TRY(gp_device("pg_gp_gram_upper"));
+  hipLaunchKernelGGL(gp_gram_upper_kernel, dim3((unsigned)ml.tiles), dim3(GP_THREADS), 0, (hipStream_t)stream, x, ldx, n, h, ldh,
+                     (flags & PG_GP_MIRROR) != 0);
+  PG_LAUNCH_CHECK("pg_gp_gram_upper");
+  return 0;
+}
+
+PG_EXPORT int pg_gp_se_mll_sums(const float* x, long ldx, int n, int d, float std, float lengthscale, const float* h, long ldh,
+                                const float* alpha_t, long lda, int p, float* ws, size_t ws_floats, float* out, void* stream) {
+  GP_MLL_PLAN_OR_RETURN(ml, n, d, p, "pg_gp_se_mll_sums");
+  PG_REQUIRE(x && h && alpha_t && ws && out, PG_EINVAL, "pg_gp_se_mll_sums: null pointer");
+  PG_REQUIRE(ldx >= d && ldh >= n && lda >= n, PG_EINVAL, "pg_gp_se_mll_sums: a row stride below its row length");
+  PG_REQUIRE(lengthscale > 0.f && std == std && std != 0.f, PG_EINVAL, "pg_gp_se_mll_sums: lengthscale = %g must be > 0, std = %g no NaN and not 0",
+             (double)lengthscale, (double)std);
+  PG_REQUIRE(ws_floats >= (size_t)ml.ws_floats, PG_EINVAL, "pg_gp_se_mll_sums: the workspace holds %zu floats, %ld are needed", ws_floats,
+             ml.ws_floats);
+  GP_TRY(gp_device("pg_gp_se_mll_sums"));
+  const hipStream_t st = (hipStream_t)stream;
+  GpMllSumsArgs a;
+  a.x = x;
+  a.h = h;
+  a.at = alpha_t;
+  a.ws = ws;
+  a.ldx = ldx;
+  a.ldh = ldh;
+  a.lda = lda;
+  a.n = n;
+  a.d = d;
+  a.p = p;
+  a.std2 = std * std;
+  a.neg_inv = -0.5f / (lengthscale * lengthscale);
+  a.pf = (float)p;
+  if (ml.se_route == 0)
+    hipLaunchKernelGGL(gp_se_mll_sums_kernel<0>, dim3((unsigned)ml.tiles), dim3(GP_THREADS), 0, st, a);
+  else
+    hipLaunchKernelGGL(gp_se_mll_sums_kernel<1>, dim3((unsigned)ml.tiles), dim3(GP_THREADS), 0, st, a);
+  PG_LAUNCH_CHECK("pg_gp_se_mll_sums");
+  const double l3 = (double)lengthscale * (double)lengthscale * (double)lengthscale;
+  hipLaunchKernelGGL(gp_mll_finish_kernel, dim3(1), dim3(GP_THREADS), 0, st, (const float*)ws, (int)ml.tiles, 1.0 / (double)std, 0.5 / l3, out);
+  PG_LAUNCH_CHECK("pg_gp_se_mll_sums");
+  return 0;
+}
+
+PG_EXPORT int pg_gp_mll_value(const float* l, long ld, int n, const float* zt, long ldz, const float* alpha_t, long lda, int p, float* out,
+                              void* stream) {
+  GP_MLL_PLAN_OR_RETURN(ml, n, 1, p, "pg_gp_mll_value");
+  PG_REQUIRE(l && zt && alpha_t && out, PG_EINVAL, "pg_gp_mll_value: null pointer");
+  PG_REQUIRE(ld >= n && ldz >= n && lda >= n, PG_EINVAL, "pg_gp_mll_value: a row stride below its row length");
+  GP_TRY(gp_device("pg_gp_mll_value"));
+  hipLaunchKernelGGL(gp_mll_value_kernel, dim3(1), dim3(GP_THREADS), 0, (hipStream_t)stream, l, ld, n, zt, ldz, alpha_t, lda, p, out);
+  PG_LAUNCH_CHECK("pg_gp_mll_value");
+  return 0;
+}

@@ -16,10 +16,19 @@ With K = kernel(train, train) + noise_var I = L L^T, r = y - mean(train), z = L^
 Stated deviations from the reference:
   * Cholesky replaces LU. Where the training covariance is numerically singular (noise_var = 0 on dense data) the reference
     returns noise; this raises torch.linalg.LinAlgError naming the failed pivot.
-  * Outputs carry no gradient, and an input that requires grad raises. Gradients with respect to hyperparameters and a
-    marginal likelihood are not built.
+  * `predict` and `sample` carry no gradient, and an input that requires grad raises: there are no gradients with respect to
+    x or y.
+  * The reference has no marginal likelihood. Here `log_marginal_likelihood()` gives log p(y) of the fitted data from the
+    cached factor, as an autograd node over std, lengthscale, the constant mean and noise_var ("se" route only; one shared
+    lengthscale, no per-dimension ones), and `optimize_hyperparameters()` runs Adam on their logarithms. With
+    G = alpha alpha^T - p K^-1 the gradients are sum G K_f / std, sum G K_f D2 / (2 l^3), tr G / 2 and sum alpha;
+    K^-1 = X X^T comes from the triangular inverse X = L^-T (ops.tri_inverse_t, ops.gram_upper_) and the sums from one fused
+    reduction that writes no derivative matrix (ops.se_mll_sums, csrc/gp_mll.hip). The inverse is made for the call and freed;
+    it is not appended to after a `fit`.
   * `sample` draws on the GPU from torch's generator and returns fp32 on the device (the reference: float64 from numpy).
 SquaredExponential and Const restate the two callables the reference defines only in its notebook."""
+
+import math
 
 import torch
 from torch import nn
@@ -78,6 +87,24 @@ class Const(nn.Module):
 
     def forward(self, x):
         return torch.full((x.shape[0], 1), self.hyperparameters()[0], device=x.device, dtype=torch.float32)
+
+
+class _LogEvidence(torch.autograd.Function):
+    """log p(y) as an autograd node over the hyperparameter tensors that require grad. The forward is handed the value and
+    the gradient vector (d/d value, d/d std, d/d lengthscale, d/d noise_var) the kernels made; `which` names the entry of
+    each tensor. The backward only scales the stored gradients by grad_output."""
+
+    @staticmethod
+    def forward(ctx, value, grads, which, *hypers):
+        ctx.save_for_backward(grads)
+        ctx.targets = [(k, h.shape, h.device, h.dtype) for k, h in zip(which, hypers)]
+        return value.clone()
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        (grads,) = ctx.saved_tensors
+        scaled = grad_output * grads
+        return (None, None, None, *(scaled[k].reshape(shape).to(device=device, dtype=dtype) for k, shape, device, dtype in ctx.targets))
 
 
 class GaussianProcess(base.GenerativeModel):
@@ -266,3 +293,99 @@ class GaussianProcess(base.GenerativeModel):
         z = torch.randn((n_samples, m), device=x.device, dtype=torch.float32, generator=generator)
         out = mu.t().expand(n_samples, m).clone(memory_format=torch.contiguous_format)
         return ops.gemm_nt_(out, z, self._sample_factor, add=True)
+
+    # -- the marginal likelihood -------------------------------------------------------------------------------------------
+    def _hyper_slots(self):
+        """(entry of the gradient vector, owner, attribute, positive) of the four hyperparameters of the "se" route."""
+        return ((0, self.mean, "value", False), (1, self.kernel, "std", True), (2, self.kernel, "lengthscale", True),
+                (3, self, "noise_var", True))
+
+    def _require_evidence(self, what):
+        if self._kernel_route != "se":
+            raise NotImplementedError(f"{what}: built for a SquaredExponential kernel with a Const mean only; a callable kernel or mean "
+                                      "has no marginal-likelihood kernels here")
+        if self.train_x is None:
+            raise ValueError(f"{what}: no training data; call fit first")
+
+    @torch.no_grad()
+    def _evidence(self, want_grads):
+        """(log p(y), gradients): a 0-dim fp32 tensor on the device and, if want_grads, the 1-D tensor (d/d value, d/d std,
+        d/d lengthscale, d/d noise_var), else None. The value alone is one launch on the cached factor; the gradients add the
+        triangular inverse, X X^T and the fused reduction, in two (n, n) workspaces that live for this call only."""
+        self._ensure_factor()
+        n = self.train_y.shape[0]
+        lower, zt, alpha_t = self._factor[:n, :n], self._zt[:, :n], self._alpha_t[:, :n]
+        out = torch.empty(5, device=self.train_x.device, dtype=torch.float32)
+        ops.mll_value(lower, zt, alpha_t, out=out[:2])
+        if not want_grads:
+            return out[0], None
+        std, lengthscale = self.kernel.hyperparameters()
+        inverse_t = torch.empty((n, n), device=out.device, dtype=torch.float32)
+        precision = torch.empty((n, n), device=out.device, dtype=torch.float32)
+        ops.tri_inverse_t(lower, out=inverse_t)
+        ops.gram_upper_(precision, inverse_t)
+        del inverse_t
+        ops.se_mll_sums(self.train_x, std, lengthscale, precision, alpha_t, out=out[2:])
+        return out[0], out[1:]
+
+    def log_marginal_likelihood(self):
+        """log p(y) of the fitted data under the current hyperparameters, a 0-dim fp32 tensor on the GPU, from the cached
+        factor (made or appended to first, as in `predict`: the same error for a covariance that is not positive definite, the
+        same one host synchronisation, none with an unchanged factor).
+
+        With grad enabled the result is an autograd node over those of kernel.std, kernel.lengthscale, mean.value and
+        noise_var that are tensors requiring grad (noise_var is a buffer: `gp.noise_var.requires_grad_()` opts it in; a
+        hyperparameter held as a Python float gets no gradient). The forward then also makes the gradients — the inverse of the
+        factor, K^-1 and the fused reduction, O(n^3) and two (n, n) workspaces that are freed before it returns — and the
+        backward only scales them by grad_output. Under no_grad, or when nothing requires grad, the value alone is computed.
+        No gradients with respect to x or y. "se" route only: NotImplementedError for a callable kernel or mean."""
+        self._require_evidence("log_marginal_likelihood")
+        wanted = []
+        if torch.is_grad_enabled():
+            for k, owner, name, _ in self._hyper_slots():
+                t = getattr(owner, name)
+                if torch.is_tensor(t) and t.requires_grad:
+                    wanted.append((k, t))
+        value, grads = self._evidence(bool(wanted))
+        if not wanted:
+            return value.clone()
+        return _LogEvidence.apply(value, grads, [k for k, _ in wanted], *[t for _, t in wanted])
+
+    def optimize_hyperparameters(self, n_steps=50, lr=0.05, learn_noise=True, learn_mean=True):
+        """n_steps of torch.optim.Adam ascending log p(y) on log std, log lengthscale, log noise_var (when learn_noise and
+        noise_var > 0) and the constant mean (when learn_mean); the positive ones by the chain rule theta d/d theta. Only
+        hyperparameters held as tensors are learned (a Python float stays as it is), whether or not they require grad. After
+        each step the new values are written back in place, which the cached factor sees: the next evaluation, and a `predict`
+        afterwards, factor the covariance afresh (`_factor_route == "full"`). Returns the list of the values of log p(y) seen,
+        one per step, each from before its step."""
+        self._require_evidence("optimize_hyperparameters")
+        learned = []
+        for k, owner, name, positive in self._hyper_slots():
+            if not torch.is_tensor(getattr(owner, name)):
+                continue
+            if (name == "noise_var" and not (learn_noise and _host_value(owner, name) > 0)) or (name == "value" and not learn_mean):
+                continue
+            start = _host_value(owner, name)
+            if positive and not start > 0:
+                raise ValueError(f"optimize_hyperparameters: {name} = {start:g} must be > 0 to be learned on its logarithm")
+            learned.append((k, owner, name, positive, start))
+        if not learned or n_steps < 1:
+            return []
+        dev = self.train_x.device
+        phi = torch.tensor([math.log(s) if pos else s for *_, pos, s in learned], device=dev, dtype=torch.float32, requires_grad=True)
+        entries = torch.tensor([k for k, *_ in learned], device=dev)
+        positive = torch.tensor([pos for *_, pos, _ in learned], device=dev)
+        optimizer = torch.optim.Adam([phi], lr=lr)
+        seen = []
+        for _ in range(n_steps):
+            value, grads = self._evidence(True)
+            with torch.no_grad():
+                theta = torch.where(positive, phi.exp(), phi)
+                phi.grad = -grads[entries] * torch.where(positive, theta, torch.ones_like(theta))
+            optimizer.step()
+            with torch.no_grad():
+                theta = torch.where(positive, phi.exp(), phi)
+                for j, (_, owner, name, _, _) in enumerate(learned):
+                    getattr(owner, name).copy_(theta[j])  # in place: bumps _version, so _host_value and the factor key see it
+            seen.append(value)
+        return torch.stack(seen).tolist()

@@ -256,4 +256,11 @@ from pytorch_generative_amd.ops.gp import (  # noqa: F401
     gemm_nt_,
     cholesky_,
     trsm_right_,
+    GP_MLL_PLAN_INTS,
+    gp_mll_plan_status,
+    gp_mll_plan,
+    tri_inverse_t,
+    gram_upper_,
+    se_mll_sums,
+    mll_value,
 )

@@ -2,6 +2,8 @@
 blocked fp32 Cholesky factorisation that can be appended to, the triangular solves X L^T = B and X L = B, and the strided GEMM
 update C = C -/+ A B^T. Every operand is a 2-D fp32 tensor whose rows are contiguous and whose row stride may be larger than
 its row (a view of a larger buffer is an operand as it lies). Functions ending in an underscore work in place. No gradients.
+The second half works on csrc/gp_mll.hip: the triangular inverse of a factor, the product that turns it into K^-1, and the
+reductions that give the log marginal likelihood and its gradients with respect to the hyperparameters as numbers on the device.
 
 Part of the operator layer (pytorch_generative_amd.ops): HIP kernels called through the C-ABI with tensor.data_ptr() and the
 current stream. No CPU / ATen fallback: a missing library, a CPU tensor or a shape outside ops.gp_plan raises."""
@@ -162,3 +164,127 @@ def trsm_right_(l, x, col_done=0, transposed=False):
     _lib.check(_lib.load().pg_gp_trsm_right(l.data_ptr(), ld, l.shape[0], x.data_ptr(), ldx, x.shape[0], int(col_done),
                                             int(bool(transposed)), _stream()), "pg_gp_trsm_right")
     return x
+
+
+# ---------------------------------------------------------------------------------------------
+# the log marginal likelihood and its hyperparameter gradients (csrc/gp_mll.hip)
+GP_MLL_PLAN_INTS = 16  # PG_GP_MLL_PLAN_INTS
+_MLL_PLAN_FIELDS = ("tile", "panels", "inverse_launches", "inverse_tile_products", "gram_tiles", "gram_tile_products", "sums_tiles",
+                    "sums_partial_rows", "workspace_floats", "se_route", "se_direct_max_d", "max_n", "max_d", "max_p", "outer_k_chunks",
+                    "sums_launches")
+
+
+def gp_mll_plan_status(n, d, p):
+    """(status, plan): the C-ABI status of pg_gp_mll_plan (0, PG_ESHAPE = -2, PG_EINVAL = -1) and the plan dict (None on error)."""
+    out = (ctypes.c_longlong * GP_MLL_PLAN_INTS)()
+    rc = _lib.load().pg_gp_mll_plan(int(n), int(d), int(p), out, GP_MLL_PLAN_INTS)
+    return rc, (None if rc else dict(zip(_MLL_PLAN_FIELDS, out)))
+
+
+def gp_mll_plan(n, d, p):
+    """The planner's answer (pg_gp_mll_plan, host only) for the marginal likelihood of n training rows with d input columns and p
+    columns of y: None for a problem it refuses (the domain of gp_plan), else a dict with the tile edge, the panels of n, the
+    launches and the 64x64x64 tile-products of the triangular inverse, the tiles and the tile-products of X X^T, the tiles and
+    the partial rows of the reduction, the workspace floats se_mll_sums needs, the covariance route of the reduction (as
+    se_kernel's) and its threshold, the domain's edges, the k chunks of the in-kernel outer product (every p takes that route)
+    and the launches of the reduction."""
+    return gp_mll_plan_status(n, d, p)[1]
+
+
+def _vec(t, size, name, at_least=False):
+    """A contiguous 1-D fp32 vector of `size` elements (or more, with at_least) on the current GPU."""
+    if t.dim() != 1 or (t.numel() < size if at_least else t.numel() != size):
+        raise ValueError(f"{name}: expected a 1-D tensor of {'at least ' if at_least else ''}{size} floats, got shape {tuple(t.shape)}")
+    if t.requires_grad:
+        raise ValueError(f"{name}: the Gaussian-process operators build no gradients (requires_grad is set)")
+    _chk(t[:1], name)
+    if t.numel() > 1 and t.stride(0) != 1:
+        raise ValueError(f"{name}: must be contiguous (stride {t.stride(0)})")
+    return t
+
+
+def _square(t, name):
+    t, ld = _mat(t, name)
+    if t.shape[0] != t.shape[1]:
+        raise ValueError(f"{name}: expected a square matrix, got {tuple(t.shape)}")
+    return t, ld
+
+
+def tri_inverse_t(l, out=None):
+    """X = l^-T for the lower-triangular l (n, n), into the UPPER triangle of `out` (diagonal included; any row stride), which is
+    returned. The strict lower triangle of `out` and the strict upper triangle of l are neither read nor written; without `out`
+    a zeroed matrix is made, so the result is the triangular matrix itself. The right-looking solve of X l^T = I in panels of
+    64 columns, restricted to the rows above each panel's end (the others are zero): about n^3 / 3 flops, 2 panels - 1
+    launches (ops.gp_mll_plan), capturable, bit-identical from run to run."""
+    l, ld = _square(l, "tri_inverse_t.l")
+    n = l.shape[0]
+    if out is None:
+        out = torch.zeros((n, n), device=l.device, dtype=torch.float32)
+    out, ldx = _square(out, "tri_inverse_t.out")
+    if out.shape[0] != n:
+        raise ValueError(f"tri_inverse_t: out of shape {tuple(out.shape)}, expected {(n, n)}")
+    _lib.check(_lib.load().pg_gp_trtri_t(l.data_ptr(), ld, n, out.data_ptr(), ldx, _stream()), "pg_gp_trtri_t")
+    return out
+
+
+def gram_upper_(h, x, *, mirror=False):
+    """h = x x^T for the UPPER-triangular x (n, n) — its strict lower triangle is not read — on the lower triangle of h (n, n),
+    diagonal included, in place; mirror=True writes h[j, i] = h[i, j] as well. Returns h. Only the tiles on or below the
+    diagonal are visited and tile (I, J) starts its k loop at row tile I, where x's rows begin: about n^3 / 3 flops. Each
+    element is one fmaf chain in ascending k (no k-split). One launch, capturable, bit-identical from run to run."""
+    h, ldh = _square(h, "gram_upper_.h")
+    x, ldx = _square(x, "gram_upper_.x")
+    if h.shape[0] != x.shape[0]:
+        raise ValueError(f"gram_upper_: h {tuple(h.shape)} and x {tuple(x.shape)} do not fit")
+    _lib.check(_lib.load().pg_gp_gram_upper(x.data_ptr(), ldx, x.shape[0], h.data_ptr(), ldh, GP_MIRROR if mirror else 0, _stream()),
+               "pg_gp_gram_upper")
+    return h
+
+
+def se_mll_sums(x, std, lengthscale, h, alpha_t, *, out=None, workspace=None):
+    """The contraction of G = alpha alpha^T - p h with the squared-exponential covariance K_f of the rows of x (n, d) and its
+    derivatives, for h (n, n) = K^-1 (only its lower triangle is read) and alpha_t (p, n): the 1-D tensor
+        (sum_ij G_ij K_f,ij / std,  sum_ij G_ij K_f,ij |x_i - x_j|^2 / (2 lengthscale^3),  tr G / 2)
+    on the GPU, into `out` (3 floats) if given — the gradients of the log marginal likelihood with respect to std, lengthscale
+    and noise_var. One workgroup per 64 x 64 tile on or below the diagonal recomputes the distances (se_kernel's routes and
+    bits), so neither K_f, its derivative nor G is written to memory; `workspace` (ops.gp_mll_plan's workspace_floats, made if
+    not given) takes one fp32 partial row per tile, which a second launch adds in double in a fixed order. No atomics:
+    bit-identical from run to run. Two launches, capturable."""
+    x, ldx = _mat(x, "se_mll_sums.x")
+    h, ldh = _square(h, "se_mll_sums.h")
+    alpha_t, lda = _mat(alpha_t, "se_mll_sums.alpha_t")
+    n, d = x.shape
+    p = alpha_t.shape[0]
+    if h.shape[0] != n or alpha_t.shape[1] != n:
+        raise ValueError(f"se_mll_sums: x {tuple(x.shape)}, h {tuple(h.shape)} and alpha_t {tuple(alpha_t.shape)} do not fit")
+    rc, plan = gp_mll_plan_status(n, d, p)
+    _lib.check(rc, "se_mll_sums")
+    if workspace is None:
+        workspace = torch.empty(plan["workspace_floats"], device=x.device, dtype=torch.float32)
+    workspace = _vec(workspace, plan["workspace_floats"], "se_mll_sums.workspace", at_least=True)
+    if out is None:
+        out = torch.empty(3, device=x.device, dtype=torch.float32)
+    out = _vec(out, 3, "se_mll_sums.out")
+    _lib.check(_lib.load().pg_gp_se_mll_sums(x.data_ptr(), ldx, n, d, float(std), float(lengthscale), h.data_ptr(), ldh, alpha_t.data_ptr(),
+                                             lda, p, workspace.data_ptr(), workspace.numel(), out.data_ptr(), _stream()),
+               "pg_gp_se_mll_sums")
+    return out
+
+
+def mll_value(l, zt, alpha_t, *, out=None):
+    """(log p(y), sum alpha) as a 1-D tensor of 2 floats on the GPU (into `out` if given) from the lower factor l (n, n) of the
+    training covariance, zt (p, n) = (l^-1 r)^T and alpha_t (p, n) = (l^-T l^-1 r)^T:
+    log p(y) = -1/2 sum zt^2 - p sum_i log l_ii - (n p / 2) log 2 pi. One workgroup, double accumulators, a fixed order."""
+    l, ld = _square(l, "mll_value.l")
+    zt, ldz = _mat(zt, "mll_value.zt")
+    alpha_t, lda = _mat(alpha_t, "mll_value.alpha_t")
+    n = l.shape[0]
+    p = zt.shape[0]
+    if zt.shape[1] != n or tuple(alpha_t.shape) != (p, n):
+        raise ValueError(f"mll_value: l {tuple(l.shape)}, zt {tuple(zt.shape)} and alpha_t {tuple(alpha_t.shape)} do not fit")
+    if out is None:
+        out = torch.empty(2, device=l.device, dtype=torch.float32)
+    out = _vec(out, 2, "mll_value.out")
+    _lib.check(_lib.load().pg_gp_mll_value(l.data_ptr(), ld, n, zt.data_ptr(), ldz, alpha_t.data_ptr(), lda, p, out.data_ptr(), _stream()),
+               "pg_gp_mll_value")
+    return out
