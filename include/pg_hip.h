@@ -654,6 +654,51 @@ int pg_gp_mll_value(const float* l, long ld, int n, const float* zt, long ldz, c
                     void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Stationary kernels with per-dimension (ARD) lengthscales (csrc/gp.hip, csrc/gp_mll.hip). With w_c = 1 / l_c, s_c = a_c - b_c
+ * and r^2 = sum_c (s_c w_c)^2 the covariance is k(a, b) = std^2 phi(r), and omega = -phi'(r) / r is finite at r = 0:
+ *     PG_GP_KIND_SE        phi = exp(-r^2 / 2)                               omega = exp(-r^2 / 2)
+ *     PG_GP_KIND_MATERN32  phi = (1 + sqrt(3) r) exp(-sqrt(3) r)             omega = 3 exp(-sqrt(3) r)
+ *     PG_GP_KIND_MATERN52  phi = (1 + sqrt(5) r + 5 r^2 / 3) exp(-sqrt(5) r) omega = (5 / 3)(1 + sqrt(5) r) exp(-sqrt(5) r)
+ * so that d k / d l_c = std^2 omega(r) s_c^2 / l_c^3 and, with G = alpha alpha^T - p K^-1 as above,
+ *     d/d l_c = S_c / (2 l_c),  S_c = sum_ij G_ij std^2 omega(r_ij) ((x_ic - x_jc) w_c)^2;   shared l: sum_ij G_ij std^2 omega r^2 / (2 l).
+ * Any other kind is PG_EINVAL. Status conventions as above.
+ *   stat_kernel:   pg_gp_se_kernel's arguments, flags, routes (pg_gp_plan decides) and promises — the diagonal exactly
+ *                  std^2 + noise_var, an element's bits a function of its two rows and of w alone — plus the kind and inv_ls, a
+ *                  DEVICE pointer to the d floats w_c. inv_ls == NULL: the shared scalar `lengthscale` is used (kind SE is then
+ *                  pg_gp_se_kernel itself, bit for bit); otherwise the scalar is ignored. Route 0 forms (a_c - b_c) w_c, the
+ *                  difference first: inputs far from the origin lose nothing and a duplicated row gives r = 0, phi = 1 exactly.
+ *                  Route 1 scales the rows by w WHILE STAGING them into LDS (no extra launch, no scaled copy of the rows) and
+ *                  clamps the squared distance at 0 before the square root.
+ *   stat_mll_sums: pg_gp_se_mll_sums for any kind with one shared lengthscale, same arguments, domain and outputs; kind SE is
+ *                  pg_gp_se_mll_sums itself, bit for bit. The other kinds sum G std^2 omega r^2 directly.
+ *   ard_mll_sums:  out[0 .. d + 2) = d/d std, d/d noise_var, d/d l_0 .. d/d l_{d-1}. One workgroup per 64 x 64 tile on or below
+ *                  the diagonal forms G in registers (alpha_i . alpha_j on the MFMA for every p, only the lower triangle of h is
+ *                  read, off-diagonal elements count twice). The per-dimension terms are exact differences on the VALU for
+ *                  every d of the domain: the rows of x go through LDS in chunks of at most 64 columns, twice — first for r^2
+ *                  (the ascending-c sum of the squares; not the bits of stat_kernel's route 1), then for the sums — once if
+ *                  d <= 64. A workgroup writes one partial row of d + 2 fp32 values into ws (ws_floats >= plan[3]); a second
+ *                  launch of d + 2 workgroups adds each column in double — thread t the tiles t, t + 256, ... ascending, then
+ *                  the fixed tree — and applies 1 / std, 1 / 2 and 1 / (2 l_c). std != 0.
+ * pg_gp_ard_plan (host only) is the one function that decides the domain of ard_mll_sums: that of pg_gp_mll_plan and d <= 256
+ * (PG_ESHAPE above: the VALU term count is n^2 d / 2). It fills out[0 .. PG_GP_ARD_PLAN_INTS): [0] the tile edge, [1] the tiles
+ * and partial rows, [2] the floats of a partial row (d + 2), [3] the workspace floats ([1] x [2]), [4] the column chunks of x,
+ * [5] the launches (2), [6] the largest d, [7] the columns of a chunk.
+ * No float atomics, nothing of size (n, n) written, no allocation, no host synchronisation (capturable), bit-identical from run
+ * to run.
+ * ------------------------------------------------------------------------------------- */
+#define PG_GP_KIND_SE 0
+#define PG_GP_KIND_MATERN32 1
+#define PG_GP_KIND_MATERN52 2
+#define PG_GP_ARD_PLAN_INTS 8
+int pg_gp_stat_kernel(int kind, const float* a, long lda, int n, const float* b, long ldb, int m, int d, float std, float lengthscale,
+                      const float* inv_ls, float noise_var, float* k, long ldk, int diag_off, int flags, void* stream);
+int pg_gp_stat_mll_sums(int kind, const float* x, long ldx, int n, int d, float std, float lengthscale, const float* h, long ldh,
+                        const float* alpha_t, long lda, int p, float* ws, size_t ws_floats, float* out, void* stream);
+int pg_gp_ard_plan(int n, int d, int p, long long* out, int out_len);
+int pg_gp_ard_mll_sums(int kind, const float* x, long ldx, int n, int d, float std, const float* inv_ls, const float* h, long ldh,
+                       const float* alpha_t, long lda, int p, float* ws, size_t ws_floats, float* out, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Density estimators (models/mixture_models.py, models/kde.py) on streaming log-density kernels (density.hip):
  * the pairwise log-density c[n][k] = sum_d f(x[n][d], theta[k][d]) is one or two fp32-MFMA GEMMs plus a per-column
  * constant, reduced by a running logsumexp over column tiles; nothing of size N x K (x F) is written to memory.

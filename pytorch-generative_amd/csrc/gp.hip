@@ -18,6 +18,11 @@
 // No float atomics, each output element is owned by one lane, every order is fixed by the shape: bit-identical from run to
 // run. No host synchronisation and no allocation: capturable. gp_plan is the one function that decides the domain and the
 // geometry; every entry point calls it, and reports a missing device only after it accepted the problem.
+//
+// Stationary kernels. The covariance kernels are templated on the kind (squared exponential, Matern 3/2, Matern 5/2) and on
+// per-dimension (ARD) lengthscales w_c = 1 / l_c; pg_gp_se_kernel is the <SE, shared lengthscale> instantiation, unchanged. With
+// ARD the exact-difference route forms (a_c - b_c) w_c and the MFMA route SCALES THE ROWS WHILE STAGING them into LDS
+// (gp_mma_tile's SCALE): one launch either way, no scaled copy of the rows, an element's bits depend on its two rows and w alone.
 #include "gp_common.h"
 
 namespace {
@@ -56,8 +61,12 @@ __global__ void __launch_bounds__(GP_THREADS) gp_gemm_kernel(const GpGemmArgs p)
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
-// Squared-exponential covariance K[i][j] = std^2 exp(-|a_i - b_j|^2 / (2 l^2)): neg_inv = -1 / (2 l^2) and std2 come from the
-// host. lower / mirror as in the GEMM; diag: elements with j == i + diag_off are written as exactly diag_val.
+// Stationary covariance K[i][j] = std^2 phi(r) (gp_common.h), templated on the kind and on ARD. The squared-exponential kernel
+// with one shared lengthscale, <PG_GP_KIND_SE, false>, is K[i][j] = std^2 exp(-|a_i - b_j|^2 / (2 l^2)) as it always was:
+// neg_inv = -1 / (2 l^2) and std2 come from the host. The other shared-lengthscale kinds take r^2 = |a_i - b_j|^2 inv_l2; with
+// ARD the distances arrive scaled by w = 1 / l per column (the exact-difference route forms (a_c - b_c) w_c, difference first;
+// the MFMA route SCALES THE ROWS WHILE STAGING them into LDS: no extra launch, no scaled copy of the rows kept anywhere).
+// lower / mirror as in the GEMM; diag: elements with j == i + diag_off are written as exactly diag_val.
 struct GpSeArgs {
   const float* a;
   const float* b;
@@ -65,20 +74,33 @@ struct GpSeArgs {
   long lda, ldb, ldk;
   int n, m, d, diag_off, lower, mirror, diag, col_tiles;
   float std2, neg_inv, diag_val;
+  const float* w;
+  float inv_l2;
 };
 
+template <int KIND, bool ARD>
 __device__ __forceinline__ void gp_se_store(const GpSeArgs& p, int gr, int gc, float sq) {
   if (!(gr < p.n && gc < p.m && (!p.lower || gc <= gr + p.diag_off))) return;
-  float v = p.std2 * expf(sq * p.neg_inv);
+  float v;
+  if (KIND == PG_GP_KIND_SE && !ARD) {
+    v = p.std2 * expf(sq * p.neg_inv);
+  } else {
+    float phi, omega;
+    gp_stat_phi_omega<KIND>(ARD ? sq : sq * p.inv_l2, phi, omega);
+    v = p.std2 * phi;
+  }
   if (p.diag && gc == gr + p.diag_off) v = p.diag_val;
   p.k[(size_t)gr * p.ldk + gc] = v;
   if (p.mirror && gc != gr) p.k[(size_t)gc * p.ldk + gr] = v;
 }
 
 // exact differences sum_k (a_ik - b_jk)^2 on the VALU, k ascending; d <= 64. A thread owns 4 x 4 elements of the tile.
+// ARD: sum_k ((a_ik - b_jk) w_k)^2.
+template <int KIND, bool ARD>
 __global__ void __launch_bounds__(GP_THREADS) gp_se_direct_kernel(const GpSeArgs p) {
   __shared__ float s_a[GP_T * GP_TRI_LD];
   __shared__ float s_b[GP_T * GP_TRI_LD];
+  __shared__ float s_w[ARD ? GP_SE_DIRECT_MAX_D : 1];
   const int r0 = (blockIdx.x / p.col_tiles) * GP_T, c0 = (blockIdx.x % p.col_tiles) * GP_T;
   if (p.lower && c0 > r0 + (GP_T - 1) + p.diag_off) return;
   const int tid = threadIdx.x;
@@ -87,6 +109,7 @@ __global__ void __launch_bounds__(GP_THREADS) gp_se_direct_kernel(const GpSeArgs
     s_a[r * GP_TRI_LD + k] = r0 + r < p.n ? p.a[(size_t)(r0 + r) * p.lda + k] : 0.f;
     s_b[r * GP_TRI_LD + k] = c0 + r < p.m ? p.b[(size_t)(c0 + r) * p.ldb + k] : 0.f;
   }
+  if (ARD && tid < p.d) s_w[tid] = p.w[tid];
   __syncthreads();
   const int tx = tid & 15, ty = tid >> 4;
   float sq[4][4];
@@ -96,6 +119,7 @@ __global__ void __launch_bounds__(GP_THREADS) gp_se_direct_kernel(const GpSeArgs
     for (int j = 0; j < 4; ++j) sq[i][j] = 0.f;
   for (int k = 0; k < p.d; ++k) {
     float av[4], bv[4];
+    const float wk = ARD ? s_w[k] : 1.f;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       av[i] = s_a[(ty + 16 * i) * GP_TRI_LD + k];
@@ -105,17 +129,20 @@ __global__ void __launch_bounds__(GP_THREADS) gp_se_direct_kernel(const GpSeArgs
     for (int i = 0; i < 4; ++i)
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const float df = av[i] - bv[j];
+        float df = av[i] - bv[j];
+        if (ARD) df *= wk;
         sq[i][j] = fmaf(df, df, sq[i][j]);
       }
   }
 #pragma unroll
   for (int i = 0; i < 4; ++i)
 #pragma unroll
-    for (int j = 0; j < 4; ++j) gp_se_store(p, r0 + ty + 16 * i, c0 + tx + 16 * j, sq[i][j]);
+    for (int j = 0; j < 4; ++j) gp_se_store<KIND, ARD>(p, r0 + ty + 16 * i, c0 + tx + 16 * j, sq[i][j]);
 }
 
-// |a|^2 + |b|^2 - 2 a.b with the cross term on the MFMA, clamped at 0 before the exp
+// |a|^2 + |b|^2 - 2 a.b with the cross term on the MFMA, clamped at 0 before the exp (and the square root). ARD: of the rows
+// scaled by w on their way into LDS.
+template <int KIND, bool ARD>
 __global__ void __launch_bounds__(GP_THREADS) gp_se_mfma_kernel(const GpSeArgs p) {
   __shared__ float s_a[GP_T * GP_LD];
   __shared__ float s_b[GP_T * GP_LD];
@@ -132,15 +159,16 @@ __global__ void __launch_bounds__(GP_THREADS) gp_se_mfma_kernel(const GpSeArgs p
   m.R = p.n;
   m.C = p.m;
   m.K = p.d;
+  m.w = p.w;
   pg_tile::Acc<GP_V> acc;
   pg_tile::zero<GP_V>(acc);
   float norm = 0.f;
-  gp_mma_tile<true, false, true>(m, r0, c0, s_a, s_b, ln, acc, norm);
+  gp_mma_tile<true, false, true, ARD>(m, r0, c0, s_a, s_b, ln, acc, norm);
   if (threadIdx.x < 2 * GP_T) s_n[threadIdx.x] = norm;
   __syncthreads();
   PG_TILE_FOR_EACH_OUTPUT(GP_V, ln, r, c) {
     const float sq = fmaf(-2.f, PG_TILE_OUTPUT(acc), s_n[r] + s_n[GP_T + c]);
-    gp_se_store(p, r0 + r, c0 + c, fmaxf(sq, 0.f));
+    gp_se_store<KIND, ARD>(p, r0 + r, c0 + c, fmaxf(sq, 0.f));
   }
 }
 
@@ -324,26 +352,39 @@ PG_EXPORT int pg_gp_plan(int n, int m, int d, int p, long long* out, int out_len
   return 0;
 }
 
-PG_EXPORT int pg_gp_se_kernel(const float* a, long lda, int n, const float* b, long ldb, int m, int d, float std, float lengthscale,
-                              float noise_var, float* k, long ldk, int diag_off, int flags, void* stream) {
-  GP_PLAN_OR_RETURN(pl, n, m, d, 1, "pg_gp_se_kernel");
-  PG_REQUIRE(a && b && k, PG_EINVAL, "pg_gp_se_kernel: null pointer");
-  PG_REQUIRE(lda >= d && ldb >= d && ldk >= m, PG_EINVAL, "pg_gp_se_kernel: a row stride below its row length");
-  PG_REQUIRE(lengthscale > 0.f && std == std && noise_var == noise_var, PG_EINVAL,
-             "pg_gp_se_kernel: lengthscale = %g must be > 0, std and noise_var no NaN", (double)lengthscale);
+namespace {
+
+template <int KIND, bool ARD>
+void gp_stat_launch(int route, dim3 grid, hipStream_t st, const GpSeArgs& p) {
+  if (route == 0)
+    hipLaunchKernelGGL((gp_se_direct_kernel<KIND, ARD>), grid, dim3(GP_THREADS), 0, st, p);
+  else
+    hipLaunchKernelGGL((gp_se_mfma_kernel<KIND, ARD>), grid, dim3(GP_THREADS), 0, st, p);
+}
+
+// the one launch path of pg_gp_se_kernel (kind SE, inv_ls NULL) and pg_gp_stat_kernel
+int gp_stat_kernel(const char* name, int kind, const float* a, long lda, int n, const float* b, long ldb, int m, int d, float std,
+                   float lengthscale, const float* inv_ls, float noise_var, float* k, long ldk, int diag_off, int flags, void* stream) {
+  GP_PLAN_OR_RETURN(pl, n, m, d, 1, name);
+  PG_REQUIRE(kind == PG_GP_KIND_SE || kind == PG_GP_KIND_MATERN32 || kind == PG_GP_KIND_MATERN52, PG_EINVAL, "%s: kind %d is none of PG_GP_KIND_*",
+             name, kind);
+  PG_REQUIRE(a && b && k, PG_EINVAL, "%s: null pointer", name);
+  PG_REQUIRE(lda >= d && ldb >= d && ldk >= m, PG_EINVAL, "%s: a row stride below its row length", name);
+  PG_REQUIRE((inv_ls || lengthscale > 0.f) && std == std && noise_var == noise_var, PG_EINVAL,
+             "%s: lengthscale = %g must be > 0, std and noise_var no NaN", name, (double)lengthscale);
   const int known = PG_GP_LOWER | PG_GP_MIRROR | PG_GP_DIAG | PG_GP_SE_DIRECT | PG_GP_SE_MFMA;
   PG_REQUIRE((flags & ~known) == 0 && (flags & (PG_GP_SE_DIRECT | PG_GP_SE_MFMA)) != (PG_GP_SE_DIRECT | PG_GP_SE_MFMA), PG_EINVAL,
-             "pg_gp_se_kernel: flags %d", flags);
-  PG_REQUIRE(diag_off > -GP_MAX_N && diag_off < GP_MAX_N, PG_EINVAL, "pg_gp_se_kernel: diag_off = %d", diag_off);
+             "%s: flags %d", name, flags);
+  PG_REQUIRE(diag_off > -GP_MAX_N && diag_off < GP_MAX_N, PG_EINVAL, "%s: diag_off = %d", name, diag_off);
   PG_REQUIRE(!(flags & PG_GP_MIRROR) || ((flags & PG_GP_LOWER) && a == b && lda == ldb && n == m && diag_off == 0), PG_EINVAL,
-             "pg_gp_se_kernel: the mirror takes the symmetric form (a is b, lower, diag_off = 0)");
+             "%s: the mirror takes the symmetric form (a is b, lower, diag_off = 0)", name);
   int route = pl.se_route;
   if (flags & PG_GP_SE_MFMA) route = 1;
   if (flags & PG_GP_SE_DIRECT) {
-    PG_REQUIRE(d <= GP_SE_DIRECT_MAX_D, PG_ESHAPE, "pg_gp_se_kernel: the exact-difference route holds d <= %d, got %d", GP_SE_DIRECT_MAX_D, d);
+    PG_REQUIRE(d <= GP_SE_DIRECT_MAX_D, PG_ESHAPE, "%s: the exact-difference route holds d <= %d, got %d", name, GP_SE_DIRECT_MAX_D, d);
     route = 0;
   }
-  GP_TRY(gp_device("pg_gp_se_kernel"));
+  GP_TRY(gp_device(name));
   GpSeArgs p;
   p.a = a;
   p.b = b;
@@ -360,15 +401,36 @@ PG_EXPORT int pg_gp_se_kernel(const float* a, long lda, int n, const float* b, l
   p.diag = (flags & PG_GP_DIAG) != 0;
   p.col_tiles = pg_cdiv(m, GP_T);
   p.std2 = std * std;
-  p.neg_inv = -0.5f / (lengthscale * lengthscale);
+  p.neg_inv = inv_ls ? -0.5f : -0.5f / (lengthscale * lengthscale);
   p.diag_val = p.std2 + noise_var;
+  p.w = inv_ls;
+  p.inv_l2 = inv_ls ? 1.f : 1.f / (lengthscale * lengthscale);
   const dim3 grid((unsigned)((long)pg_cdiv(n, GP_T) * p.col_tiles));
-  if (route == 0)
-    hipLaunchKernelGGL(gp_se_direct_kernel, grid, dim3(GP_THREADS), 0, (hipStream_t)stream, p);
-  else
-    hipLaunchKernelGGL(gp_se_mfma_kernel, grid, dim3(GP_THREADS), 0, (hipStream_t)stream, p);
-  PG_LAUNCH_CHECK("pg_gp_se_kernel");
+  const hipStream_t st = (hipStream_t)stream;
+  if (inv_ls) {
+    if (kind == PG_GP_KIND_SE) gp_stat_launch<PG_GP_KIND_SE, true>(route, grid, st, p);
+    if (kind == PG_GP_KIND_MATERN32) gp_stat_launch<PG_GP_KIND_MATERN32, true>(route, grid, st, p);
+    if (kind == PG_GP_KIND_MATERN52) gp_stat_launch<PG_GP_KIND_MATERN52, true>(route, grid, st, p);
+  } else {
+    if (kind == PG_GP_KIND_SE) gp_stat_launch<PG_GP_KIND_SE, false>(route, grid, st, p);
+    if (kind == PG_GP_KIND_MATERN32) gp_stat_launch<PG_GP_KIND_MATERN32, false>(route, grid, st, p);
+    if (kind == PG_GP_KIND_MATERN52) gp_stat_launch<PG_GP_KIND_MATERN52, false>(route, grid, st, p);
+  }
+  PG_LAUNCH_CHECK(name);
   return 0;
+}
+
+}  // namespace
+
+PG_EXPORT int pg_gp_se_kernel(const float* a, long lda, int n, const float* b, long ldb, int m, int d, float std, float lengthscale,
+                              float noise_var, float* k, long ldk, int diag_off, int flags, void* stream) {
+  return gp_stat_kernel("pg_gp_se_kernel", PG_GP_KIND_SE, a, lda, n, b, ldb, m, d, std, lengthscale, nullptr, noise_var, k, ldk, diag_off, flags,
+                        stream);
+}
+
+PG_EXPORT int pg_gp_stat_kernel(int kind, const float* a, long lda, int n, const float* b, long ldb, int m, int d, float std, float lengthscale,
+                                const float* inv_ls, float noise_var, float* k, long ldk, int diag_off, int flags, void* stream) {
+  return gp_stat_kernel("pg_gp_stat_kernel", kind, a, lda, n, b, ldb, m, d, std, lengthscale, inv_ls, noise_var, k, ldk, diag_off, flags, stream);
 }
 
 PG_EXPORT int pg_gp_add_diag(float* a, long ld, int n, float value, void* stream) {

@@ -22,19 +22,45 @@ constexpr int GP_MAX_D = 4096;
 constexpr int GP_MAX_P = 4096;
 constexpr int GP_SE_DIRECT_D = 16;      // largest d of the exact-difference route: measured faster up to 16, slower from 32 (profiles/gp.json)
 constexpr int GP_SE_DIRECT_MAX_D = 64;  // largest d the exact-difference kernel holds in LDS when the route is forced
+constexpr int GP_ARD_MAX_D = 256;       // largest d of the per-dimension gradient reduction: n^2 d / 2 terms on the VALU
+constexpr int GP_ARD_CHUNK = 64;        // columns of x it stages per pass
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// The stationary kernels k = std^2 phi(r) (PG_GP_KIND_*): phi and omega = -phi'(r) / r, both finite at r = 0.
+//   SE          phi = exp(-r^2 / 2)                                omega = phi
+//   Matern 3/2  phi = (1 + s) exp(-s), s = sqrt(3) r               omega = 3 exp(-s)
+//   Matern 5/2  phi = (1 + s + s^2 / 3) exp(-s), s = sqrt(5) r     omega = (5 / 3)(1 + s) exp(-s)
+// r2 is the squared scaled distance, >= 0.
+template <int KIND>
+__device__ __forceinline__ void gp_stat_phi_omega(float r2, float& phi, float& omega) {
+  if (KIND == PG_GP_KIND_SE) {
+    phi = omega = expf(-0.5f * r2);
+  } else if (KIND == PG_GP_KIND_MATERN32) {
+    const float s = 1.7320508075688772f * sqrtf(r2), e = expf(-s);
+    phi = (1.f + s) * e;
+    omega = 3.f * e;
+  } else {
+    const float s = 2.2360679774997897f * sqrtf(r2), e = expf(-s);
+    phi = (1.f + s + s * s * (1.f / 3.f)) * e;
+    omega = (5.f / 3.f) * (1.f + s) * e;
+  }
+}
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // The 64 x 64 x K product of one workgroup: acc += (NEG ? -A : A) B^T with A(r, k) = a[r * a_rs + k] and
 // B(c, k) = b[c * b_rs + k * b_ks], on mfma_tile.h's pipeline (BK: B is k-contiguous). Ragged edges are zero-filled. NORMS:
-// thread t < 64 also sums A(r0 + t, k)^2, thread 64 + t B(c0 + t, k)^2, in k order.
+// thread t < 64 also sums A(r0 + t, k)^2, thread 64 + t B(c0 + t, k)^2, in k order. SCALE (BK only): both operands are
+// multiplied by w[k] on the way into LDS (a thread's elements of a chunk share k), so the product and the norms are those of
+// the scaled rows; without it w is not read and nothing changes.
 struct GpMma {
   const float* a;
   const float* b;
   long a_rs, b_rs, b_ks;
   int R, C, K;
+  const float* w = nullptr;
 };
 
-template <bool BK, bool NEG, bool NORMS>
+template <bool BK, bool NEG, bool NORMS, bool SCALE = false>
 __device__ __forceinline__ void gp_mma_tile(const GpMma& p, int r0, int c0, float* s_a, float* s_b, const pg_tile::Lanes<GP_V>& ln,
                                             pg_tile::Acc<GP_V>& acc, float& norm) {
   const int tid = ln.tid;
@@ -42,6 +68,16 @@ __device__ __forceinline__ void gp_mma_tile(const GpMma& p, int r0, int c0, floa
   auto load = [&](int ch) {
     pg_tile::load_operand<GP_V, true, NEG>(ra, p.a, p.a_rs, 1, r0, p.R, ch * GP_KC, p.K, tid);
     pg_tile::load_operand<GP_V, BK>(rb, p.b, p.b_rs, p.b_ks, c0, p.C, ch * GP_KC, p.K, tid);
+    if (SCALE) {
+      static_assert(!SCALE || BK, "the scaled walk is k-contiguous");
+      const int gk = ch * GP_KC + tid % GP_KC;
+      const float wk = gk < p.K ? p.w[gk] : 0.f;
+#pragma unroll
+      for (int j = 0; j < GP_T * GP_KC / GP_THREADS; ++j) {
+        ra[j] *= wk;
+        rb[j] *= wk;
+      }
+    }
   };
   auto store = [&]() {
     pg_tile::store_operand<GP_V, true>(s_a, ra, tid);

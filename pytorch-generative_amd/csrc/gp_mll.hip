@@ -19,6 +19,10 @@
 //     three sums in a fixed order — lane (16 elements in the order of PG_TILE_FOR_EACH_OUTPUT), wave (shuffle tree), the four
 //     waves in order — to one fp32 partial row per tile. gp_mll_finish_kernel adds the rows in double: thread t the tiles t,
 //     t + 256, ... ascending, then a fixed tree over the 256 threads.
+//   * pg_gp_stat_mll_sums is the same reduction for the other stationary kinds with one shared lengthscale (the kind is a
+//     template parameter; pg_gp_se_mll_sums is the SE instantiation), and pg_gp_ard_mll_sums the one for per-dimension
+//     lengthscales: d + 2 sums per tile, the per-dimension terms by exact differences on the VALU in two passes over the
+//     column chunks of x (gp_ard_mll_sums_kernel); gp_ard_plan decides its domain (d <= 256).
 // No float atomics, no host synchronisation, no allocation: capturable, bit-identical from run to run. gp_mll_plan is the one
 // function that decides domain and geometry; every entry point calls it and reports a missing device only afterwards.
 #include "gp_common.h"
@@ -175,9 +179,31 @@ struct GpMllSumsArgs {
   long ldx, ldh, lda;
   int n, d, p;
   float std2, neg_inv, pf;
+  float inv_l2;    // the shared-lengthscale kinds other than SE: r^2 = D2 inv_l2
+  const float* w;  // the ARD reduction: 1 / l per column
 };
 
-template <int ROUTE>
+// g = alpha_i . alpha_j over the p columns of y for the tile at (r0, c0), on the MFMA for every p.
+__device__ __forceinline__ void mll_alpha_outer(const GpMllSumsArgs& p, int r0, int c0, float* s_a, float* s_b, const pg_tile::Lanes<GP_V>& ln,
+                                                pg_tile::Acc<GP_V>& g) {
+  const int tid = ln.tid;
+  pg_tile::zero<GP_V>(g);
+  pg_tile::Regs<GP_V> ra, rb;
+  auto load = [&](int ch) {
+    pg_tile::load_operand<GP_V, false>(ra, p.at, 1, p.lda, r0, p.n, ch * GP_KC, p.p, tid);
+    pg_tile::load_operand<GP_V, false>(rb, p.at, 1, p.lda, c0, p.n, ch * GP_KC, p.p, tid);
+  };
+  auto store = [&]() {
+    pg_tile::store_operand<GP_V, false>(s_a, ra, tid);
+    pg_tile::store_operand<GP_V, false>(s_b, rb, tid);
+  };
+  auto none = [](int) {};
+  PG_TILE_PIPELINE(GP_V, false, 0, (p.p + GP_KC - 1) / GP_KC, load, store, g, s_a, s_b, ln, none);
+}
+
+// KIND = PG_GP_KIND_SE is the reduction as it always was (sum G K_f, sum G K_f D2, tr G; the finish applies 1 / (2 l^3)). The
+// Matern kinds take K_f = std^2 phi(r) and accumulate G std^2 omega(r) r^2 as the second sum (the finish applies 1 / (2 l)).
+template <int ROUTE, int KIND>
 __global__ void __launch_bounds__(GP_THREADS) gp_se_mll_sums_kernel(const GpMllSumsArgs p) {
   __shared__ float s_a[GP_T * GP_LD];
   __shared__ float s_b[GP_T * GP_LD];
@@ -191,20 +217,7 @@ __global__ void __launch_bounds__(GP_THREADS) gp_se_mll_sums_kernel(const GpMllS
 
   // alpha_i . alpha_j over the p columns of y: alpha^T is (p, n), so both operands are row-contiguous
   pg_tile::Acc<GP_V> g;
-  pg_tile::zero<GP_V>(g);
-  {
-    pg_tile::Regs<GP_V> ra, rb;
-    auto load = [&](int ch) {
-      pg_tile::load_operand<GP_V, false>(ra, p.at, 1, p.lda, r0, p.n, ch * GP_KC, p.p, tid);
-      pg_tile::load_operand<GP_V, false>(rb, p.at, 1, p.lda, c0, p.n, ch * GP_KC, p.p, tid);
-    };
-    auto store = [&]() {
-      pg_tile::store_operand<GP_V, false>(s_a, ra, tid);
-      pg_tile::store_operand<GP_V, false>(s_b, rb, tid);
-    };
-    auto none = [](int) {};
-    PG_TILE_PIPELINE(GP_V, false, 0, (p.p + GP_KC - 1) / GP_KC, load, store, g, s_a, s_b, ln, none);
-  }
+  mll_alpha_outer(p, r0, c0, s_a, s_b, ln, g);
 
   // the squared distances, with the bits of se_kernel's route
   pg_tile::Acc<GP_V> sq;
@@ -263,9 +276,18 @@ __global__ void __launch_bounds__(GP_THREADS) gp_se_mll_sums_kernel(const GpMllS
       sum[2] += gv;
     } else {  // (i, j) and (j, i)
       const float d2 = PG_TILE_OUTPUT(sq);
-      const float t = 2.f * gv * (p.std2 * expf(d2 * p.neg_inv));
-      sum[0] += t;
-      sum[1] = fmaf(t, d2, sum[1]);
+      if (KIND == PG_GP_KIND_SE) {
+        const float t = 2.f * gv * (p.std2 * expf(d2 * p.neg_inv));
+        sum[0] += t;
+        sum[1] = fmaf(t, d2, sum[1]);
+      } else {
+        const float r2 = d2 * p.inv_l2;
+        float phi, omega;
+        gp_stat_phi_omega<KIND>(r2, phi, omega);
+        const float t = 2.f * gv * p.std2;
+        sum[0] = fmaf(t, phi, sum[0]);
+        sum[1] = fmaf(t * omega, r2, sum[1]);
+      }
     }
   }
 #pragma unroll
@@ -278,6 +300,141 @@ __global__ void __launch_bounds__(GP_THREADS) gp_se_mll_sums_kernel(const GpMllS
   if (tid < MLL_SUMS)
     p.ws[(size_t)blockIdx.x * MLL_SUMS + tid] =
         ((s_red[tid] + s_red[MLL_SUMS + tid]) + s_red[2 * MLL_SUMS + tid]) + s_red[3 * MLL_SUMS + tid];
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// The ARD reduction: per tile on or below the diagonal, sum G K_f, tr G and, for every column c of x,
+//     S_c = sum_ij G_ij std^2 omega(r_ij) ((x_ic - x_jc) w_c)^2          (off-diagonal elements twice, the diagonal adds 0).
+// G as above (alpha_i . alpha_j on the MFMA, minus p h from the lower triangle). The per-dimension terms are exact differences
+// on the VALU: the rows of x go through LDS in chunks of at most 64 columns, TWICE — pass 1 sums r^2 = sum_c ((x_ic - x_jc) w_c)^2
+// in ascending c and turns it into the coefficient 2 G std^2 omega(r) of each of a thread's 16 elements (kept in the registers
+// r^2 had), pass 2 forms the squares again and adds coefficient x square per column: 16 elements in the order of
+// PG_TILE_FOR_EACH_OUTPUT, the wave by a shuffle tree, the four waves in order. With one chunk (d <= 64) the rows are staged once.
+// One partial row of d + 2 floats per tile: [sum G K_f, tr G, S_0 .. S_{d-1}].
+constexpr int ARD_LD = GP_ARD_CHUNK + 1;
+
+template <int KIND>
+__global__ void __launch_bounds__(GP_THREADS) gp_ard_mll_sums_kernel(const GpMllSumsArgs p) {
+  __shared__ float s_a[GP_T * GP_LD];
+  __shared__ float s_b[GP_T * GP_LD];
+  __shared__ float s_xa[GP_T * ARD_LD];
+  __shared__ float s_xb[GP_T * ARD_LD];
+  __shared__ float s_w[GP_ARD_CHUNK];
+  __shared__ float s_col[4 * GP_ARD_MAX_D];
+  __shared__ float s_red[4 * 2];
+  int I, J;
+  mll_tri_tile(blockIdx.x, I, J);
+  const int r0 = I * GP_T, c0 = J * GP_T;
+  const pg_tile::Lanes<GP_V> ln;
+  const int tid = ln.tid;
+
+  pg_tile::Acc<GP_V> g;
+  mll_alpha_outer(p, r0, c0, s_a, s_b, ln, g);
+
+  const int chunks = (p.d + GP_ARD_CHUNK - 1) / GP_ARD_CHUNK;
+  auto stage = [&](int k0, int kc) {
+    __syncthreads();  // the readers of the chunk before are done
+    for (int e = tid; e < GP_T * kc; e += GP_THREADS) {
+      const int r = e / kc, k = e % kc;
+      s_xa[r * ARD_LD + k] = r0 + r < p.n ? p.x[(size_t)(r0 + r) * p.ldx + k0 + k] : 0.f;
+      s_xb[r * ARD_LD + k] = c0 + r < p.n ? p.x[(size_t)(c0 + r) * p.ldx + k0 + k] : 0.f;
+    }
+    if (tid < kc) s_w[tid] = p.w[k0 + tid];
+    __syncthreads();
+  };
+  int ra[2][4], rb[2];  // LDS offsets of the rows of x behind a thread's elements
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) ra[i][q] = pg_tile::out_row<GP_V>(ln, i, q) * ARD_LD;
+    rb[i] = pg_tile::out_col<GP_V>(ln, i) * ARD_LD;
+  }
+
+  // pass 1: r^2, then the coefficients
+  pg_tile::Acc<GP_V> sq;
+  pg_tile::zero<GP_V>(sq);
+  for (int ch = 0; ch < chunks; ++ch) {
+    const int k0 = ch * GP_ARD_CHUNK, kc = min(GP_ARD_CHUNK, p.d - k0);
+    stage(k0, kc);
+    for (int k = 0; k < kc; ++k) {
+      const float wk = s_w[k];
+      float av[2][4], bv[2];
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) av[i][q] = s_xa[ra[i][q] + k];
+        bv[i] = s_xb[rb[i] + k];
+      }
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const float df = (av[i][q] - bv[j]) * wk;
+            sq[i][j][q] = fmaf(df, df, sq[i][j][q]);
+          }
+    }
+  }
+  float sum[2] = {0.f, 0.f};  // sum G K_f, tr G
+  PG_TILE_FOR_EACH_OUTPUT(GP_V, ln, li, lj) {
+    const int gr = r0 + li, gc = c0 + lj;
+    float coef = 0.f;
+    if (gr < p.n && gc <= gr) {
+      const float gv = fmaf(-p.pf, p.h[(size_t)gr * p.ldh + gc], PG_TILE_OUTPUT(g));
+      if (gc == gr) {  // K_f = std^2 exactly, and every difference is 0
+        sum[0] = fmaf(gv, p.std2, sum[0]);
+        sum[1] += gv;
+      } else {  // (i, j) and (j, i)
+        float phi, omega;
+        gp_stat_phi_omega<KIND>(PG_TILE_OUTPUT(sq), phi, omega);
+        const float t = 2.f * gv * p.std2;
+        sum[0] = fmaf(t, phi, sum[0]);
+        coef = t * omega;
+      }
+    }
+    PG_TILE_OUTPUT(sq) = coef;
+  }
+
+  // pass 2: per column, coefficient x ((x_ic - x_jc) w_c)^2
+  for (int ch = 0; ch < chunks; ++ch) {
+    const int k0 = ch * GP_ARD_CHUNK, kc = min(GP_ARD_CHUNK, p.d - k0);
+    if (chunks > 1) stage(k0, kc);
+    for (int k = 0; k < kc; ++k) {
+      const float wk = s_w[k];
+      float av[2][4], bv[2];
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) av[i][q] = s_xa[ra[i][q] + k];
+        bv[i] = s_xb[rb[i] + k];
+      }
+      float s = 0.f;
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const float df = (av[i][q] - bv[j]) * wk;
+            s = fmaf(sq[i][j][q], df * df, s);
+          }
+#pragma unroll
+      for (int off = 32; off >= 1; off >>= 1) s += __shfl_down(s, off);
+      if ((tid & 63) == 0) s_col[(tid >> 6) * GP_ARD_MAX_D + k0 + k] = s;
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) sum[k] += __shfl_down(sum[k], off);
+    if ((tid & 63) == 0) s_red[(tid >> 6) * 2 + k] = sum[k];
+  }
+  __syncthreads();
+  float* row = p.ws + (size_t)blockIdx.x * (p.d + 2);
+  if (tid < 2) row[tid] = ((s_red[tid] + s_red[2 + tid]) + s_red[4 + tid]) + s_red[6 + tid];
+  if (tid < p.d)  // d <= 256 = the threads of the workgroup
+    row[2 + tid] = ((s_col[tid] + s_col[GP_ARD_MAX_D + tid]) + s_col[2 * GP_ARD_MAX_D + tid]) + s_col[3 * GP_ARD_MAX_D + tid];
 }
 
 // The sum of `len` doubles per thread slot, a fixed tree over the 256 threads; the total is in s[0 .. len) afterwards.
@@ -295,6 +452,7 @@ __device__ __forceinline__ void mll_tree(double* s, const double (&v)[LEN], int 
   }
 }
 
+// inv_2l3: what the second sum is scaled by, 1 / (2 l^3) for the squared exponential and 1 / (2 l) for the other kinds
 __global__ void __launch_bounds__(GP_THREADS) gp_mll_finish_kernel(const float* __restrict__ ws, int tiles, double inv_std, double inv_2l3,
                                                                    float* __restrict__ out) {
   __shared__ double s[MLL_SUMS * GP_THREADS];
@@ -309,6 +467,21 @@ __global__ void __launch_bounds__(GP_THREADS) gp_mll_finish_kernel(const float* 
     out[0] = (float)(s[0] * inv_std);
     out[1] = (float)(s[GP_THREADS] * inv_2l3);
     out[2] = (float)(0.5 * s[2 * GP_THREADS]);
+  }
+}
+
+// The ARD finish: workgroup c adds column c of the partial rows in double — thread t the tiles t, t + 256, ... ascending, then
+// the fixed tree — and applies 1 / std (c = 0), 1 / 2 (c = 1) or 1 / (2 l) = w / 2 of its column.
+__global__ void __launch_bounds__(GP_THREADS) gp_ard_finish_kernel(const float* __restrict__ ws, int tiles, int row_floats, double inv_std,
+                                                                   const float* __restrict__ w, float* __restrict__ out) {
+  __shared__ double s[GP_THREADS];
+  const int tid = threadIdx.x, c = blockIdx.x;
+  double v[1] = {0.};
+  for (int t = tid; t < tiles; t += GP_THREADS) v[0] += (double)ws[(size_t)t * row_floats + c];
+  mll_tree<1>(s, v, tid);
+  if (tid == 0) {
+    const double scale = c == 0 ? inv_std : (c == 1 ? 0.5 : 0.5 * (double)w[c - 2]);
+    out[c] = (float)(s[0] * scale);
   }
 }
 
@@ -352,6 +525,25 @@ int gp_mll_plan(int n, int d, int p, GpMllPlan& ml, const char* name) {
   ml.tiles = P * (P + 1) / 2;
   ml.gram_products = P * (P + 1) * (P + 2) / 6;  // sum_I (I + 1)(P - I)
   ml.ws_floats = MLL_SUMS * ml.tiles;
+  return 0;
+}
+
+// The domain and the geometry of the ARD reduction: gp_mll_plan's, and d <= 256.
+struct GpArdPlan {
+  long tiles, row_floats, ws_floats;
+  int chunks;
+};
+
+int gp_ard_plan(int n, int d, int p, GpArdPlan& ap, const char* name) {
+  GpMllPlan ml;
+  const int rc = gp_mll_plan(n, d, p, ml, name);
+  if (rc) return rc;
+  PG_REQUIRE(d <= GP_ARD_MAX_D, PG_ESHAPE, "%s: d = %d: per-dimension lengthscale gradients are built for at most %d input columns", name, d,
+             GP_ARD_MAX_D);
+  ap.tiles = ml.tiles;
+  ap.row_floats = d + 2;
+  ap.ws_floats = ap.tiles * ap.row_floats;
+  ap.chunks = pg_cdiv(d, GP_ARD_CHUNK);
   return 0;
 }
 
@@ -418,16 +610,29 @@ PG_EXPORT int pg_gp_gram_upper(const float* x, long ldx, int n, float* h, long l
   return 0;
 }
 
-PG_EXPORT int pg_gp_se_mll_sums(const float* x, long ldx, int n, int d, float std, float lengthscale, const float* h, long ldh,
-                                const float* alpha_t, long lda, int p, float* ws, size_t ws_floats, float* out, void* stream) {
-  GP_MLL_PLAN_OR_RETURN(ml, n, d, p, "pg_gp_se_mll_sums");
-  PG_REQUIRE(x && h && alpha_t && ws && out, PG_EINVAL, "pg_gp_se_mll_sums: null pointer");
-  PG_REQUIRE(ldx >= d && ldh >= n && lda >= n, PG_EINVAL, "pg_gp_se_mll_sums: a row stride below its row length");
-  PG_REQUIRE(lengthscale > 0.f && std == std && std != 0.f, PG_EINVAL, "pg_gp_se_mll_sums: lengthscale = %g must be > 0, std = %g no NaN and not 0",
+namespace {
+
+bool gp_kind_known(int kind) { return kind == PG_GP_KIND_SE || kind == PG_GP_KIND_MATERN32 || kind == PG_GP_KIND_MATERN52; }
+
+template <int KIND>
+void gp_stat_sums_launch(int route, unsigned tiles, hipStream_t st, const GpMllSumsArgs& a) {
+  if (route == 0)
+    hipLaunchKernelGGL((gp_se_mll_sums_kernel<0, KIND>), dim3(tiles), dim3(GP_THREADS), 0, st, a);
+  else
+    hipLaunchKernelGGL((gp_se_mll_sums_kernel<1, KIND>), dim3(tiles), dim3(GP_THREADS), 0, st, a);
+}
+
+// the one launch path of pg_gp_se_mll_sums (kind SE) and pg_gp_stat_mll_sums
+int gp_stat_mll_sums(const char* name, int kind, const float* x, long ldx, int n, int d, float std, float lengthscale, const float* h, long ldh,
+                     const float* alpha_t, long lda, int p, float* ws, size_t ws_floats, float* out, void* stream) {
+  GP_MLL_PLAN_OR_RETURN(ml, n, d, p, name);
+  PG_REQUIRE(gp_kind_known(kind), PG_EINVAL, "%s: kind %d is none of PG_GP_KIND_*", name, kind);
+  PG_REQUIRE(x && h && alpha_t && ws && out, PG_EINVAL, "%s: null pointer", name);
+  PG_REQUIRE(ldx >= d && ldh >= n && lda >= n, PG_EINVAL, "%s: a row stride below its row length", name);
+  PG_REQUIRE(lengthscale > 0.f && std == std && std != 0.f, PG_EINVAL, "%s: lengthscale = %g must be > 0, std = %g no NaN and not 0", name,
              (double)lengthscale, (double)std);
-  PG_REQUIRE(ws_floats >= (size_t)ml.ws_floats, PG_EINVAL, "pg_gp_se_mll_sums: the workspace holds %zu floats, %ld are needed", ws_floats,
-             ml.ws_floats);
-  GP_TRY(gp_device("pg_gp_se_mll_sums"));
+  PG_REQUIRE(ws_floats >= (size_t)ml.ws_floats, PG_EINVAL, "%s: the workspace holds %zu floats, %ld are needed", name, ws_floats, ml.ws_floats);
+  GP_TRY(gp_device(name));
   const hipStream_t st = (hipStream_t)stream;
   GpMllSumsArgs a;
   a.x = x;
@@ -443,14 +648,82 @@ PG_EXPORT int pg_gp_se_mll_sums(const float* x, long ldx, int n, int d, float st
   a.std2 = std * std;
   a.neg_inv = -0.5f / (lengthscale * lengthscale);
   a.pf = (float)p;
-  if (ml.se_route == 0)
-    hipLaunchKernelGGL(gp_se_mll_sums_kernel<0>, dim3((unsigned)ml.tiles), dim3(GP_THREADS), 0, st, a);
-  else
-    hipLaunchKernelGGL(gp_se_mll_sums_kernel<1>, dim3((unsigned)ml.tiles), dim3(GP_THREADS), 0, st, a);
-  PG_LAUNCH_CHECK("pg_gp_se_mll_sums");
+  a.inv_l2 = 1.f / (lengthscale * lengthscale);
+  a.w = nullptr;
+  if (kind == PG_GP_KIND_SE) gp_stat_sums_launch<PG_GP_KIND_SE>(ml.se_route, (unsigned)ml.tiles, st, a);
+  if (kind == PG_GP_KIND_MATERN32) gp_stat_sums_launch<PG_GP_KIND_MATERN32>(ml.se_route, (unsigned)ml.tiles, st, a);
+  if (kind == PG_GP_KIND_MATERN52) gp_stat_sums_launch<PG_GP_KIND_MATERN52>(ml.se_route, (unsigned)ml.tiles, st, a);
+  PG_LAUNCH_CHECK(name);
   const double l3 = (double)lengthscale * (double)lengthscale * (double)lengthscale;
-  hipLaunchKernelGGL(gp_mll_finish_kernel, dim3(1), dim3(GP_THREADS), 0, st, (const float*)ws, (int)ml.tiles, 1.0 / (double)std, 0.5 / l3, out);
-  PG_LAUNCH_CHECK("pg_gp_se_mll_sums");
+  const double scale = kind == PG_GP_KIND_SE ? 0.5 / l3 : 0.5 / (double)lengthscale;
+  hipLaunchKernelGGL(gp_mll_finish_kernel, dim3(1), dim3(GP_THREADS), 0, st, (const float*)ws, (int)ml.tiles, 1.0 / (double)std, scale, out);
+  PG_LAUNCH_CHECK(name);
+  return 0;
+}
+
+}  // namespace
+
+PG_EXPORT int pg_gp_se_mll_sums(const float* x, long ldx, int n, int d, float std, float lengthscale, const float* h, long ldh,
+                                const float* alpha_t, long lda, int p, float* ws, size_t ws_floats, float* out, void* stream) {
+  return gp_stat_mll_sums("pg_gp_se_mll_sums", PG_GP_KIND_SE, x, ldx, n, d, std, lengthscale, h, ldh, alpha_t, lda, p, ws, ws_floats, out, stream);
+}
+
+PG_EXPORT int pg_gp_stat_mll_sums(int kind, const float* x, long ldx, int n, int d, float std, float lengthscale, const float* h, long ldh,
+                                  const float* alpha_t, long lda, int p, float* ws, size_t ws_floats, float* out, void* stream) {
+  return gp_stat_mll_sums("pg_gp_stat_mll_sums", kind, x, ldx, n, d, std, lengthscale, h, ldh, alpha_t, lda, p, ws, ws_floats, out, stream);
+}
+
+PG_EXPORT int pg_gp_ard_plan(int n, int d, int p, long long* out, int out_len) {
+  PG_REQUIRE(out && out_len >= PG_GP_ARD_PLAN_INTS, PG_EINVAL, "pg_gp_ard_plan: null pointer or short output array");
+  GpArdPlan ap;
+  GP_TRY(gp_ard_plan(n, d, p, ap, "pg_gp_ard_plan"));
+  out[0] = GP_T;
+  out[1] = ap.tiles;
+  out[2] = ap.row_floats;
+  out[3] = ap.ws_floats;
+  out[4] = ap.chunks;
+  out[5] = 2;
+  out[6] = GP_ARD_MAX_D;
+  out[7] = GP_ARD_CHUNK;
+  return 0;
+}
+
+PG_EXPORT int pg_gp_ard_mll_sums(int kind, const float* x, long ldx, int n, int d, float std, const float* inv_ls, const float* h, long ldh,
+                                 const float* alpha_t, long lda, int p, float* ws, size_t ws_floats, float* out, void* stream) {
+  const char* name = "pg_gp_ard_mll_sums";
+  GpArdPlan ap;
+  GP_TRY(gp_ard_plan(n, d, p, ap, name));
+  PG_REQUIRE(gp_kind_known(kind), PG_EINVAL, "%s: kind %d is none of PG_GP_KIND_*", name, kind);
+  PG_REQUIRE(x && inv_ls && h && alpha_t && ws && out, PG_EINVAL, "%s: null pointer", name);
+  PG_REQUIRE(ldx >= d && ldh >= n && lda >= n, PG_EINVAL, "%s: a row stride below its row length", name);
+  PG_REQUIRE(std == std && std != 0.f, PG_EINVAL, "%s: std = %g no NaN and not 0", name, (double)std);
+  PG_REQUIRE(ws_floats >= (size_t)ap.ws_floats, PG_EINVAL, "%s: the workspace holds %zu floats, %ld are needed", name, ws_floats, ap.ws_floats);
+  GP_TRY(gp_device(name));
+  const hipStream_t st = (hipStream_t)stream;
+  GpMllSumsArgs a;
+  a.x = x;
+  a.h = h;
+  a.at = alpha_t;
+  a.ws = ws;
+  a.ldx = ldx;
+  a.ldh = ldh;
+  a.lda = lda;
+  a.n = n;
+  a.d = d;
+  a.p = p;
+  a.std2 = std * std;
+  a.neg_inv = -0.5f;
+  a.pf = (float)p;
+  a.inv_l2 = 1.f;
+  a.w = inv_ls;
+  const dim3 grid((unsigned)ap.tiles), block(GP_THREADS);
+  if (kind == PG_GP_KIND_SE) hipLaunchKernelGGL(gp_ard_mll_sums_kernel<PG_GP_KIND_SE>, grid, block, 0, st, a);
+  if (kind == PG_GP_KIND_MATERN32) hipLaunchKernelGGL(gp_ard_mll_sums_kernel<PG_GP_KIND_MATERN32>, grid, block, 0, st, a);
+  if (kind == PG_GP_KIND_MATERN52) hipLaunchKernelGGL(gp_ard_mll_sums_kernel<PG_GP_KIND_MATERN52>, grid, block, 0, st, a);
+  PG_LAUNCH_CHECK(name);
+  hipLaunchKernelGGL(gp_ard_finish_kernel, dim3((unsigned)ap.row_floats), block, 0, st, (const float*)ws, (int)ap.tiles, (int)ap.row_floats,
+                     1.0 / (double)std, inv_ls, out);
+  PG_LAUNCH_CHECK(name);
   return 0;
 }
 

@@ -158,6 +158,10 @@ SIGNATURES = {
     "pg_gp_gram_upper": (c_i, [c_f, c_l, c_i, c_f, c_l, c_i, c_s]),
     "pg_gp_se_mll_sums": (c_i, [c_f, c_l, c_i, c_i, c_flt, c_flt, c_f, c_l, c_f, c_l, c_i, c_f, c_z, c_f, c_s]),
     "pg_gp_mll_value": (c_i, [c_f, c_l, c_i, c_f, c_l, c_f, c_l, c_i, c_f, c_s]),
+    "pg_gp_stat_kernel": (c_i, [c_i, c_f, c_l, c_i, c_f, c_l, c_i, c_i, c_flt, c_flt, c_f, c_flt, c_f, c_l, c_i, c_i, c_s]),
+    "pg_gp_stat_mll_sums": (c_i, [c_i, c_f, c_l, c_i, c_i, c_flt, c_flt, c_f, c_l, c_f, c_l, c_i, c_f, c_z, c_f, c_s]),
+    "pg_gp_ard_plan": (c_i, [c_i] * 3 + [ctypes.POINTER(ctypes.c_longlong), c_i]),
+    "pg_gp_ard_mll_sums": (c_i, [c_i, c_f, c_l, c_i, c_i, c_flt, c_f, c_f, c_l, c_f, c_l, c_i, c_f, c_z, c_f, c_s]),
     "pg_nice_scale_fwd": (c_i, [c_f] * 3 + [c_i] * 3 + [c_s]),
     "pg_nice_scale_bwd_workspace_floats": (c_z, [c_i] * 2),
     "pg_nice_scale_bwd": (c_i, [c_f] * 5 + [c_i] * 3 + [c_f, c_z, c_s]),

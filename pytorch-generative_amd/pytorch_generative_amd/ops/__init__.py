@@ -263,4 +263,11 @@ from pytorch_generative_amd.ops.gp import (  # noqa: F401
     gram_upper_,
     se_mll_sums,
     mll_value,
+    GP_ARD_PLAN_INTS,
+    GP_KINDS,
+    gp_ard_plan_status,
+    gp_ard_plan,
+    stationary_kernel,
+    stationary_mll_sums,
+    ard_mll_sums,
 )

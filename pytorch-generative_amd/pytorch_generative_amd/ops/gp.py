@@ -4,6 +4,8 @@ update C = C -/+ A B^T. Every operand is a 2-D fp32 tensor whose rows are contig
 its row (a view of a larger buffer is an operand as it lies). Functions ending in an underscore work in place. No gradients.
 The second half works on csrc/gp_mll.hip: the triangular inverse of a factor, the product that turns it into K^-1, and the
 reductions that give the log marginal likelihood and its gradients with respect to the hyperparameters as numbers on the device.
+The third part serves the stationary kernels beyond the shared-lengthscale squared exponential: Matern 3/2 and 5/2, and one
+lengthscale per input column (ARD) for all three kinds, with the reduction that gives every d/d lengthscale_c.
 
 Part of the operator layer (pytorch_generative_amd.ops): HIP kernels called through the C-ABI with tensor.data_ptr() and the
 current stream. No CPU / ATen fallback: a missing library, a CPU tensor or a shape outside ops.gp_plan raises."""
@@ -287,4 +289,156 @@ def mll_value(l, zt, alpha_t, *, out=None):
     out = _vec(out, 2, "mll_value.out")
     _lib.check(_lib.load().pg_gp_mll_value(l.data_ptr(), ld, n, zt.data_ptr(), ldz, alpha_t.data_ptr(), lda, p, out.data_ptr(), _stream()),
                "pg_gp_mll_value")
+    return out
+
+
+# ---------------------------------------------------------------------------------------------
+# stationary kernels with per-dimension (ARD) lengthscales: squared exponential, Matern 3/2 and 5/2
+GP_ARD_PLAN_INTS = 8  # PG_GP_ARD_PLAN_INTS
+GP_KINDS = {"se": 0, "matern32": 1, "matern52": 2}  # PG_GP_KIND_*
+_ARD_PLAN_FIELDS = ("tile", "sums_tiles", "partial_row_floats", "workspace_floats", "column_chunks", "sums_launches", "max_d", "chunk_columns")
+
+
+def gp_ard_plan_status(n, d, p):
+    """(status, plan): the C-ABI status of pg_gp_ard_plan (0, PG_ESHAPE = -2, PG_EINVAL = -1) and the plan dict (None on error)."""
+    out = (ctypes.c_longlong * GP_ARD_PLAN_INTS)()
+    rc = _lib.load().pg_gp_ard_plan(int(n), int(d), int(p), out, GP_ARD_PLAN_INTS)
+    return rc, (None if rc else dict(zip(_ARD_PLAN_FIELDS, out)))
+
+
+def gp_ard_plan(n, d, p):
+    """The planner's answer (pg_gp_ard_plan, host only) for the per-dimension lengthscale gradients of n training rows with d
+    input columns and p columns of y: None for a problem it refuses (the domain of gp_mll_plan, and d <= 256), else a dict with
+    the tile edge, the tiles (= partial rows) of the reduction, the floats of a partial row (d + 2), the workspace floats
+    ard_mll_sums needs, the column chunks the rows of x are staged in, the launches, the largest d and the columns of a chunk."""
+    return gp_ard_plan_status(n, d, p)[1]
+
+
+def _kind(kind, name):
+    if kind not in GP_KINDS:
+        raise ValueError(f"{name}: kind {kind!r} is none of {sorted(GP_KINDS)}")
+    return GP_KINDS[kind]
+
+
+def _lengthscale(lengthscale, inv_lengthscale, d, name):
+    """(the scalar lengthscale for the C-ABI, the device vector 1 / lengthscale or None). A tensor lengthscale is per dimension;
+    inv_lengthscale is the caller's cached reciprocal of it, which is then not computed again."""
+    if inv_lengthscale is None and not torch.is_tensor(lengthscale):
+        return float(lengthscale), None
+    given = lengthscale if inv_lengthscale is None else inv_lengthscale
+    if given.dim() != 1 or given.numel() != d:
+        raise ValueError(f"{name}: a per-dimension lengthscale of shape {tuple(given.shape)} for inputs of {d} columns")
+    given = _vec(given, d, f"{name}.lengthscale")
+    return 1.0, (given.reciprocal() if inv_lengthscale is None else given)
+
+
+def stationary_kernel(a, b, std, lengthscale, noise_var=0.0, *, kind="se", out=None, mirror=True, diag_offset=None, route=None,
+                      inv_lengthscale=None):
+    """The stationary covariance K[i, j] = std^2 phi(r_ij) of a (n, d) and b (m, d), (n, m), r^2 = sum_c ((a_ic - b_jc) / l_c)^2:
+    kind "se" (phi = exp(-r^2 / 2)), "matern32" ((1 + sqrt(3) r) exp(-sqrt(3) r)) or "matern52"
+    ((1 + sqrt(5) r + 5 r^2 / 3) exp(-sqrt(5) r)). lengthscale: a float (shared) or a 1-D fp32 tensor of d entries on the GPU
+    (one per input column); inv_lengthscale: its reciprocal, if the caller keeps one (lengthscale is then not read).
+
+    `b is a`, mirror, diag_offset, out and route are se_kernel's, with the same promises: the diagonal exactly std^2 + noise_var,
+    exact symmetry, an element's bits depending on its two rows and the lengthscales alone. The exact-difference route
+    (d <= 16, forced up to 64) scales the DIFFERENCE, so inputs far from the origin lose nothing and a duplicated row gives
+    exactly std^2; the MFMA route scales the rows while staging them. kind "se" with a float lengthscale is se_kernel, bit for
+    bit. One launch, capturable, bit-identical from run to run."""
+    name = "stationary_kernel"
+    a, lda = _mat(a, f"{name}.a")
+    sym = b is a
+    b, ldb = (a, lda) if sym else _mat(b, f"{name}.b")
+    n, d = a.shape
+    m = b.shape[0]
+    if b.shape[1] != d:
+        raise ValueError(f"{name}: a has {d} columns, b {b.shape[1]}")
+    if route not in _SE_ROUTES:
+        raise ValueError(f"{name}: route {route!r} is none of None, 'direct', 'mfma'")
+    code = _kind(kind, name)
+    scalar, inv = _lengthscale(lengthscale, inv_lengthscale, d, name)
+    rc, _ = gp_plan_status(n, m, d, 1)
+    _lib.check(rc, name)
+    if out is None:
+        out = torch.empty((n, m), device=a.device, dtype=torch.float32)
+    out, ldk = _mat(out, f"{name}.out")
+    if tuple(out.shape) != (n, m):
+        raise ValueError(f"{name}: out of shape {tuple(out.shape)}, expected {(n, m)}")
+    flags = _SE_ROUTES[route]
+    off = 0
+    if sym:
+        if diag_offset is not None:
+            raise ValueError(f"{name}: diag_offset belongs to the cross form")
+        flags |= GP_LOWER | GP_DIAG | (GP_MIRROR if mirror else 0)
+    elif diag_offset is not None:
+        flags |= GP_LOWER | GP_DIAG
+        off = int(diag_offset)
+    _lib.check(_lib.load().pg_gp_stat_kernel(code, a.data_ptr(), lda, n, b.data_ptr(), ldb, m, d, float(std), scalar,
+                                             None if inv is None else inv.data_ptr(), float(noise_var), out.data_ptr(), ldk, off, flags,
+                                             _stream()), "pg_gp_stat_kernel")
+    return out
+
+
+def _sums_operands(x, h, alpha_t, name):
+    x, ldx = _mat(x, f"{name}.x")
+    h, ldh = _square(h, f"{name}.h")
+    alpha_t, lda = _mat(alpha_t, f"{name}.alpha_t")
+    if h.shape[0] != x.shape[0] or alpha_t.shape[1] != x.shape[0]:
+        raise ValueError(f"{name}: x {tuple(x.shape)}, h {tuple(h.shape)} and alpha_t {tuple(alpha_t.shape)} do not fit")
+    return x, ldx, h, ldh, alpha_t, lda
+
+
+def stationary_mll_sums(x, std, lengthscale, h, alpha_t, *, kind="se", out=None, workspace=None):
+    """se_mll_sums for any kind of stationary_kernel with one shared lengthscale (a float): the 1-D tensor
+        (sum_ij G_ij K_f,ij / std,  sum_ij G_ij std^2 omega(r_ij) r_ij^2 / (2 lengthscale),  tr G / 2),   omega = -phi'(r) / r,
+    the gradients of the log marginal likelihood with respect to std, lengthscale and noise_var. Same operands, workspace
+    (ops.gp_mll_plan) and promises; kind "se" is se_mll_sums, bit for bit. Two launches, capturable."""
+    name = "stationary_mll_sums"
+    x, ldx, h, ldh, alpha_t, lda = _sums_operands(x, h, alpha_t, name)
+    n, d = x.shape
+    p = alpha_t.shape[0]
+    code = _kind(kind, name)
+    rc, plan = gp_mll_plan_status(n, d, p)
+    _lib.check(rc, name)
+    if workspace is None:
+        workspace = torch.empty(plan["workspace_floats"], device=x.device, dtype=torch.float32)
+    workspace = _vec(workspace, plan["workspace_floats"], f"{name}.workspace", at_least=True)
+    if out is None:
+        out = torch.empty(3, device=x.device, dtype=torch.float32)
+    out = _vec(out, 3, f"{name}.out")
+    _lib.check(_lib.load().pg_gp_stat_mll_sums(code, x.data_ptr(), ldx, n, d, float(std), float(lengthscale), h.data_ptr(), ldh,
+                                               alpha_t.data_ptr(), lda, p, workspace.data_ptr(), workspace.numel(), out.data_ptr(), _stream()),
+               "pg_gp_stat_mll_sums")
+    return out
+
+
+def ard_mll_sums(x, std, lengthscale, h, alpha_t, *, kind="se", out=None, workspace=None, inv_lengthscale=None):
+    """The gradients of the log marginal likelihood with respect to std, noise_var and EVERY per-dimension lengthscale, for the
+    rows of x (n, d), h (n, n) = K^-1 (only its lower triangle is read) and alpha_t (p, n): the 1-D tensor of d + 2 floats
+        (sum_ij G_ij K_f,ij / std,  tr G / 2,  S_0 / (2 l_0), ..., S_{d-1} / (2 l_{d-1})),
+        S_c = sum_ij G_ij std^2 omega(r_ij) ((x_ic - x_jc) / l_c)^2,   G = alpha alpha^T - p h,
+    on the GPU, into `out` if given. lengthscale: a 1-D fp32 tensor of d entries on the GPU (inv_lengthscale: its reciprocal, if
+    the caller keeps one). One workgroup per 64 x 64 tile on or below the diagonal; the per-dimension terms are exact
+    differences on the VALU, the rows of x staged in chunks of 64 columns; nothing of size (n, n) is written. `workspace`
+    (ops.gp_ard_plan's workspace_floats, made if not given) takes one fp32 partial row of d + 2 floats per tile, which a second
+    launch adds in double in a fixed order. d <= 256 (ValueError above). No atomics: bit-identical from run to run. Two
+    launches, capturable."""
+    name = "ard_mll_sums"
+    x, ldx, h, ldh, alpha_t, lda = _sums_operands(x, h, alpha_t, name)
+    n, d = x.shape
+    p = alpha_t.shape[0]
+    code = _kind(kind, name)
+    if inv_lengthscale is None and not torch.is_tensor(lengthscale):
+        raise ValueError(f"{name}: lengthscale must be a 1-D tensor of {d} entries (stationary_mll_sums takes a shared float)")
+    _, inv = _lengthscale(lengthscale, inv_lengthscale, d, name)
+    rc, plan = gp_ard_plan_status(n, d, p)
+    _lib.check(rc, name)
+    if workspace is None:
+        workspace = torch.empty(plan["workspace_floats"], device=x.device, dtype=torch.float32)
+    workspace = _vec(workspace, plan["workspace_floats"], f"{name}.workspace", at_least=True)
+    if out is None:
+        out = torch.empty(d + 2, device=x.device, dtype=torch.float32)
+    out = _vec(out, d + 2, f"{name}.out")
+    _lib.check(_lib.load().pg_gp_ard_mll_sums(code, x.data_ptr(), ldx, n, d, float(std), inv.data_ptr(), h.data_ptr(), ldh, alpha_t.data_ptr(),
+                                              lda, p, workspace.data_ptr(), workspace.numel(), out.data_ptr(), _stream()),
+               "pg_gp_ard_mll_sums")
     return out
