@@ -564,7 +564,8 @@ int pg_fvbn_unpack(const float* wp, float* dense, int D, void* stream);
  * the plan and the launches alike, nothing launched. PG_EINVAL for a null pointer, a short array, a row stride below the row
  * length, unknown flags. Without a device an entry point returns hipErrorNoDevice (100), and only after the plan and the
  * argument checks accepted the call.
- *   se_kernel:  K[i][j] = std^2 exp(-|a_i - b_j|^2 / (2 lengthscale^2)) for a (n, d), b (m, d) into K (n, m). PG_GP_LOWER: only
+ *   se_kernel:  pg_gp_stat_kernel (below) with kind SE and no inv_ls, under its own name in the messages.
+ *               K[i][j] = std^2 exp(-|a_i - b_j|^2 / (2 lengthscale^2)) for a (n, d), b (m, d) into K (n, m). PG_GP_LOWER: only
  *               elements with j <= i + diag_off are written and tiles wholly above that line are not visited; PG_GP_DIAG: the
  *               elements j == i + diag_off are written as exactly std^2 + noise_var; PG_GP_MIRROR (a is b, lower, diag_off 0):
  *               K[j][i] = K[i][j] as well, so the matrix is exactly symmetric. Route 1 clamps the squared distance at 0 before
@@ -580,7 +581,8 @@ int pg_fvbn_unpack(const float* wp, float* dense, int D, void* stream);
  *               final and untouched, rows >= done continue from the values the updates left. A pivot that is not > 0 (a NaN
  *               included) stores base + index + 1 into *info by a plain store, only while *info is 0; the kernel goes on.
  *   trsm_diag:  X L_kk^T = B in place (transposed != 0: X L_kk = B) for rows x jb, 64 rows per workgroup; columns < done are
- *               final (forward form). fmaf chains in ascending (transposed: descending) k, then one IEEE division.
+ *               final (forward form). fmaf chains in ascending (transposed: descending) k, then one IEEE division. The kernel
+ *               (gp_subst_diag_kernel, csrc/gp_common.h) is also trtri_t's substitution.
  *   potrf:      the lower factor of A (n, n) in place, right-looking, at most three launches per panel of 64 columns; the strict
  *               upper triangle is neither read nor written. n_done > 0: rows < n_done hold a finished factor and only rows
  *               n_done .. n (holding A's values in columns 0 .. their own) are completed; the result has the bits of the full
@@ -634,13 +636,14 @@ int pg_gp_trsm_right(const float* l, long ld, int n, float* x, long ldx, int row
  *   gram_upper:  H = X X^T for the upper triangular X, on the lower triangle of h (diagonal included); flags = PG_GP_MIRROR:
  *                h[j][i] = h[i][j] too. Tile (I, J), J <= I, starts its k loop at 64 I; the strict lower triangle of x is
  *                not read. Each element is one fmaf chain in ascending k. No k-split. h must not be x.
- *   se_mll_sums: one workgroup per 64 x 64 tile on or below the diagonal recomputes D2 and K_f from the rows of x (n, d) (the
- *                routes and the bits of se_kernel; the diagonal is K_f = std^2, D2 = 0 exactly), forms
- *                G_ij = sum_c alpha_ic alpha_jc - p H_ij in registers (only the lower triangle of h is read) and sums
- *                G K_f, G K_f D2 (off-diagonal elements twice) and G_ii; K_f, D2 and G are never written. Every workgroup
- *                writes its three fp32 partials into ws (ws_floats >= plan[8], PG_EINVAL below); a second launch of one
- *                workgroup adds them in double — thread t the tiles t, t + 256, ... ascending, then a fixed tree — and writes
- *                out[0 .. 3) = d/d std, d/d lengthscale, d/d noise_var. lengthscale > 0, std != 0.
+ *   se_mll_sums: pg_gp_stat_mll_sums (below) with kind SE, under its own name in the messages: one workgroup per 64 x 64 tile
+ *                on or below the diagonal recomputes D2 and K_f from the rows of x (n, d) (the routes and the bits of
+ *                se_kernel; the diagonal is K_f = std^2, D2 = 0 exactly), forms G_ij = sum_c alpha_ic alpha_jc - p H_ij in
+ *                registers (only the lower triangle of h is read) and sums G K_f, G K_f D2 (off-diagonal elements twice) and
+ *                G_ii; K_f, D2 and G are never written. Every workgroup writes its three fp32 partials into ws (ws_floats >=
+ *                plan[8], PG_EINVAL below); a second launch of one workgroup adds them in double — thread t the tiles t, t +
+ *                256, ... ascending, then a fixed tree — and writes out[0 .. 3) = d/d std, d/d lengthscale, d/d noise_var.
+ *                lengthscale > 0, std != 0.
  *   mll_value:   one workgroup, fixed order, double accumulators: out[0] = log p(y), out[1] = sum alpha.
  * out is device memory. No float atomics, no allocation, no host synchronisation (capturable), bit-identical from run to run.
  * ------------------------------------------------------------------------------------- */
@@ -665,12 +668,12 @@ int pg_gp_mll_value(const float* l, long ld, int n, const float* zt, long ldz, c
  *   stat_kernel:   pg_gp_se_kernel's arguments, flags, routes (pg_gp_plan decides) and promises — the diagonal exactly
  *                  std^2 + noise_var, an element's bits a function of its two rows and of w alone — plus the kind and inv_ls, a
  *                  DEVICE pointer to the d floats w_c. inv_ls == NULL: the shared scalar `lengthscale` is used (kind SE is then
- *                  pg_gp_se_kernel itself, bit for bit); otherwise the scalar is ignored. Route 0 forms (a_c - b_c) w_c, the
+ *                  what pg_gp_se_kernel forwards to); otherwise the scalar is ignored. Route 0 forms (a_c - b_c) w_c, the
  *                  difference first: inputs far from the origin lose nothing and a duplicated row gives r = 0, phi = 1 exactly.
  *                  Route 1 scales the rows by w WHILE STAGING them into LDS (no extra launch, no scaled copy of the rows) and
  *                  clamps the squared distance at 0 before the square root.
  *   stat_mll_sums: pg_gp_se_mll_sums for any kind with one shared lengthscale, same arguments, domain and outputs; kind SE is
- *                  pg_gp_se_mll_sums itself, bit for bit. The other kinds sum G std^2 omega r^2 directly.
+ *                  what pg_gp_se_mll_sums forwards to. The other kinds sum G std^2 omega r^2 directly.
  *   ard_mll_sums:  out[0 .. d + 2) = d/d std, d/d noise_var, d/d l_0 .. d/d l_{d-1}. One workgroup per 64 x 64 tile on or below
  *                  the diagonal forms G in registers (alpha_i . alpha_j on the MFMA for every p, only the lower triangle of h is
  *                  read, off-diagonal elements count twice). The per-dimension terms are exact differences on the VALU for

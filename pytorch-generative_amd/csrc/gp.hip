@@ -9,8 +9,8 @@
 //   * gp_gemm_kernel seeds its accumulators with the tile of C and multiplies -A on the tile of mfma_tile.h, whose sums are one
 //     fmaf chain per output in k order from whatever the accumulator held: a trailing update applied panel after panel
 //     continues the same chain, whatever the blocking;
-//   * gp_potrf_diag_kernel and gp_trsm_diag_kernel continue it on the VALU inside the panel of 64 columns that holds j, then
-//     take one square root or one IEEE division (no explicit inverse of a diagonal block).
+//   * gp_potrf_diag_kernel and gp_subst_diag_kernel (gp_common.h) continue it on the VALU inside the panel of 64 columns that
+//     holds j, then take one square root or one IEEE division (no explicit inverse of a diagonal block).
 // The chain of an element therefore does not depend on how many rows the matrix had when its row was factored: completing rows
 // n_done .. n of a factor (pg_gp_potrf with n_done > 0) gives the bits of the full factorisation. Panels sit at absolute
 // multiples of 64; the MFMA only multiplies whole finished panels, the panel that contains n_done is finished on the VALU.
@@ -20,7 +20,7 @@
 // geometry; every entry point calls it, and reports a missing device only after it accepted the problem.
 //
 // Stationary kernels. The covariance kernels are templated on the kind (squared exponential, Matern 3/2, Matern 5/2) and on
-// per-dimension (ARD) lengthscales w_c = 1 / l_c; pg_gp_se_kernel is the <SE, shared lengthscale> instantiation, unchanged. With
+// per-dimension (ARD) lengthscales w_c = 1 / l_c; pg_gp_se_kernel is pg_gp_stat_kernel with kind SE and no inv_ls. With
 // ARD the exact-difference route forms (a_c - b_c) w_c and the MFMA route SCALES THE ROWS WHILE STAGING them into LDS
 // (gp_mma_tile's SCALE): one launch either way, no scaled copy of the rows, an element's bits depend on its two rows and w alone.
 #include "gp_common.h"
@@ -104,11 +104,7 @@ __global__ void __launch_bounds__(GP_THREADS) gp_se_direct_kernel(const GpSeArgs
   const int r0 = (blockIdx.x / p.col_tiles) * GP_T, c0 = (blockIdx.x % p.col_tiles) * GP_T;
   if (p.lower && c0 > r0 + (GP_T - 1) + p.diag_off) return;
   const int tid = threadIdx.x;
-  for (int e = tid; e < GP_T * p.d; e += GP_THREADS) {
-    const int r = e / p.d, k = e % p.d;
-    s_a[r * GP_TRI_LD + k] = r0 + r < p.n ? p.a[(size_t)(r0 + r) * p.lda + k] : 0.f;
-    s_b[r * GP_TRI_LD + k] = c0 + r < p.m ? p.b[(size_t)(c0 + r) * p.ldb + k] : 0.f;
-  }
+  GP_STAGE_ROWS(GP_TRI_LD, s_a, s_b, p.a, p.lda, r0, p.n, p.b, p.ldb, c0, p.m, 0, p.d, tid);
   if (ARD && tid < p.d) s_w[tid] = p.w[tid];
   __syncthreads();
   const int tx = tid & 15, ty = tid >> 4;
@@ -222,60 +218,6 @@ __global__ void __launch_bounds__(GP_THREADS) gp_potrf_diag_kernel(float* __rest
   if (tid == 0 && bad != 0 && *info == 0) *info = bad;
 }
 
-// The substitution against one diagonal block, 64 rows of X per workgroup, four lanes per row, each with the columns
-// j = 4 q + (lane & 3) of its row in registers; x_k goes to the row's lanes by a shuffle.
-//   forward (BACK = false): X L^T = B, x_ij = (b_ij - sum_{k < j} x_ik l_jk) / l_jj, k ascending; columns < done are final.
-//   backward (BACK = true): X L = B,   x_ij = (b_ij - sum_{k > j} x_ik l_kj) / l_jj, k descending.
-template <bool BACK>
-__global__ void __launch_bounds__(GP_THREADS) gp_trsm_diag_kernel(const float* __restrict__ l, long ld, float* __restrict__ x, long ldx,
-                                                                  int rows, int jb, int done) {
-  __shared__ float s_l[GP_T * GP_TRI_LD];
-  const int tid = threadIdx.x, lane = tid & 63;
-  for (int e = tid; e < GP_T * GP_T; e += GP_THREADS) {
-    const int j = e >> 6, k = e & 63;
-    float v = j == k ? 1.f : 0.f;  // rows beyond jb: the identity
-    if (j < jb && k <= j) v = l[(size_t)j * ld + k];
-    s_l[j * GP_TRI_LD + k] = v;
-  }
-  const int row = blockIdx.x * GP_T + (tid >> 2), c = tid & 3;
-  float v[16];
-#pragma unroll
-  for (int q = 0; q < 16; ++q) {
-    const int j = 4 * q + c;
-    v[q] = (row < rows && j < jb) ? x[(size_t)row * ldx + j] : 0.f;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int kk = 0; kk < GP_T; ++kk) {
-    const int k = BACK ? GP_T - 1 - kk : kk;
-    if (k < jb) {  // the same in every lane
-      const int qk = k >> 2, ck = k & 3;
-      float cand = v[qk];
-      if (BACK || k >= done) cand = cand / s_l[k * GP_TRI_LD + k];
-      const float xk = __shfl(cand, (lane & ~3) | ck);
-      if (c == ck) v[qk] = xk;
-      if (BACK) {
-#pragma unroll
-        for (int q = 0; q <= qk; ++q) {
-          const int j = 4 * q + c;
-          if (j < k) v[q] = fmaf(-xk, s_l[k * GP_TRI_LD + j], v[q]);
-        }
-      } else {
-#pragma unroll
-        for (int q = qk; q < 16; ++q) {
-          const int j = 4 * q + c;
-          if (j > k && j >= done) v[q] = fmaf(-xk, s_l[j * GP_TRI_LD + k], v[q]);
-        }
-      }
-    }
-  }
-#pragma unroll
-  for (int q = 0; q < 16; ++q) {
-    const int j = 4 * q + c;
-    if (row < rows && j < jb && j >= done) x[(size_t)row * ldx + j] = v[q];
-  }
-}
-
 // the launches; arguments are checked by the callers
 int gp_gemm(const float* a, long lda, const float* b, long ldb, float* c, long ldc, int R, int C, int K, int diag_off, int flags,
             hipStream_t st, const char* name) {
@@ -321,9 +263,9 @@ int gp_potrf_diag(float* a, long ld, int jb, int done, int base, int* info, hipS
 int gp_trsm_diag(const float* l, long ld, float* x, long ldx, int rows, int jb, int done, int back, hipStream_t st, const char* name) {
   const dim3 grid((unsigned)pg_cdiv(rows, GP_T));
   if (back)
-    hipLaunchKernelGGL(gp_trsm_diag_kernel<true>, grid, dim3(GP_THREADS), 0, st, l, ld, x, ldx, rows, jb, 0);
+    hipLaunchKernelGGL((gp_subst_diag_kernel<true, false>), grid, dim3(GP_THREADS), 0, st, l, ld, x, ldx, rows, jb, 0);
   else
-    hipLaunchKernelGGL(gp_trsm_diag_kernel<false>, grid, dim3(GP_THREADS), 0, st, l, ld, x, ldx, rows, jb, done);
+    hipLaunchKernelGGL((gp_subst_diag_kernel<false, false>), grid, dim3(GP_THREADS), 0, st, l, ld, x, ldx, rows, jb, done);
   PG_LAUNCH_CHECK(name);
   return 0;
 }
@@ -366,8 +308,7 @@ void gp_stat_launch(int route, dim3 grid, hipStream_t st, const GpSeArgs& p) {
 int gp_stat_kernel(const char* name, int kind, const float* a, long lda, int n, const float* b, long ldb, int m, int d, float std,
                    float lengthscale, const float* inv_ls, float noise_var, float* k, long ldk, int diag_off, int flags, void* stream) {
   GP_PLAN_OR_RETURN(pl, n, m, d, 1, name);
-  PG_REQUIRE(kind == PG_GP_KIND_SE || kind == PG_GP_KIND_MATERN32 || kind == PG_GP_KIND_MATERN52, PG_EINVAL, "%s: kind %d is none of PG_GP_KIND_*",
-             name, kind);
+  PG_REQUIRE(gp_kind_known(kind), PG_EINVAL, "%s: kind %d is none of PG_GP_KIND_*", name, kind);
   PG_REQUIRE(a && b && k, PG_EINVAL, "%s: null pointer", name);
   PG_REQUIRE(lda >= d && ldb >= d && ldk >= m, PG_EINVAL, "%s: a row stride below its row length", name);
   PG_REQUIRE((inv_ls || lengthscale > 0.f) && std == std && noise_var == noise_var, PG_EINVAL,
@@ -407,15 +348,12 @@ int gp_stat_kernel(const char* name, int kind, const float* a, long lda, int n, 
   p.inv_l2 = inv_ls ? 1.f : 1.f / (lengthscale * lengthscale);
   const dim3 grid((unsigned)((long)pg_cdiv(n, GP_T) * p.col_tiles));
   const hipStream_t st = (hipStream_t)stream;
-  if (inv_ls) {
-    if (kind == PG_GP_KIND_SE) gp_stat_launch<PG_GP_KIND_SE, true>(route, grid, st, p);
-    if (kind == PG_GP_KIND_MATERN32) gp_stat_launch<PG_GP_KIND_MATERN32, true>(route, grid, st, p);
-    if (kind == PG_GP_KIND_MATERN52) gp_stat_launch<PG_GP_KIND_MATERN52, true>(route, grid, st, p);
-  } else {
-    if (kind == PG_GP_KIND_SE) gp_stat_launch<PG_GP_KIND_SE, false>(route, grid, st, p);
-    if (kind == PG_GP_KIND_MATERN32) gp_stat_launch<PG_GP_KIND_MATERN32, false>(route, grid, st, p);
-    if (kind == PG_GP_KIND_MATERN52) gp_stat_launch<PG_GP_KIND_MATERN52, false>(route, grid, st, p);
-  }
+  gp_with_kind(kind, [&](auto K) {
+    if (inv_ls)
+      gp_stat_launch<decltype(K)::value, true>(route, grid, st, p);
+    else
+      gp_stat_launch<decltype(K)::value, false>(route, grid, st, p);
+  });
   PG_LAUNCH_CHECK(name);
   return 0;
 }

@@ -1,8 +1,11 @@
-// gp_common.h — what gp.hip and gp_mll.hip share: the tile constants, the 64 x 64 x K product of one workgroup on mfma_tile.h,
-// and the one function that decides the domain and the geometry of the Gaussian-process kernels. Moved here from gp.hip as it
-// was; every name keeps internal linkage (one copy per translation unit).
+// gp_common.h — what gp.hip and gp_mll.hip share: the tile constants, the stationary kinds and their host-side dispatch, the
+// 64 x 64 x K product of one workgroup on mfma_tile.h, the staging of rows into LDS and the exact differences behind a lane's
+// MFMA outputs, the substitution against a diagonal block (gp.hip's panel solves and gp_mll.hip's triangular inverse are
+// instantiations of one kernel), and the one function that decides the domain and the geometry of the Gaussian-process
+// kernels. Every name keeps internal linkage (one copy per translation unit).
 #pragma once
 #include <algorithm>
+#include <type_traits>
 
 #include "common.h"
 #include "mfma_tile.h"
@@ -16,7 +19,7 @@ constexpr int GP_KC = GpTile::KC;  // k per LDS chunk
 constexpr int GP_LD = GpTile::LD;  // LDS row stride of an operand chunk
 constexpr int GP_THREADS = pg_tile::THREADS;
 constexpr int GP_BLK_LD = 68;    // LDS row stride of the diagonal block in gp_potrf_diag_kernel
-constexpr int GP_TRI_LD = 65;    // LDS row stride of the diagonal block in gp_trsm_diag_kernel and of the rows in gp_se_direct_kernel
+constexpr int GP_TRI_LD = 65;    // LDS row stride of the diagonal block in gp_subst_diag_kernel and of the rows in gp_se_direct_kernel
 constexpr int GP_MAX_N = 16384;  // n, m: element offsets of an (n, n) matrix fit 32 bits
 constexpr int GP_MAX_D = 4096;
 constexpr int GP_MAX_P = 4096;
@@ -44,6 +47,16 @@ __device__ __forceinline__ void gp_stat_phi_omega(float r2, float& phi, float& o
     phi = (1.f + s + s * s * (1.f / 3.f)) * e;
     omega = (5.f / 3.f) * (1.f + s) * e;
   }
+}
+
+inline bool gp_kind_known(int kind) { return kind == PG_GP_KIND_SE || kind == PG_GP_KIND_MATERN32 || kind == PG_GP_KIND_MATERN52; }
+
+// Calls f(std::integral_constant<int, kind>()) for a known kind: the one place where a run-time kind picks an instantiation.
+template <class F>
+void gp_with_kind(int kind, F&& f) {
+  if (kind == PG_GP_KIND_SE) f(std::integral_constant<int, PG_GP_KIND_SE>());
+  if (kind == PG_GP_KIND_MATERN32) f(std::integral_constant<int, PG_GP_KIND_MATERN32>());
+  if (kind == PG_GP_KIND_MATERN52) f(std::integral_constant<int, PG_GP_KIND_MATERN52>());
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -91,6 +104,122 @@ __device__ __forceinline__ void gp_mma_tile(const GpMma& p, int r0, int c0, floa
     }
   };
   PG_TILE_PIPELINE(GP_V, false, 0, (p.K + GP_KC - 1) / GP_KC, load, store, acc, s_a, s_b, ln, norms);  // every caller has K >= 1
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// GP_STAGE_ROWS: columns k0 .. k0 + kc of the rows ra0 .. ra0 + 63 of a and rb0 .. rb0 + 63 of b into LDS at row stride LD, zero
+// from row na (nb) on; the caller synchronises. A macro, so that the loop reaches the kernel as source: as a force-inlined
+// function it changed the code of gp_se_direct_kernel (tools/same_code_as.py), as a macro it does not.
+#define GP_STAGE_ROWS(LD, s_a, s_b, a, lda, ra0, na, b, ldb, rb0, nb, k0, kc, tid)                        \
+  for (int e_ = (tid); e_ < GP_T * (kc); e_ += GP_THREADS) {                                              \
+    const int r_ = e_ / (kc), k_ = e_ % (kc);                                                             \
+    (s_a)[r_ * (LD) + k_] = (ra0) + r_ < (na) ? (a)[(size_t)((ra0) + r_) * (lda) + (k0) + k_] : 0.f;      \
+    (s_b)[r_ * (LD) + k_] = (rb0) + r_ < (nb) ? (b)[(size_t)((rb0) + r_) * (ldb) + (k0) + k_] : 0.f;      \
+  }
+
+// The exact differences behind a lane's 16 MFMA outputs (the layout of PG_TILE_FOR_EACH_OUTPUT: 2 x 4 rows of a against 2 rows
+// of b, staged at row stride LD), scaled per column. fetch reads column k of those rows; diff is (a - b) wk, the difference
+// first; add_squares adds diff^2 to each output by one fmaf, so a sum over k is one chain in the order of the calls. Both passes
+// of the ARD reduction use it; the shared-lengthscale reduction keeps its unscaled loop written out (gp_mll.hip says why).
+template <int LD>
+struct GpLaneDiffs {
+  int ra[2][4], rb[2];
+  float av[2][4], bv[2];
+  __device__ __forceinline__ explicit GpLaneDiffs(const pg_tile::Lanes<GP_V>& ln) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) ra[i][q] = pg_tile::out_row<GP_V>(ln, i, q) * LD;
+      rb[i] = pg_tile::out_col<GP_V>(ln, i) * LD;
+    }
+  }
+  __device__ __forceinline__ void fetch(const float* s_a, const float* s_b, int k) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) av[i][q] = s_a[ra[i][q] + k];
+      bv[i] = s_b[rb[i] + k];
+    }
+  }
+  __device__ __forceinline__ float diff(int i, int j, int q, float wk) const {
+    return (av[i][q] - bv[j]) * wk;
+  }
+  __device__ __forceinline__ void add_squares(pg_tile::Acc<GP_V>& sq, float wk) const {
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const float df = diff(i, j, q, wk);
+          sq[i][j][q] = fmaf(df, df, sq[i][j][q]);
+        }
+  }
+};
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// The substitution against one diagonal block l (jb, jb), 64 rows of X per workgroup, four lanes per row, each with the columns
+// j = 4 q + (lane & 3) of its row in registers; x_k goes to the row's lanes by a shuffle. One fmaf chain per element, then one
+// IEEE division (no explicit inverse of the block).
+//   forward (BACK = false): X L^T = B, x_ij = (b_ij - sum_{k < j} x_ik l_jk) / l_jj, k ascending; columns < done are final.
+//   backward (BACK = true): X L = B,   x_ij = (b_ij - sum_{k > j} x_ik l_kj) / l_jj, k descending; done = 0.
+//   UNIT (forward, done = 0): a panel of X L^T = I. x points at column j0 = rows - jb of row 0; the workgroup of the diagonal
+//   block (rows j0 ..) starts from the identity instead of reading x and writes the columns on or right of the diagonal only;
+//   the others continue from the values the updates left.
+template <bool BACK, bool UNIT>
+__global__ void __launch_bounds__(GP_THREADS) gp_subst_diag_kernel(const float* __restrict__ l, long ld, float* __restrict__ x, long ldx,
+                                                                   int rows, int jb, int done_columns) {
+  static_assert(!(BACK && UNIT), "the identity right-hand side belongs to the forward form");
+  __shared__ float s_l[GP_T * GP_TRI_LD];
+  const int tid = threadIdx.x, lane = tid & 63;
+  for (int e = tid; e < GP_T * GP_T; e += GP_THREADS) {
+    const int j = e >> 6, k = e & 63;
+    float v = j == k ? 1.f : 0.f;  // rows beyond jb: the identity
+    if (j < jb && k <= j) v = l[(size_t)j * ld + k];
+    s_l[j * GP_TRI_LD + k] = v;
+  }
+  const int done = UNIT ? 0 : done_columns;
+  const int row = blockIdx.x * GP_T + (tid >> 2), c = tid & 3;
+  const bool unit = UNIT && (int)blockIdx.x * GP_T == rows - jb;
+  const int first = unit ? row - (rows - jb) : done;  // the first column this row writes
+  float v[16];
+#pragma unroll
+  for (int q = 0; q < 16; ++q) {
+    const int j = 4 * q + c;
+    float b = 0.f;
+    if (row < rows && j < jb) b = unit ? (j == first ? 1.f : 0.f) : x[(size_t)row * ldx + j];
+    v[q] = b;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int kk = 0; kk < GP_T; ++kk) {
+    const int k = BACK ? GP_T - 1 - kk : kk;
+    if (k < jb) {  // the same in every lane
+      const int qk = k >> 2, ck = k & 3;
+      float cand = v[qk];
+      if (BACK || k >= done) cand = cand / s_l[k * GP_TRI_LD + k];
+      const float xk = __shfl(cand, (lane & ~3) | ck);
+      if (c == ck) v[qk] = xk;
+      if (BACK) {
+#pragma unroll
+        for (int q = 0; q <= qk; ++q) {
+          const int j = 4 * q + c;
+          if (j < k) v[q] = fmaf(-xk, s_l[k * GP_TRI_LD + j], v[q]);
+        }
+      } else {
+#pragma unroll
+        for (int q = qk; q < 16; ++q) {
+          const int j = 4 * q + c;
+          if (j > k && j >= done) v[q] = fmaf(-xk, s_l[j * GP_TRI_LD + k], v[q]);
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < 16; ++q) {
+    const int j = 4 * q + c;
+    if (row < rows && j < jb && j >= first) x[(size_t)row * ldx + j] = v[q];
+  }
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------

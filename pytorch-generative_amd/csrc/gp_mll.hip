@@ -4,12 +4,12 @@
 //     G = alpha alpha^T - p K^-1,   d/d std = sum G K_f / std,   d/d l = sum G K_f D2 / (2 l^3),   d/d noise_var = tr G / 2.
 //
 // The triangular structure. K^-1 = X X^T with X = L^-T, which is UPPER triangular:
-//   * pg_gp_trtri_t solves X L^T = I right-looking in panels of 64 columns at absolute multiples of 64. Row r of X is zero left of
-//     column r, so panel k is solved for the rows above its end only: the diagonal block and the blocks above it by the fmaf
-//     chain plus one division of gp.hip's substitution on the VALU (the diagonal block starts from the identity and keeps its
-//     upper triangle), then the (k + 1) x (P - 1 - k) tiles to the right on the MFMA, seeded with x — with zero for the row
-//     tile k, which is touched for the first time. Element (r, c) is one chain (delta_rc - sum_{k < c} x_rk l_ck) / l_cc in
-//     ascending k, as in gp.hip.
+//   * pg_gp_trtri_t solves X L^T = I right-looking in panels of 64 columns at absolute multiples of 64. Row r of X is zero
+//     left of column r, so panel k is solved for the rows above its end only: the diagonal block and the blocks above it by
+//     the fmaf chain plus one division of gp_common.h's substitution on the VALU (gp_subst_diag_kernel<false, true>: the
+//     diagonal block starts from the identity and keeps its upper triangle), then the (k + 1) x (P - 1 - k) tiles to the
+//     right on the MFMA, seeded with x — with zero for the row tile k, which is touched for the first time. Element (r, c) is
+//     one chain (delta_rc - sum_{k < c} x_rk l_ck) / l_cc in ascending k, as in gp.hip.
 //   * pg_gp_gram_upper forms (X X^T)_ij = sum_{k >= max(i, j)} x_ik x_jk for the tiles on or below the diagonal; tile (I, J)
 //     starts its k loop at 64 I. What lies below the diagonal of x is garbage and is masked to zero on the way into LDS: it adds
 //     exact zeros to a chain in ascending k.
@@ -19,8 +19,8 @@
 //     three sums in a fixed order — lane (16 elements in the order of PG_TILE_FOR_EACH_OUTPUT), wave (shuffle tree), the four
 //     waves in order — to one fp32 partial row per tile. gp_mll_finish_kernel adds the rows in double: thread t the tiles t,
 //     t + 256, ... ascending, then a fixed tree over the 256 threads.
-//   * pg_gp_stat_mll_sums is the same reduction for the other stationary kinds with one shared lengthscale (the kind is a
-//     template parameter; pg_gp_se_mll_sums is the SE instantiation), and pg_gp_ard_mll_sums the one for per-dimension
+//   * pg_gp_stat_mll_sums is the same reduction for every stationary kind with one shared lengthscale (the kind is a
+//     template parameter; pg_gp_se_mll_sums is pg_gp_stat_mll_sums with kind SE), and pg_gp_ard_mll_sums the one for per-dimension
 //     lengthscales: d + 2 sums per tile, the per-dimension terms by exact differences on the VALU in two passes over the
 //     column chunks of x (gp_ard_mll_sums_kernel); gp_ard_plan decides its domain (d <= 256).
 // No float atomics, no host synchronisation, no allocation: capturable, bit-identical from run to run. gp_mll_plan is the one
@@ -56,54 +56,6 @@ __device__ __forceinline__ void mll_load_upper(pg_tile::Regs<GP_V>& reg, const f
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
-// Panel k of X L^T = I, columns j0 .. j0 + jb of the rows 0 .. j0 + jb: gp.hip's forward substitution against the diagonal block
-// l (jb, jb), 64 rows per workgroup, four lanes per row. x points at column j0 of row 0. The workgroup of the diagonal block
-// (rows j0 ..) starts from the identity and writes the columns on or right of the diagonal only; the others continue from the
-// values the updates left.
-__global__ void __launch_bounds__(GP_THREADS) gp_trtri_diag_kernel(const float* __restrict__ l, long ld, float* __restrict__ x, long ldx,
-                                                                   int j0, int jb) {
-  __shared__ float s_l[GP_T * GP_TRI_LD];
-  const int tid = threadIdx.x, lane = tid & 63;
-  for (int e = tid; e < GP_T * GP_T; e += GP_THREADS) {
-    const int j = e >> 6, k = e & 63;
-    float v = j == k ? 1.f : 0.f;  // rows beyond jb: the identity
-    if (j < jb && k <= j) v = l[(size_t)j * ld + k];
-    s_l[j * GP_TRI_LD + k] = v;
-  }
-  const int rows = j0 + jb;
-  const int row = blockIdx.x * GP_T + (tid >> 2), c = tid & 3;
-  const bool diag = (int)blockIdx.x * GP_T == j0;
-  const int first = diag ? row - j0 : 0;  // the first column of the panel this row owns
-  float v[16];
-#pragma unroll
-  for (int q = 0; q < 16; ++q) {
-    const int j = 4 * q + c;
-    float b = 0.f;
-    if (row < rows && j < jb) b = diag ? (j == first ? 1.f : 0.f) : x[(size_t)row * ldx + j];
-    v[q] = b;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < GP_T; ++k) {
-    if (k < jb) {  // the same in every lane
-      const int qk = k >> 2, ck = k & 3;
-      const float cand = v[qk] / s_l[k * GP_TRI_LD + k];
-      const float xk = __shfl(cand, (lane & ~3) | ck);
-      if (c == ck) v[qk] = xk;
-#pragma unroll
-      for (int q = qk; q < 16; ++q) {
-        const int j = 4 * q + c;
-        if (j > k) v[q] = fmaf(-xk, s_l[j * GP_TRI_LD + k], v[q]);
-      }
-    }
-  }
-#pragma unroll
-  for (int q = 0; q < 16; ++q) {
-    const int j = 4 * q + c;
-    if (row < rows && j < jb && j >= first) x[(size_t)row * ldx + j] = v[q];
-  }
-}
-
 // The update after panel k (j0 = 64 k): x[r][c] -= sum_{k' < 64} x[r][j0 + k'] l[c][j0 + k'] for the rows r < j0 + 64 and the
 // columns c >= j0 + 64, one 64 x 64 tile per workgroup. The row tile of the panel itself has not been written yet: it is
 // seeded with zero and its operand is the upper triangle of the diagonal block.
@@ -223,12 +175,11 @@ __global__ void __launch_bounds__(GP_THREADS) gp_se_mll_sums_kernel(const GpMllS
   pg_tile::Acc<GP_V> sq;
   pg_tile::zero<GP_V>(sq);
   if (ROUTE == 0) {
-    for (int e = tid; e < GP_T * p.d; e += GP_THREADS) {
-      const int r = e / p.d, k = e % p.d;
-      s_a[r * MLL_DIRECT_LD + k] = r0 + r < p.n ? p.x[(size_t)(r0 + r) * p.ldx + k] : 0.f;
-      s_b[r * MLL_DIRECT_LD + k] = c0 + r < p.n ? p.x[(size_t)(c0 + r) * p.ldx + k] : 0.f;
-    }
+    GP_STAGE_ROWS(MLL_DIRECT_LD, s_a, s_b, p.x, p.ldx, r0, p.n, p.x, p.ldx, c0, p.n, 0, p.d, tid);
     __syncthreads();
+    // Not an unscaled GpLaneDiffs, which is the same arithmetic: with it sums_ms of tools/gp_mll_bench.py at d = 1 read
+    // 1.01 / 1.06 / 1.05 of the parent at n = 8192 in three visits, beside 1.00 / 1.01 / 1.02 for the untouched MFMA route at
+    // d = 64 (profiles/gp_one_path.json). Written out, the kernel compiles to the parent's instructions.
     for (int k = 0; k < p.d; ++k) {
       float av[2][4], bv[2];
 #pragma unroll
@@ -334,21 +285,11 @@ __global__ void __launch_bounds__(GP_THREADS) gp_ard_mll_sums_kernel(const GpMll
   const int chunks = (p.d + GP_ARD_CHUNK - 1) / GP_ARD_CHUNK;
   auto stage = [&](int k0, int kc) {
     __syncthreads();  // the readers of the chunk before are done
-    for (int e = tid; e < GP_T * kc; e += GP_THREADS) {
-      const int r = e / kc, k = e % kc;
-      s_xa[r * ARD_LD + k] = r0 + r < p.n ? p.x[(size_t)(r0 + r) * p.ldx + k0 + k] : 0.f;
-      s_xb[r * ARD_LD + k] = c0 + r < p.n ? p.x[(size_t)(c0 + r) * p.ldx + k0 + k] : 0.f;
-    }
+    GP_STAGE_ROWS(ARD_LD, s_xa, s_xb, p.x, p.ldx, r0, p.n, p.x, p.ldx, c0, p.n, k0, kc, tid);
     if (tid < kc) s_w[tid] = p.w[k0 + tid];
     __syncthreads();
   };
-  int ra[2][4], rb[2];  // LDS offsets of the rows of x behind a thread's elements
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) ra[i][q] = pg_tile::out_row<GP_V>(ln, i, q) * ARD_LD;
-    rb[i] = pg_tile::out_col<GP_V>(ln, i) * ARD_LD;
-  }
+  GpLaneDiffs<ARD_LD> df(ln);  // the rows of x behind a thread's elements
 
   // pass 1: r^2, then the coefficients
   pg_tile::Acc<GP_V> sq;
@@ -357,23 +298,8 @@ __global__ void __launch_bounds__(GP_THREADS) gp_ard_mll_sums_kernel(const GpMll
     const int k0 = ch * GP_ARD_CHUNK, kc = min(GP_ARD_CHUNK, p.d - k0);
     stage(k0, kc);
     for (int k = 0; k < kc; ++k) {
-      const float wk = s_w[k];
-      float av[2][4], bv[2];
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) av[i][q] = s_xa[ra[i][q] + k];
-        bv[i] = s_xb[rb[i] + k];
-      }
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const float df = (av[i][q] - bv[j]) * wk;
-            sq[i][j][q] = fmaf(df, df, sq[i][j][q]);
-          }
+      df.fetch(s_xa, s_xb, k);
+      df.add_squares(sq, s_w[k]);
     }
   }
   float sum[2] = {0.f, 0.f};  // sum G K_f, tr G
@@ -402,13 +328,7 @@ __global__ void __launch_bounds__(GP_THREADS) gp_ard_mll_sums_kernel(const GpMll
     if (chunks > 1) stage(k0, kc);
     for (int k = 0; k < kc; ++k) {
       const float wk = s_w[k];
-      float av[2][4], bv[2];
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) av[i][q] = s_xa[ra[i][q] + k];
-        bv[i] = s_xb[rb[i] + k];
-      }
+      df.fetch(s_xa, s_xb, k);
       float s = 0.f;
 #pragma unroll
       for (int i = 0; i < 2; ++i)
@@ -416,8 +336,8 @@ __global__ void __launch_bounds__(GP_THREADS) gp_ard_mll_sums_kernel(const GpMll
         for (int j = 0; j < 2; ++j)
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
-            const float df = (av[i][q] - bv[j]) * wk;
-            s = fmaf(sq[i][j][q], df * df, s);
+            const float dv = df.diff(i, j, q, wk);
+            s = fmaf(sq[i][j][q], dv * dv, s);
           }
 #pragma unroll
       for (int off = 32; off >= 1; off >>= 1) s += __shfl_down(s, off);
@@ -587,8 +507,8 @@ PG_EXPORT int pg_gp_trtri_t(const float* l, long ld, int n, float* x, long ldx, 
   const hipStream_t st = (hipStream_t)stream;
   for (int k = 0; k < ml.panels; ++k) {
     const int j0 = k * GP_T, jb = std::min(GP_T, n - j0), right = ml.panels - 1 - k;
-    hipLaunchKernelGGL(gp_trtri_diag_kernel, dim3((unsigned)(k + 1)), dim3(GP_THREADS), 0, st, l + (size_t)j0 * ld + j0, ld, x + j0, ldx, j0,
-                       jb);
+    hipLaunchKernelGGL((gp_subst_diag_kernel<false, true>), dim3((unsigned)(k + 1)), dim3(GP_THREADS), 0, st, l + (size_t)j0 * ld + j0, ld,
+                       x + j0, ldx, j0 + jb, jb, 0);
     PG_LAUNCH_CHECK("pg_gp_trtri_t");
     if (right > 0) {
       hipLaunchKernelGGL(gp_trtri_update_kernel, dim3((unsigned)((k + 1) * right)), dim3(GP_THREADS), 0, st, l, ld, x, ldx, n, j0, right);
@@ -612,29 +532,21 @@ PG_EXPORT int pg_gp_gram_upper(const float* x, long ldx, int n, float* h, long l
 
 namespace {
 
-bool gp_kind_known(int kind) { return kind == PG_GP_KIND_SE || kind == PG_GP_KIND_MATERN32 || kind == PG_GP_KIND_MATERN52; }
-
-template <int KIND>
-void gp_stat_sums_launch(int route, unsigned tiles, hipStream_t st, const GpMllSumsArgs& a) {
-  if (route == 0)
-    hipLaunchKernelGGL((gp_se_mll_sums_kernel<0, KIND>), dim3(tiles), dim3(GP_THREADS), 0, st, a);
-  else
-    hipLaunchKernelGGL((gp_se_mll_sums_kernel<1, KIND>), dim3(tiles), dim3(GP_THREADS), 0, st, a);
-}
-
-// the one launch path of pg_gp_se_mll_sums (kind SE) and pg_gp_stat_mll_sums
-int gp_stat_mll_sums(const char* name, int kind, const float* x, long ldx, int n, int d, float std, float lengthscale, const float* h, long ldh,
-                     const float* alpha_t, long lda, int p, float* ws, size_t ws_floats, float* out, void* stream) {
-  GP_MLL_PLAN_OR_RETURN(ml, n, d, p, name);
+// What the two reductions check after their plan accepted the call, and the arguments of their kernels. inv_ls: the per-dimension
+// reduction's 1 / l (`ard`; the scalar lengthscale is then 1 and not checked), else NULL. A missing device is reported last.
+int gp_mll_sums_args(const char* name, int kind, const float* x, long ldx, int n, int d, float std, float lengthscale, bool ard,
+                     const float* inv_ls, const float* h, long ldh, const float* alpha_t, long lda, int p, float* ws, size_t ws_floats,
+                     long ws_needed, const float* out, GpMllSumsArgs& a) {
   PG_REQUIRE(gp_kind_known(kind), PG_EINVAL, "%s: kind %d is none of PG_GP_KIND_*", name, kind);
-  PG_REQUIRE(x && h && alpha_t && ws && out, PG_EINVAL, "%s: null pointer", name);
+  PG_REQUIRE(x && (inv_ls || !ard) && h && alpha_t && ws && out, PG_EINVAL, "%s: null pointer", name);
   PG_REQUIRE(ldx >= d && ldh >= n && lda >= n, PG_EINVAL, "%s: a row stride below its row length", name);
-  PG_REQUIRE(lengthscale > 0.f && std == std && std != 0.f, PG_EINVAL, "%s: lengthscale = %g must be > 0, std = %g no NaN and not 0", name,
-             (double)lengthscale, (double)std);
-  PG_REQUIRE(ws_floats >= (size_t)ml.ws_floats, PG_EINVAL, "%s: the workspace holds %zu floats, %ld are needed", name, ws_floats, ml.ws_floats);
+  if (ard)
+    PG_REQUIRE(std == std && std != 0.f, PG_EINVAL, "%s: std = %g no NaN and not 0", name, (double)std);
+  else
+    PG_REQUIRE(lengthscale > 0.f && std == std && std != 0.f, PG_EINVAL, "%s: lengthscale = %g must be > 0, std = %g no NaN and not 0", name,
+               (double)lengthscale, (double)std);
+  PG_REQUIRE(ws_floats >= (size_t)ws_needed, PG_EINVAL, "%s: the workspace holds %zu floats, %ld are needed", name, ws_floats, ws_needed);
   GP_TRY(gp_device(name));
-  const hipStream_t st = (hipStream_t)stream;
-  GpMllSumsArgs a;
   a.x = x;
   a.h = h;
   a.at = alpha_t;
@@ -649,10 +561,24 @@ int gp_stat_mll_sums(const char* name, int kind, const float* x, long ldx, int n
   a.neg_inv = -0.5f / (lengthscale * lengthscale);
   a.pf = (float)p;
   a.inv_l2 = 1.f / (lengthscale * lengthscale);
-  a.w = nullptr;
-  if (kind == PG_GP_KIND_SE) gp_stat_sums_launch<PG_GP_KIND_SE>(ml.se_route, (unsigned)ml.tiles, st, a);
-  if (kind == PG_GP_KIND_MATERN32) gp_stat_sums_launch<PG_GP_KIND_MATERN32>(ml.se_route, (unsigned)ml.tiles, st, a);
-  if (kind == PG_GP_KIND_MATERN52) gp_stat_sums_launch<PG_GP_KIND_MATERN52>(ml.se_route, (unsigned)ml.tiles, st, a);
+  a.w = inv_ls;
+  return 0;
+}
+
+// the one launch path of pg_gp_se_mll_sums (kind SE) and pg_gp_stat_mll_sums
+int gp_stat_mll_sums(const char* name, int kind, const float* x, long ldx, int n, int d, float std, float lengthscale, const float* h, long ldh,
+                     const float* alpha_t, long lda, int p, float* ws, size_t ws_floats, float* out, void* stream) {
+  GP_MLL_PLAN_OR_RETURN(ml, n, d, p, name);
+  GpMllSumsArgs a;
+  GP_TRY(gp_mll_sums_args(name, kind, x, ldx, n, d, std, lengthscale, false, nullptr, h, ldh, alpha_t, lda, p, ws, ws_floats, ml.ws_floats, out, a));
+  const hipStream_t st = (hipStream_t)stream;
+  const dim3 grid((unsigned)ml.tiles), block(GP_THREADS);
+  gp_with_kind(kind, [&](auto K) {
+    if (ml.se_route == 0)
+      hipLaunchKernelGGL((gp_se_mll_sums_kernel<0, decltype(K)::value>), grid, block, 0, st, a);
+    else
+      hipLaunchKernelGGL((gp_se_mll_sums_kernel<1, decltype(K)::value>), grid, block, 0, st, a);
+  });
   PG_LAUNCH_CHECK(name);
   const double l3 = (double)lengthscale * (double)lengthscale * (double)lengthscale;
   const double scale = kind == PG_GP_KIND_SE ? 0.5 / l3 : 0.5 / (double)lengthscale;
@@ -693,33 +619,11 @@ PG_EXPORT int pg_gp_ard_mll_sums(int kind, const float* x, long ldx, int n, int 
   const char* name = "pg_gp_ard_mll_sums";
   GpArdPlan ap;
   GP_TRY(gp_ard_plan(n, d, p, ap, name));
-  PG_REQUIRE(gp_kind_known(kind), PG_EINVAL, "%s: kind %d is none of PG_GP_KIND_*", name, kind);
-  PG_REQUIRE(x && inv_ls && h && alpha_t && ws && out, PG_EINVAL, "%s: null pointer", name);
-  PG_REQUIRE(ldx >= d && ldh >= n && lda >= n, PG_EINVAL, "%s: a row stride below its row length", name);
-  PG_REQUIRE(std == std && std != 0.f, PG_EINVAL, "%s: std = %g no NaN and not 0", name, (double)std);
-  PG_REQUIRE(ws_floats >= (size_t)ap.ws_floats, PG_EINVAL, "%s: the workspace holds %zu floats, %ld are needed", name, ws_floats, ap.ws_floats);
-  GP_TRY(gp_device(name));
-  const hipStream_t st = (hipStream_t)stream;
   GpMllSumsArgs a;
-  a.x = x;
-  a.h = h;
-  a.at = alpha_t;
-  a.ws = ws;
-  a.ldx = ldx;
-  a.ldh = ldh;
-  a.lda = lda;
-  a.n = n;
-  a.d = d;
-  a.p = p;
-  a.std2 = std * std;
-  a.neg_inv = -0.5f;
-  a.pf = (float)p;
-  a.inv_l2 = 1.f;
-  a.w = inv_ls;
+  GP_TRY(gp_mll_sums_args(name, kind, x, ldx, n, d, std, 1.f, true, inv_ls, h, ldh, alpha_t, lda, p, ws, ws_floats, ap.ws_floats, out, a));
+  const hipStream_t st = (hipStream_t)stream;
   const dim3 grid((unsigned)ap.tiles), block(GP_THREADS);
-  if (kind == PG_GP_KIND_SE) hipLaunchKernelGGL(gp_ard_mll_sums_kernel<PG_GP_KIND_SE>, grid, block, 0, st, a);
-  if (kind == PG_GP_KIND_MATERN32) hipLaunchKernelGGL(gp_ard_mll_sums_kernel<PG_GP_KIND_MATERN32>, grid, block, 0, st, a);
-  if (kind == PG_GP_KIND_MATERN52) hipLaunchKernelGGL(gp_ard_mll_sums_kernel<PG_GP_KIND_MATERN52>, grid, block, 0, st, a);
+  gp_with_kind(kind, [&](auto K) { hipLaunchKernelGGL(gp_ard_mll_sums_kernel<decltype(K)::value>, grid, block, 0, st, a); });
   PG_LAUNCH_CHECK(name);
   hipLaunchKernelGGL(gp_ard_finish_kernel, dim3((unsigned)ap.row_floats), block, 0, st, (const float*)ws, (int)ap.tiles, (int)ap.row_floats,
                      1.0 / (double)std, inv_ls, out);

@@ -19,16 +19,16 @@ Stated deviations from the reference:
   * `predict` and `sample` carry no gradient, and an input that requires grad raises: there are no gradients with respect to
     x or y.
   * The reference has no marginal likelihood. Here `log_marginal_likelihood()` gives log p(y) of the fitted data from the
-    cached factor, as an autograd node over std, lengthscale, the constant mean and noise_var (the "se" and "stationary"
-    routes), and `optimize_hyperparameters()` runs Adam on their logarithms. With
+    cached factor, as an autograd node over std, lengthscale, the constant mean and noise_var (every route but "callable"),
+    and `optimize_hyperparameters()` runs Adam on their logarithms. With
     G = alpha alpha^T - p K^-1 the gradients are sum G K_f / std, sum G K_f D2 / (2 l^3), tr G / 2 and sum alpha;
     K^-1 = X X^T comes from the triangular inverse X = L^-T (ops.tri_inverse_t, ops.gram_upper_) and the sums from one fused
-    reduction that writes no derivative matrix (ops.se_mll_sums, csrc/gp_mll.hip). The inverse is made for the call and freed;
+    reduction that writes no derivative matrix (ops.stationary_mll_sums, csrc/gp_mll.hip). The inverse is made for the call and freed;
     it is not appended to after a `fit`.
   * The reference has one kernel, in its notebook. Here SquaredExponential also takes one lengthscale PER INPUT COLUMN (ARD) and
-    Matern (nu = 3/2, 5/2) stands beside it; both run on ops.stationary_kernel ("stationary" route) with everything the "se"
-    route has — the appended factor, the evidence, its gradients (d/d l_c = S_c / (2 l_c) from ops.ard_mll_sums, up to 256
-    columns) and the optimiser.
+    Matern (nu = 3/2, 5/2) stands beside it; every stationary kernel runs on ops.stationary_kernel, one code path with the
+    appended factor, the evidence, its gradients (d/d l_c = S_c / (2 l_c) from ops.ard_mll_sums, up to 256 columns) and the
+    optimiser.
   * `sample` draws on the GPU from torch's generator and returns fp32 on the device (the reference: float64 from numpy).
 SquaredExponential and Const restate the two callables the reference defines only in its notebook."""
 
@@ -119,18 +119,12 @@ class _Stationary(nn.Module):
 
 class SquaredExponential(_Stationary):
     """k(a, b) = std^2 exp(-|a - b|^2 / (2 lengthscale^2)). std and lengthscale: floats, tensors, or (default) Parameters
-    initialised to 1. Called on 2-D GPU tensors it returns the (rows of left, rows of right) covariance from ops.se_kernel;
-    `kernel(x, x)` (the same tensor twice) is exactly symmetric with the diagonal exactly std^2. A 1-D lengthscale of d entries
-    (or n_dims = d: a Parameter of d ones) gives every input column its own, k = std^2 exp(-sum_c ((a_c - b_c) / l_c)^2 / 2),
-    from ops.stationary_kernel."""
+    initialised to 1. Called on 2-D GPU tensors it returns the (rows of left, rows of right) covariance from
+    ops.stationary_kernel; `kernel(x, x)` (the same tensor twice) is exactly symmetric with the diagonal exactly std^2. A 1-D
+    lengthscale of d entries (or n_dims = d: a Parameter of d ones) gives every input column its own,
+    k = std^2 exp(-sum_c ((a_c - b_c) / l_c)^2 / 2)."""
 
     kind = "se"
-
-    def forward(self, left, right):
-        if self.ard:
-            return self.covariance(left, right)
-        std, lengthscale = self.hyperparameters()
-        return ops.se_kernel(left, right, std, lengthscale)
 
 
 class Matern(_Stationary):
@@ -191,11 +185,12 @@ class GaussianProcess(base.GenerativeModel):
     that state call reset_cache() — otherwise a cached factor keeps serving `predict` (a SquaredExponential or Const beside such a
     callable is still watched: a change of its values makes the factor afresh). incremental = False is always safe.
 
-    `_kernel_route` is "se" (SquaredExponential kernel with one shared lengthscale and Const mean: covariances straight from
-    ops.se_kernel), "stationary" (a Matern kernel, or a SquaredExponential with one lengthscale per input column, and Const
-    mean: covariances straight from ops.stationary_kernel; it appends, evaluates and learns exactly as "se" does) or
-    "callable" (the callables are called on the device tensors; a square result kernel(t, t) is copied as it is, but only its
-    lower triangle is read: the factorisation and the covariance update never look above the diagonal, the output is mirrored)."""
+    `_kernel_route` is a label for what was built, not a code path: "se" (SquaredExponential kernel with one shared
+    lengthscale and Const mean) and "stationary" (a Matern kernel, or a SquaredExponential with one lengthscale per input
+    column, and Const mean) run the same code — covariances straight from kernel.covariance (ops.stationary_kernel), the
+    appended factor, the evidence and the optimiser; the code asks only whether the route is "callable" (the callables are
+    called on the device tensors; a square result kernel(t, t) is copied as it is, but only its lower triangle is read: the
+    factorisation and the covariance update never look above the diagonal, the output is mirrored)."""
 
     incremental = True
 
@@ -246,29 +241,20 @@ class GaussianProcess(base.GenerativeModel):
     def _cross(self, x):
         """kernel(x, train), (m, n), in memory of its own (the solve overwrites it)."""
         if self._kernel_route != "callable":
-            return self.kernel(x, self.train_x)
+            return self.kernel.covariance(x, self.train_x)
         out = self.kernel(x, self.train_x)
         return out.clone() if out.is_contiguous() else out.contiguous()
 
     def _prior(self, x, mirror):
         """kernel(x, x), (m, m), in memory of its own; with mirror=False only its lower triangle is promised."""
-        if self._kernel_route == "se":
-            std, lengthscale = self.kernel.hyperparameters()
-            return ops.se_kernel(x, x, std, lengthscale, mirror=mirror)
-        if self._kernel_route == "stationary":
+        if self._kernel_route != "callable":
             return self.kernel.covariance(x, x, mirror=mirror)
         return self.kernel(x, x).clone(memory_format=torch.contiguous_format)
 
     def _train_rows(self, lo, hi, out, noise):
         """Rows lo .. hi of kernel(train, train) + noise I into out (hi - lo, hi): columns 0 .. their own."""
         x = self.train_x
-        if self._kernel_route == "se":
-            std, lengthscale = self.kernel.hyperparameters()
-            if lo == 0:
-                ops.se_kernel(x, x, std, lengthscale, noise, out=out, mirror=False)
-            else:
-                ops.se_kernel(x[lo:hi], x, std, lengthscale, noise, out=out, diag_offset=lo)
-        elif self._kernel_route == "stationary":
+        if self._kernel_route != "callable":
             if lo == 0:
                 self.kernel.covariance(x, x, noise, out=out, mirror=False)
             else:
@@ -382,8 +368,8 @@ class GaussianProcess(base.GenerativeModel):
 
     # -- the marginal likelihood -------------------------------------------------------------------------------------------
     def _hyper_slots(self):
-        """(entry of the gradient vector, owner, attribute, positive) of the hyperparameters: the four entries 0 .. 3 of the
-        "se" route and of one shared lengthscale; with d per-dimension lengthscales the vector has 3 + d entries, noise_var
+        """(entry of the gradient vector, owner, attribute, positive) of the hyperparameters: the four entries 0 .. 3 of one
+        shared lengthscale; with d per-dimension lengthscales the vector has 3 + d entries, noise_var
         at 2 and the lengthscales in the slice 3 .. 3 + d."""
         if self.kernel.ard:
             d = self.kernel.lengthscale.numel()
@@ -421,9 +407,7 @@ class GaussianProcess(base.GenerativeModel):
         ops.tri_inverse_t(lower, out=inverse_t)
         ops.gram_upper_(precision, inverse_t)
         del inverse_t
-        if self._kernel_route == "se":
-            ops.se_mll_sums(self.train_x, std, lengthscale, precision, alpha_t, out=out[2:])
-        elif ard:
+        if ard:
             ops.ard_mll_sums(self.train_x, std, None, precision, alpha_t, kind=self.kernel.kind, out=out[2:],
                              inv_lengthscale=_device_inverse(self.kernel, "lengthscale", out.device))
         else:
@@ -445,11 +429,11 @@ class GaussianProcess(base.GenerativeModel):
 
         With grad enabled the result is an autograd node over those of kernel.std, kernel.lengthscale, mean.value and
         noise_var that are tensors requiring grad (noise_var is a buffer: `gp.noise_var.requires_grad_()` opts it in; a
-        hyperparameter held as a Python float gets no gradient). The forward then also makes the gradients — the inverse of the
-        factor, K^-1 and the fused reduction, O(n^3) and two (n, n) workspaces that are freed before it returns — and the
-        backward only scales them by grad_output. Under no_grad, or when nothing requires grad, the value alone is computed.
-        No gradients with respect to x or y. The "se" and "stationary" routes: NotImplementedError for a callable kernel or
-        mean. A 1-D lengthscale receives a gradient of its own shape, (d,), for d <= 256 (ValueError above)."""
+        hyperparameter held as a Python float gets no gradient). The forward then also makes the gradients — the inverse of
+        the factor, K^-1 and the fused reduction, O(n^3) and two (n, n) workspaces that are freed before it returns — and
+        the backward only scales them by grad_output. Under no_grad, or when nothing requires grad, the value alone is
+        computed. No gradients with respect to x or y. NotImplementedError for a callable kernel or mean (the "callable"
+        route). A 1-D lengthscale receives a gradient of its own shape, (d,), for d <= 256 (ValueError above)."""
         self._require_evidence("log_marginal_likelihood")
         wanted = []
         if torch.is_grad_enabled():

@@ -25,11 +25,17 @@ _PLAN_FIELDS = ("tile", "k_chunk", "panels", "row_tiles", "se_route", "se_direct
 _SE_ROUTES = {None: 0, "direct": GP_SE_DIRECT, "mfma": GP_SE_MFMA}
 
 
+def _plan_status(entry, ints, fields, *dims):
+    """(status, plan) of the host-only planner `entry`: its C-ABI status (0, PG_ESHAPE = -2, PG_EINVAL = -1) and the plan dict
+    (None on error)."""
+    out = (ctypes.c_longlong * ints)()
+    rc = getattr(_lib.load(), entry)(*map(int, dims), out, ints)
+    return rc, (None if rc else dict(zip(fields, out)))
+
+
 def gp_plan_status(n, m, d, p):
-    """(status, plan): the C-ABI status of pg_gp_plan (0, PG_ESHAPE = -2, PG_EINVAL = -1) and the plan dict (None on error)."""
-    out = (ctypes.c_longlong * GP_PLAN_INTS)()
-    rc = _lib.load().pg_gp_plan(int(n), int(m), int(d), int(p), out, GP_PLAN_INTS)
-    return rc, (None if rc else dict(zip(_PLAN_FIELDS, out)))
+    """(status, plan) of pg_gp_plan, see _plan_status."""
+    return _plan_status("pg_gp_plan", GP_PLAN_INTS, _PLAN_FIELDS, n, m, d, p)
 
 
 def gp_plan(n, m, d, p):
@@ -68,35 +74,9 @@ def se_kernel(a, b, std, lengthscale, noise_var=0.0, *, out=None, mirror=True, d
     diag_offset = o (cross form): only the elements j <= i + o are written and the elements j == i + o are exactly
     std^2 + noise_var — rows of a larger symmetric matrix. Otherwise every element is written and noise_var is not used.
     route: None (ops.gp_plan decides: exact differences for d <= 16, |a|^2 + |b|^2 - 2 a.b on the MFMA above), "direct"
-    (d <= 64) or "mfma". One launch, capturable, bit-identical from run to run; an element depends on its two rows alone."""
-    a, lda = _mat(a, "se_kernel.a")
-    sym = b is a
-    b, ldb = (a, lda) if sym else _mat(b, "se_kernel.b")
-    n, d = a.shape
-    m = b.shape[0]
-    if b.shape[1] != d:
-        raise ValueError(f"se_kernel: a has {d} columns, b {b.shape[1]}")
-    if route not in _SE_ROUTES:
-        raise ValueError(f"se_kernel: route {route!r} is none of None, 'direct', 'mfma'")
-    rc, _ = gp_plan_status(n, m, d, 1)
-    _lib.check(rc, "se_kernel")
-    if out is None:
-        out = torch.empty((n, m), device=a.device, dtype=torch.float32)
-    out, ldk = _mat(out, "se_kernel.out")
-    if tuple(out.shape) != (n, m):
-        raise ValueError(f"se_kernel: out of shape {tuple(out.shape)}, expected {(n, m)}")
-    flags = _SE_ROUTES[route]
-    off = 0
-    if sym:
-        if diag_offset is not None:
-            raise ValueError("se_kernel: diag_offset belongs to the cross form")
-        flags |= GP_LOWER | GP_DIAG | (GP_MIRROR if mirror else 0)
-    elif diag_offset is not None:
-        flags |= GP_LOWER | GP_DIAG
-        off = int(diag_offset)
-    _lib.check(_lib.load().pg_gp_se_kernel(a.data_ptr(), lda, n, b.data_ptr(), ldb, m, d, float(std), float(lengthscale), float(noise_var),
-                                           out.data_ptr(), ldk, off, flags, _stream()), "pg_gp_se_kernel")
-    return out
+    (d <= 64) or "mfma". One launch, capturable, bit-identical from run to run; an element depends on its two rows alone.
+    stationary_kernel with kind "se" under this function's name."""
+    return _stationary_kernel("se_kernel", a, b, std, float(lengthscale), noise_var, "se", out, mirror, diag_offset, route, None)
 
 
 def add_diag_(a, value):
@@ -177,10 +157,8 @@ _MLL_PLAN_FIELDS = ("tile", "panels", "inverse_launches", "inverse_tile_products
 
 
 def gp_mll_plan_status(n, d, p):
-    """(status, plan): the C-ABI status of pg_gp_mll_plan (0, PG_ESHAPE = -2, PG_EINVAL = -1) and the plan dict (None on error)."""
-    out = (ctypes.c_longlong * GP_MLL_PLAN_INTS)()
-    rc = _lib.load().pg_gp_mll_plan(int(n), int(d), int(p), out, GP_MLL_PLAN_INTS)
-    return rc, (None if rc else dict(zip(_MLL_PLAN_FIELDS, out)))
+    """(status, plan) of pg_gp_mll_plan, see _plan_status."""
+    return _plan_status("pg_gp_mll_plan", GP_MLL_PLAN_INTS, _MLL_PLAN_FIELDS, n, d, p)
 
 
 def gp_mll_plan(n, d, p):
@@ -251,26 +229,8 @@ def se_mll_sums(x, std, lengthscale, h, alpha_t, *, out=None, workspace=None):
     and noise_var. One workgroup per 64 x 64 tile on or below the diagonal recomputes the distances (se_kernel's routes and
     bits), so neither K_f, its derivative nor G is written to memory; `workspace` (ops.gp_mll_plan's workspace_floats, made if
     not given) takes one fp32 partial row per tile, which a second launch adds in double in a fixed order. No atomics:
-    bit-identical from run to run. Two launches, capturable."""
-    x, ldx = _mat(x, "se_mll_sums.x")
-    h, ldh = _square(h, "se_mll_sums.h")
-    alpha_t, lda = _mat(alpha_t, "se_mll_sums.alpha_t")
-    n, d = x.shape
-    p = alpha_t.shape[0]
-    if h.shape[0] != n or alpha_t.shape[1] != n:
-        raise ValueError(f"se_mll_sums: x {tuple(x.shape)}, h {tuple(h.shape)} and alpha_t {tuple(alpha_t.shape)} do not fit")
-    rc, plan = gp_mll_plan_status(n, d, p)
-    _lib.check(rc, "se_mll_sums")
-    if workspace is None:
-        workspace = torch.empty(plan["workspace_floats"], device=x.device, dtype=torch.float32)
-    workspace = _vec(workspace, plan["workspace_floats"], "se_mll_sums.workspace", at_least=True)
-    if out is None:
-        out = torch.empty(3, device=x.device, dtype=torch.float32)
-    out = _vec(out, 3, "se_mll_sums.out")
-    _lib.check(_lib.load().pg_gp_se_mll_sums(x.data_ptr(), ldx, n, d, float(std), float(lengthscale), h.data_ptr(), ldh, alpha_t.data_ptr(),
-                                             lda, p, workspace.data_ptr(), workspace.numel(), out.data_ptr(), _stream()),
-               "pg_gp_se_mll_sums")
-    return out
+    bit-identical from run to run. Two launches, capturable. stationary_mll_sums with kind "se" under this function's name."""
+    return _stationary_mll_sums("se_mll_sums", x, std, lengthscale, h, alpha_t, "se", out, workspace)
 
 
 def mll_value(l, zt, alpha_t, *, out=None):
@@ -300,10 +260,8 @@ _ARD_PLAN_FIELDS = ("tile", "sums_tiles", "partial_row_floats", "workspace_float
 
 
 def gp_ard_plan_status(n, d, p):
-    """(status, plan): the C-ABI status of pg_gp_ard_plan (0, PG_ESHAPE = -2, PG_EINVAL = -1) and the plan dict (None on error)."""
-    out = (ctypes.c_longlong * GP_ARD_PLAN_INTS)()
-    rc = _lib.load().pg_gp_ard_plan(int(n), int(d), int(p), out, GP_ARD_PLAN_INTS)
-    return rc, (None if rc else dict(zip(_ARD_PLAN_FIELDS, out)))
+    """(status, plan) of pg_gp_ard_plan, see _plan_status."""
+    return _plan_status("pg_gp_ard_plan", GP_ARD_PLAN_INTS, _ARD_PLAN_FIELDS, n, d, p)
 
 
 def gp_ard_plan(n, d, p):
@@ -342,9 +300,13 @@ def stationary_kernel(a, b, std, lengthscale, noise_var=0.0, *, kind="se", out=N
     `b is a`, mirror, diag_offset, out and route are se_kernel's, with the same promises: the diagonal exactly std^2 + noise_var,
     exact symmetry, an element's bits depending on its two rows and the lengthscales alone. The exact-difference route
     (d <= 16, forced up to 64) scales the DIFFERENCE, so inputs far from the origin lose nothing and a duplicated row gives
-    exactly std^2; the MFMA route scales the rows while staging them. kind "se" with a float lengthscale is se_kernel, bit for
-    bit. One launch, capturable, bit-identical from run to run."""
-    name = "stationary_kernel"
+    exactly std^2; the MFMA route scales the rows while staging them. kind "se" with a float lengthscale is se_kernel. One
+    launch, capturable, bit-identical from run to run."""
+    return _stationary_kernel("stationary_kernel", a, b, std, lengthscale, noise_var, kind, out, mirror, diag_offset, route, inv_lengthscale)
+
+
+def _stationary_kernel(name, a, b, std, lengthscale, noise_var, kind, out, mirror, diag_offset, route, inv_lengthscale):
+    """stationary_kernel, and se_kernel with kind "se", under the `name` their messages carry."""
     a, lda = _mat(a, f"{name}.a")
     sym = b is a
     b, ldb = (a, lda) if sym else _mat(b, f"{name}.b")
@@ -387,24 +349,33 @@ def _sums_operands(x, h, alpha_t, name):
     return x, ldx, h, ldh, alpha_t, lda
 
 
+def _sums_buffers(workspace, out, plan, out_floats, device, name):
+    """The workspace (at least the plan's workspace_floats) and `out` (out_floats) of a reduction: made if None, else checked."""
+    if workspace is None:
+        workspace = torch.empty(plan["workspace_floats"], device=device, dtype=torch.float32)
+    workspace = _vec(workspace, plan["workspace_floats"], f"{name}.workspace", at_least=True)
+    if out is None:
+        out = torch.empty(out_floats, device=device, dtype=torch.float32)
+    return workspace, _vec(out, out_floats, f"{name}.out")
+
+
 def stationary_mll_sums(x, std, lengthscale, h, alpha_t, *, kind="se", out=None, workspace=None):
     """se_mll_sums for any kind of stationary_kernel with one shared lengthscale (a float): the 1-D tensor
         (sum_ij G_ij K_f,ij / std,  sum_ij G_ij std^2 omega(r_ij) r_ij^2 / (2 lengthscale),  tr G / 2),   omega = -phi'(r) / r,
     the gradients of the log marginal likelihood with respect to std, lengthscale and noise_var. Same operands, workspace
-    (ops.gp_mll_plan) and promises; kind "se" is se_mll_sums, bit for bit. Two launches, capturable."""
-    name = "stationary_mll_sums"
+    (ops.gp_mll_plan) and promises; kind "se" is se_mll_sums. Two launches, capturable."""
+    return _stationary_mll_sums("stationary_mll_sums", x, std, lengthscale, h, alpha_t, kind, out, workspace)
+
+
+def _stationary_mll_sums(name, x, std, lengthscale, h, alpha_t, kind, out, workspace):
+    """stationary_mll_sums, and se_mll_sums with kind "se", under the `name` their messages carry."""
     x, ldx, h, ldh, alpha_t, lda = _sums_operands(x, h, alpha_t, name)
     n, d = x.shape
     p = alpha_t.shape[0]
     code = _kind(kind, name)
     rc, plan = gp_mll_plan_status(n, d, p)
     _lib.check(rc, name)
-    if workspace is None:
-        workspace = torch.empty(plan["workspace_floats"], device=x.device, dtype=torch.float32)
-    workspace = _vec(workspace, plan["workspace_floats"], f"{name}.workspace", at_least=True)
-    if out is None:
-        out = torch.empty(3, device=x.device, dtype=torch.float32)
-    out = _vec(out, 3, f"{name}.out")
+    workspace, out = _sums_buffers(workspace, out, plan, 3, x.device, name)
     _lib.check(_lib.load().pg_gp_stat_mll_sums(code, x.data_ptr(), ldx, n, d, float(std), float(lengthscale), h.data_ptr(), ldh,
                                                alpha_t.data_ptr(), lda, p, workspace.data_ptr(), workspace.numel(), out.data_ptr(), _stream()),
                "pg_gp_stat_mll_sums")
@@ -432,12 +403,7 @@ def ard_mll_sums(x, std, lengthscale, h, alpha_t, *, kind="se", out=None, worksp
     _, inv = _lengthscale(lengthscale, inv_lengthscale, d, name)
     rc, plan = gp_ard_plan_status(n, d, p)
     _lib.check(rc, name)
-    if workspace is None:
-        workspace = torch.empty(plan["workspace_floats"], device=x.device, dtype=torch.float32)
-    workspace = _vec(workspace, plan["workspace_floats"], f"{name}.workspace", at_least=True)
-    if out is None:
-        out = torch.empty(d + 2, device=x.device, dtype=torch.float32)
-    out = _vec(out, d + 2, f"{name}.out")
+    workspace, out = _sums_buffers(workspace, out, plan, d + 2, x.device, name)
     _lib.check(_lib.load().pg_gp_ard_mll_sums(code, x.data_ptr(), ldx, n, d, float(std), inv.data_ptr(), h.data_ptr(), ldh, alpha_t.data_ptr(),
                                               lda, p, workspace.data_ptr(), workspace.numel(), out.data_ptr(), _stream()),
                "pg_gp_ard_mll_sums")

@@ -1,20 +1,26 @@
-"""Do two builds of the library give the same bits on the fp32-MFMA tile kernels (csrc/mfma_tile.h: dense_linear, fvbn, gp)?
+"""Do two builds of the library give the same bits on the fp32-MFMA tile kernels (csrc/mfma_tile.h: dense_linear, fvbn, gp) and
+on everything the Gaussian process runs?
 
-    PG_HIP_LIB=<library A> timeout -k 10 240 python tools/tile_bits.py --label A --out A.json \\
+    PG_HIP_LIB=<library A> timeout -k 10 240 python tools/tile_bits.py --label A --out A.json [--package <tree A>] \\
       && PG_HIP_LIB=<library B> timeout -k 10 240 python tools/tile_bits.py --label B --out B.json \\
       && python tools/tile_bits.py --compare A.json B.json [--verdict verdict.json]   # exit code 1 on any difference
 
 One process per library (_lib loads one only), each under its own time limit, chained so that nothing starts after a failure.
 The other library is built from an earlier commit with build.py's flags, outside the tree:
-    mkdir -p /tmp/pg_parent && git archive <commit> pytorch-generative_amd/build.py pytorch-generative_amd/csrc include \\
-      | tar -x -C /tmp/pg_parent && python /tmp/pg_parent/pytorch-generative_amd/build.py
+    mkdir -p /tmp/pg_parent && git archive <commit> pytorch-generative_amd include | tar -x -C /tmp/pg_parent \\
+      && python /tmp/pg_parent/pytorch-generative_amd/build.py
     # -> /tmp/pg_parent/pytorch-generative_amd/pytorch_generative_amd/lib/libpg_hip.so
+--package /tmp/pg_parent/pytorch-generative_amd imports pytorch_generative_amd from that directory instead of the working tree,
+so that the earlier commit's Python layer (operators, model) runs on its own library; the cases only use names both have.
 
 For a fixed list of cases the inputs come from seeded CPU generators, the entry points run once and the JSON holds the sha256 of
 every output's raw bytes. The cases are the shape lists with which the GPU tests reach every branch of the three plans
 (tests/test_gpu_nice.py DIRECT_SHAPES and its two extra weight-gradient shapes, tests/test_gpu_fvbn.py SHAPES,
 tests/test_gpu_gp.py FACTOR_N, its append pairs, its GEMM update and its covariance at d = 17, 40); the dense list is checked
-against pg_dense_linear_plan to reach small-unsplit, small-k-split and large for every kind, and the record says so."""
+against pg_dense_linear_plan to reach small-unsplit, small-k-split and large for every kind, and the record says so. The
+Gaussian process is covered beyond the tile: every covariance entry point, kind, lengthscale form and route on both sides of
+the route threshold (gp_covariance), the triangular inverse and X X^T over one to three panels (gp_inverse), the three
+reductions through the C-ABI with the workspace rows they write (gp_sums), the value, and three models end to end (gp_models)."""
 
 import argparse
 import hashlib
@@ -34,6 +40,13 @@ FVBN_SHAPES = [(d, n) for d in FVBN_D for n in FVBN_N] + [(200, 33 * TILE - 62)]
 FACTOR_N = (1, 2, 63, 64, 65, 130, 321)
 APPEND = [(1, 2), (63, 65), (64, 65), (65, 130), (130, 321)]
 SE_D = (17, 40)
+GP_KINDS = ("se", "matern32", "matern52")  # ops.GP_KINDS: 0, 1, 2
+COV_D = (1, 16, 17, 64, 70)     # the route threshold (16 | 17) and the largest d of the forced exact-difference route (64 | 70)
+INVERSE_N = (1, 63, 64, 65, 130)  # 130: three panels, a fresh row tile, a continued one, two column tiles in the update
+SUMS_N = (1, 64, 65, 130)
+SUMS_D = (1, 16, 17, 70)
+ARD_D = (1, 64, 65, 130)        # one chunk, a full chunk, two chunks, three chunks
+VALUE_N = (1, 65, 130)
 
 
 def digest(t):
@@ -178,6 +191,143 @@ def gp(dev, out):
         out[f"gp se d={d} lower no mirror"] = digest(half)
 
 
+def gp_covariance(dev, out):
+    """pg_gp_se_kernel and pg_gp_stat_kernel (every kind, shared / per-dimension lengthscales) through the C-ABI, both routes, in
+    the four forms of gp(): cross into a strided out, symmetric mirrored, lower rows at diag_offset = 70, lower without mirror."""
+    import torch
+    from pytorch_generative_amd import _lib
+    from pytorch_generative_amd.ops import gp as og
+
+    lib, st = _lib.load(), torch.cuda.current_stream().cuda_stream
+    n, m, std, noise = 130, 70, 1.3, 0.05
+    sym = og.GP_LOWER | og.GP_DIAG
+    for d in COV_D:
+        g = torch.Generator().manual_seed(300 + d)
+        a, b = strided(n, d, d + 3, g, dev), strided(m, d, d + 2, g, dev)
+        lengthscale = 0.9 * d ** 0.5
+        inv = (1.0 / (lengthscale * (0.5 + torch.rand(d, generator=g)))).to(dev)
+        entries = [("se_kernel", None, None)] + [(f"stat {k} {'ard' if w is not None else 'shared'}", c, w)
+                                                 for c, k in enumerate(GP_KINDS) for w in (None, inv)]
+        for route, flag in (("direct", og.GP_SE_DIRECT), ("mfma", og.GP_SE_MFMA)):
+            if route == "direct" and d > 64:
+                continue
+            for label, code, w in entries:
+                def run(form, left, rows, right, cols, k, off, flags):
+                    head = (left.data_ptr(), d + 3, rows, right.data_ptr(), right.stride(0), cols, d, std, lengthscale)
+                    tail = (noise, k.data_ptr(), k.stride(0), off, flags | flag, st)
+                    if code is None:
+                        _lib.check(lib.pg_gp_se_kernel(*head, *tail), "pg_gp_se_kernel")
+                    else:
+                        _lib.check(lib.pg_gp_stat_kernel(code, *head, None if w is None else w.data_ptr(), *tail), "pg_gp_stat_kernel")
+                    out[f"gp cov {label} d={d} {route} {form}"] = digest(k)
+
+                run("cross", a, n, b, m, torch.full((n, m + 9), 7.0, device=dev), 0, 0)
+                run("symmetric mirrored diag", a, n, a, n, torch.full((n, n), 7.0, device=dev), 0, sym | og.GP_MIRROR)
+                run("lower rows diag_offset=70", a[70:], n - 70, a, n, torch.full((n - 70, n), 7.0, device=dev), 70, sym)
+                run("lower no mirror", a, n, a, n, torch.full((n, n), 7.0, device=dev), 0, sym)
+
+
+def gp_factor(n, pad, dev):
+    """The lower factor of spd(n) in a buffer of row stride n + pad (7.0 beyond the row), by ops.cholesky_."""
+    import torch
+    from pytorch_generative_amd import ops
+
+    buf = torch.full((n, n + pad), 7.0)
+    buf[:, :n] = spd(n, 200 + n)
+    buf = buf.to(dev)
+    assert int(ops.cholesky_(buf[:, :n])) == 0
+    return buf
+
+
+def gp_inverse(dev, out):
+    import torch
+    from pytorch_generative_amd import ops
+
+    for n in INVERSE_N:
+        low = gp_factor(n, 3, dev)
+        x = torch.full((n, n + 5), 7.0, device=dev)
+        ops.tri_inverse_t(low[:, :n], out=x[:, :n])
+        out[f"gp tri_inverse_t n={n}"] = digest(x)
+        for mirror in (False, True):
+            h = torch.full((n, n + 2), 7.0, device=dev)
+            ops.gram_upper_(h[:, :n], x[:, :n], mirror=mirror)
+            out[f"gp gram_upper n={n} mirror={mirror}"] = digest(h)
+
+
+def gp_sums(dev, out):
+    """pg_gp_se_mll_sums, pg_gp_stat_mll_sums and pg_gp_ard_mll_sums through the C-ABI on strided operands; the digests are of
+    `out` and of the workspace rows the plan says are written. Then ops.mll_value."""
+    import torch
+    from pytorch_generative_amd import _lib, ops
+
+    lib, st = _lib.load(), torch.cuda.current_stream().cuda_stream
+    std = 1.3
+    for ard, ds in ((False, SUMS_D), (True, ARD_D)):
+        for n in SUMS_N:
+            for d in ds:
+                for p in (1, ops.gp_plan(n, 1, d, 1)["k_chunk"] + 1):
+                    g = torch.Generator().manual_seed(n * 1000 + d * 10 + p)
+                    x, at = strided(n, d, d + 3, g, dev), strided(p, n, n + 5, g, dev)
+                    h = torch.randn(n, n, generator=g)
+                    h = strided(n, n, n + 2, g, dev, fill=(h + h.t()) / n)
+                    lengthscale = 0.9 * d ** 0.5
+                    inv = (1.0 / (lengthscale * (0.5 + torch.rand(d, generator=g)))).to(dev)
+                    floats = (ops.gp_ard_plan if ard else ops.gp_mll_plan)(n, d, p)["workspace_floats"]
+                    entries = [(f"{'ard' if ard else 'stat'} {k}", c) for c, k in enumerate(GP_KINDS)] + ([] if ard else [("se_mll_sums", None)])
+                    for label, code in entries:
+                        ws, res = torch.full((floats + 4,), 7.0, device=dev), torch.full((d + 2 if ard else 3,), 7.0, device=dev)
+                        head = (x.data_ptr(), d + 3, n, d, std)
+                        tail = (h.data_ptr(), n + 2, at.data_ptr(), n + 5, p, ws.data_ptr(), floats, res.data_ptr(), st)
+                        if ard:
+                            _lib.check(lib.pg_gp_ard_mll_sums(code, *head, inv.data_ptr(), *tail), "pg_gp_ard_mll_sums")
+                        elif code is None:
+                            _lib.check(lib.pg_gp_se_mll_sums(*head, lengthscale, *tail), "pg_gp_se_mll_sums")
+                        else:
+                            _lib.check(lib.pg_gp_stat_mll_sums(code, *head, lengthscale, *tail), "pg_gp_stat_mll_sums")
+                        out[f"gp sums {label} n={n} d={d} p={p} out"] = digest(res)
+                        out[f"gp sums {label} n={n} d={d} p={p} workspace"] = digest(ws[:floats])
+    for n in VALUE_N:
+        low = gp_factor(n, 3, dev)
+        for p in (1, ops.gp_plan(n, 1, 1, 1)["k_chunk"] + 1):
+            g = torch.Generator().manual_seed(n * 10 + p)
+            zt, at = strided(p, n, n + 1, g, dev), strided(p, n, n + 4, g, dev)
+            out[f"gp mll_value n={n} p={p}"] = digest(ops.mll_value(low[:, :n], zt[:, :n], at[:, :n]))
+
+
+def gp_models(dev, out):
+    """Scalar SE, Matern 5/2 with a shared lengthscale and SE with per-dimension lengthscales, every hyperparameter a parameter:
+    fit 65 rows, predict 70 queries, fit 65 more, predict, then the evidence and its gradients. Returns the routes seen."""
+    import torch
+    from torch import nn
+    from pytorch_generative_amd.models import gaussian_process as gpm
+
+    g = torch.Generator().manual_seed(12)
+    x = 4.0 * torch.rand(130, 3, generator=g)
+    y = (torch.sin(x.sum(1, keepdim=True)) + 0.3 * torch.randn(130, 1, generator=g)).to(dev)
+    x, q = x.to(dev), (4.0 * torch.rand(70, 3, generator=g)).to(dev)
+    par = lambda v: nn.Parameter(torch.tensor(v))
+    kernels = {"se": lambda: gpm.SquaredExponential(par(1.3), par(0.7)), "matern52": lambda: gpm.Matern(2.5, par(1.3), par(0.7)),
+               "se ard": lambda: gpm.SquaredExponential(par(1.3), par([0.7, 0.9, 1.2]))}
+    routes = {}
+    for name, make in kernels.items():
+        model = gpm.GaussianProcess(gpm.Const(par(0.2)), make(), 0.1).to(dev)
+        model.noise_var.requires_grad_()
+        seen = [model._kernel_route]
+        for step, (lo, hi) in enumerate(((0, 65), (65, 130))):
+            model.fit(x[lo:hi], y[lo:hi])
+            mu, sig = model.predict(q)
+            out[f"gp model {name} predict {step} mu"], out[f"gp model {name} predict {step} sig"] = digest(mu), digest(sig)
+            seen.append(model._factor_route)
+        value = model.log_marginal_likelihood()
+        value.backward()
+        out[f"gp model {name} log p(y)"] = digest(value)
+        for label, t in (("std", model.kernel.std), ("lengthscale", model.kernel.lengthscale), ("noise_var", model.noise_var),
+                         ("value", model.mean.value)):
+            out[f"gp model {name} d/d {label}"] = digest(t.grad)
+        routes[name] = seen
+    return routes
+
+
 def compare(path_a, path_b, verdict_path):
     a, b = json.load(open(path_a)), json.load(open(path_b))
     da, db = a["digests"], b["digests"]
@@ -195,9 +345,12 @@ def main():
     ap.add_argument("--label", default=None, help="what the record calls the library, e.g. the commit it was built from")
     ap.add_argument("--compare", nargs=2, metavar=("A.json", "B.json"))
     ap.add_argument("--verdict", default=None)
+    ap.add_argument("--package", default=None, metavar="DIR", help="import pytorch_generative_amd from DIR, not from the working tree")
     a = ap.parse_args()
     if a.compare:
         sys.exit(compare(a.compare[0], a.compare[1], a.verdict))
+    if a.package:
+        sys.path[0] = os.path.abspath(a.package)
     import torch
     from pytorch_generative_amd import _lib
 
@@ -206,6 +359,11 @@ def main():
     digests = {}
     rec = {"library": a.label or os.path.basename(_lib.LIB_PATH), "device": torch.cuda.get_device_name(0), "dense_plan_branches": dense(dev, digests), "fvbn_plan_branches": fvbn(dev, digests)}
     gp(dev, digests)
+    gp_covariance(dev, digests)
+    gp_inverse(dev, digests)
+    gp_sums(dev, digests)
+    rec["gp_model_routes"] = gp_models(dev, digests)
+    rec["package"] = os.path.dirname(os.path.dirname(os.path.abspath(_lib.__file__)))
     rec["digests"] = digests
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     json.dump(rec, open(a.out, "w"), indent=1)
